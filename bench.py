@@ -1,10 +1,14 @@
 #!/usr/bin/env python
 """bench.py — BASELINE.json's headline metric on MI355X: GAN train steps/sec @32^3 voxels (+ SDFNet Mpoints/sec).
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python bench.py --gpus N --steps K --warmup W [--config wgan|hybrid_progressive|hybrid_wgan|sdf]      (self-launching)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--config ...]                                             (launcher form)
+
+A plain run sets up, warms up, times the K steps and prints the line; nothing else.  `--dump-outputs DIR` then writes what the
+last timed step computed (the arrays its caller receives, and the updated flat parameter buffers) as DIR/<name>.npy: same
+arguments, same seeded inputs, so two builds can be compared output for output.  `--full` adds the side measurements below.
 
 Both multi-GPU forms run the same thing, one process per GPU: without WORLD_SIZE in the environment `--gpus N > 1` makes this
 process the launcher (`self_launch`: N copies of itself with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / a free
@@ -22,7 +26,7 @@ behind the same harness (the multi-GPU ones are `hybrid_progressive` = configs[3
     hybrid_wgan         train_hybrid_wgan.py 32^3, batch 8/GPU: 5 critic + 1 generator updates
     sdf                 train_sdf_autodecoder.py, latent 256, 200 000 points per step per GPU (value in Mpoints/s)
 
-Rank 0 prints ONE JSON line (schema in the task contract).  At N=1 with the default config it carries
+Rank 0 prints ONE JSON line (schema in the task contract).  With `--full`, at N=1 with the default config it also carries
   `roofline`      the kernel that takes the largest share of the step (Conv3d 128->64 input-gradient / ConvTranspose3d forward
                   implicit GEMM, `conv_dgrad_halo_kernel<0>`: 22 % of the step), timed alone with HIP events on the launch
                   stream at the critic's 128-sample shape, plus `kernels`: the same measurement for every conv form of the
@@ -586,7 +590,10 @@ def make_wgan(rank, world=1, strong=False):
             "unit": "steps/s", "units_per_step": 1.0 / (world if strong else 1),
             "workload": "train_wgan.py 32^3 voxel WGAN, fp32, batch=64 synthetic SDF grids (BASELINE configs[1])",
             "batch": B, "extra": {"critic_updates_per_step": 5, "generator_updates_per_step": 1},
-            "allreduce_bytes_per_step": 4 * (5 * trainer.c_opt.f.total + trainer.g_opt.f.total)}
+            "allreduce_bytes_per_step": 4 * (5 * trainer.c_opt.f.total + trainer.g_opt.f.total),
+            # the step returns the last critic update's (loss, scores of the fake half, scores of the real half)
+            "outputs": lambda last: {"critic_loss": last[0], "critic_scores_fake": last[1], "critic_scores_real": last[2],
+                                     "critic_params": trainer.c_opt.f.flat, "generator_params": trainer.g_opt.f.flat}}
     return (lambda: trainer.step(reals, zs, zg)), info, (reals, zs, zg, state)
 
 
@@ -606,9 +613,8 @@ def make_hybrid_progressive(rank, world=1, strong=False):
     alphas = [torch.rand(B, 1, 1, 1, generator=gen).cuda() for _ in range(5)]
 
     def step():   # train_hybrid_progressive_gan.py:120-166: generator on every 5th batch (first), discriminator on every batch
-        tr.generator_step(zs[5])
-        for real, z, alpha in zip(reals, zs, alphas):
-            tr.discriminator_step(real, z, alpha)
+        g_loss = tr.generator_step(zs[5])
+        return g_loss, [tr.discriminator_step(real, z, alpha) for real, z, alpha in zip(reals, zs, alphas)]
     info = {"optimizers": [tr.d_opt, tr.g_opt],
             "metric": "hybrid progressive WGAN-GP train steps/sec @64^3 (1 generator + 5 discriminator updates, batch 16/GPU)",
             "unit": "steps/s", "units_per_step": 1.0 / (world if strong else 1),
@@ -616,7 +622,10 @@ def make_hybrid_progressive(rank, world=1, strong=False):
                         "WGAN-GP double backward, fp32, batch=16 (BASELINE configs[3])",
             "batch": B, "extra": {"discriminator_updates_per_step": 5, "generator_updates_per_step": 1},
             "allreduce_bytes_per_step": 4 * (5 * tr.d_opt.f.total + tr.g_opt.f.total),
-            "sdfnet_points": {"forward": 6 * B * R ** 3, "backward": B * R ** 3, "latent": 128}}
+            "sdfnet_points": {"forward": 6 * B * R ** 3, "backward": B * R ** 3, "latent": 128},
+            "outputs": lambda last: {"generator_loss": last[0], "discriminator_loss": torch.stack([d[0] for d in last[1]]),
+                                     "gradient_penalty": torch.stack([d[1] for d in last[1]]),
+                                     "discriminator_params": tr.d_opt.f.flat, "generator_params": tr.g_opt.f.flat}}
     return step, info, None
 
 
@@ -633,17 +642,23 @@ def make_hybrid_wgan(rank, world=1, strong=False):
     zs = [torch.randn(B, 128, generator=gen).cuda() for _ in range(6)]
 
     def step():   # train_hybrid_wgan.py:78-115: critic on every batch, generator on every 5th
+        critic, gen_out = [], None
         for i, (real, z) in enumerate(zip(reals, zs)):
-            tr.critic_step(real, z)
+            critic.append(tr.critic_step(real, z))
             if i == 0:
-                tr.generator_step(zs[5])
+                gen_out = tr.generator_step(zs[5])
+        return critic, gen_out
     info = {"optimizers": [tr.c_opt, tr.g_opt],
             "metric": "hybrid WGAN train steps/sec @32^3 (5 critic + 1 generator updates, batch 8/GPU)", "unit": "steps/s",
             "units_per_step": 1.0 / (world if strong else 1),
             "workload": "train_hybrid_wgan.py, SDFNet generator sampled to 32^3 + 3D-CNN critic, fp32, batch=8 (BASELINE configs[4])",
             "batch": B, "extra": {"critic_updates_per_step": 5, "generator_updates_per_step": 1},
             "allreduce_bytes_per_step": 4 * (5 * tr.c_opt.f.total + tr.g_opt.f.total),
-            "sdfnet_points": {"forward": 6 * B * 32 ** 3, "backward": B * 32 ** 3, "latent": 128}}
+            "sdfnet_points": {"forward": 6 * B * 32 ** 3, "backward": B * 32 ** 3, "latent": 128},
+            "outputs": lambda last: {"critic_loss": torch.stack([c[0] for c in last[0]]), "critic_scores_fake": last[0][-1][1],
+                                     "critic_scores_real": last[0][-1][2], "generator_loss": last[1][0],
+                                     "generator_scores": last[1][1], "critic_params": tr.c_opt.f.flat,
+                                     "generator_params": tr.g_opt.f.flat}}
     return step, info, None
 
 
@@ -665,7 +680,8 @@ def make_sdf(rank, world=1, strong=False):
             "workload": "train_sdf_autodecoder.py DeepSDF, latent=256, 200k (xyz,sdf) points/step, fp32 (BASELINE configs[2])",
             "batch": npts, "extra": {},
             "allreduce_bytes_per_step": 4 * (tr.net_opt.f.total + tr.lat_opt.f.total),
-            "sdfnet_points": {"forward": npts, "backward": npts, "latent": lat}}
+            "sdfnet_points": {"forward": npts, "backward": npts, "latent": lat},
+            "outputs": lambda loss: {"loss": loss, "net_params": tr.net_opt.f.flat, "latent_codes": tr.lat_opt.f.flat}}
     return (lambda: tr.step(idx)), info, None
 
 
@@ -744,6 +760,33 @@ def replica_digests(optimizers, world):
 
 
 WORKLOADS = {"wgan": make_wgan, "hybrid_progressive": make_hybrid_progressive, "hybrid_wgan": make_hybrid_wgan, "sdf": make_sdf}
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs writes at most this much in all
+DUMP_SAMPLE = 1 << 22           # an output with more elements is written as a fixed, seeded sample of this many
+
+
+def write_outputs(outdir, arrays):
+    """--dump-outputs: every tensor of `arrays` (name -> tensor) as outdir/<name>.npy, float64 kept, everything else as float32.
+    An array of more than DUMP_SAMPLE elements is written flattened, as the elements at DUMP_SAMPLE sorted positions drawn with
+    a fixed seed (the same positions in every run of the same configuration).  Returns {name: (shape written, sampled)}."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    prepared, total = {}, 0
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        sampled = t.numel() > DUMP_SAMPLE
+        if sampled:
+            flat = t.reshape(-1)
+            pick = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            t = flat[pick.to(flat.device)]
+        a = t.cpu().numpy()
+        total += a.nbytes
+        prepared[name] = (a, sampled)
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("bench.py --dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    for name, (a, _) in prepared.items():
+        np.save(os.path.join(outdir, name + ".npy"), a, allow_pickle=False)
+    return {name: (a.shape, sampled) for name, (a, sampled) in prepared.items()}
 
 
 def self_launch(gpus, argv, script=None):
@@ -804,20 +847,34 @@ def self_launch(gpus, argv, script=None):
     return rc
 
 
-def main():
-    if len(sys.argv) > 1 and sys.argv[1] == "--cpu-replica":
-        return _cpu_replica_main(sys.argv[2:])
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", choices=sorted(WORKLOADS), default="wgan")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak (default, the headline): every GPU runs the reference's own batch; strong: the reference's batch is "
                          "split over the GPUs (64 -> 64/N samples, 16 -> 16/N shapes, 200 000 -> 200 000/N points per GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline / SDFNet side measurements")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements of the N = 1 wgan line (roofline, per-kernel table, SDFNet, other configs, "
+                         "drop-in loop, CPU baseline); off by default: a plain run times the steps and nothing else")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip roofline / SDFNet / other-config side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--cpu-replica":
+        return _cpu_replica_main(sys.argv[2:])
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))        # this process becomes the launcher of N ranks
@@ -848,9 +905,13 @@ def main():
         parallel.EXPOSED.enable()      # event pairs around every wait for a gradient exchange (two event records each)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # before anything else runs the step again (the --full side measurements do)
+        for name, (shape, sampled) in write_outputs(args.dump_outputs, info["outputs"](last)).items():
+            print("bench.py: wrote %s.npy %s%s" % (name, list(shape), " (seeded sample)" if sampled else ""), file=sys.stderr)
     digests, exposed = None, None
     if world > 1:
         t = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
@@ -896,7 +957,7 @@ def main():
             line["comm"]["parameter_digests_rank0"] = digests[0]
         if args.config == "wgan":
             line["critic_updates_per_s"] = round(world * args.steps * 5 / elapsed, 3)
-            if world == 1 and not args.no_extras:
+            if args.full and world == 1 and not args.no_extras:
                 # single-kernel and side measurements belong to the N = 1 line only: at N > 1 the other ranks would sit in the
                 # closing barrier while rank 0 measures
                 line["roofline"], line["kernels"] = roofline_and_kernels()
@@ -906,7 +967,7 @@ def main():
                 line["dropin_loop"]["trainer_step_launches_per_step"] = _count_launches(step)
                 for k in ("resident_batches", "host_batches_copied_in_the_loop"):
                     line["dropin_loop"][k]["fraction_of_trainer_step"] = round(line["dropin_loop"][k]["steps_per_s"] / line["value"], 4)
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 reals, zs, zg, (g_state, c_state) = wgan_data
                 line["cpu_baseline"] = cpu_baseline(reals, zs, zg, g_state, c_state)
         print(json.dumps(line), flush=True)

@@ -105,7 +105,7 @@ def md_tables():
     bl = os.path.join(dst, tag + "_bench_line.json")
     if os.path.exists(bl):
         d = json.loads([ln for ln in open(bl).read().splitlines() if ln.startswith("{")][-1])
-        L += ["### `%s_bench_line.json` (`python bench.py`, N = 1)" % tag, "",
+        L += ["### `%s_bench_line.json` (`python bench.py --full`, N = 1)" % tag, "",
               "| quantity | value |", "|---|---|",
               "| %s | **%.2f %s** (%.3f ms per step) |" % (d["metric"], d["value"], d["unit"], d["ms_per_step"]),
               "| roofline kernel | %s: %.1f %s of %.1f = **%.3f** |" % (d["roofline"]["kernel"].split(" (")[0], d["roofline"]["achieved"],

@@ -3,7 +3,7 @@
 out=gpurun_out/${1:-pass}; mkdir -p $out
 timeout 1500 python -m pytest tests/test_gpu_ops.py tests/test_gpu_fullsize.py tests/test_gpu_modules.py -x -q -m gpu > $out/pytest.log 2>&1; echo "pytest rc=$?"; tail -3 $out/pytest.log
 python scripts/edge_ab.py > $out/edge.json 2> $out/edge.err; cat $out/edge.json
-timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
 python - $out <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1]+'/bench.json'))

@@ -16,7 +16,7 @@ run_pmc() {  # name, counters, command...
   rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d /tmp/sgprof/$name -o $name -- "$@" > $out/$name.log 2>&1
   f=$(find /tmp/sgprof/$name -name "*counter_collection.csv" | head -1); [ -n "$f" ] && cp $f $out/${name}_counters.csv
 }
-run_stats bench python $repo/bench.py --steps 5 --warmup 1 --no-cpu-baseline
+run_stats bench python $repo/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline
 run_stats wgan_step python $repo/bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-extras
 run_stats sdf_train python $repo/scripts/sdf_train_bench.py
 run_stats hybrid_progressive python $repo/bench.py --config hybrid_progressive --steps 2 --warmup 1 --no-cpu-baseline --no-extras
@@ -42,7 +42,7 @@ python scripts/point_gan_bench.py > $out/${tag}_point_gan_bench.txt 2> $out/poin
 # the plane-streaming ConvT(64 -> 1) kernel alone: SQ / TCC / LDS counter groups at 64, 32 (old kernel) and 256 samples
 bash scripts/convt_pmc.sh > $out/${tag}_convT_c1_counters.txt 2> $out/convt_pmc.err
 # the driver's own command, and the rehearsal of its multi-GPU form on this one GPU (gloo, two ranks on cuda:0)
-python bench.py > $out/${tag}_bench_line.json 2> $out/bench_line.err
+python bench.py --full > $out/${tag}_bench_line.json 2> $out/bench_line.err
 SG_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 5 --warmup 2 --no-extras > $out/${tag}_bench_line_2ranks_gloo_one_gpu.json 2> $out/bench_2ranks.err
 # ordered launch lists of one steady-state step
 bash scripts/timeline_run.sh > $out/timeline.log 2>&1

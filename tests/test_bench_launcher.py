@@ -90,3 +90,39 @@ def test_cpu_baseline_fills_all_cores_with_pinned_replicas(monkeypatch):
     agg = bench._cpu_replicas(2, 2, 1, reals, zs, zg, g_state, c_state)
     assert agg is not None and agg["replicas"] == 2 and agg["steps_each"] == 1
     assert agg["steps_per_s"] > 0 and abs(agg["steps_per_s"] - 2 * 1 / agg["slowest_s"]) < 1e-2 * agg["steps_per_s"]
+
+
+def test_a_plain_run_times_the_steps_only_and_refuses_zero_steps():
+    """`python bench.py --gpus 1 --steps K --warmup W`: no side measurements unless --full, no dump unless --dump-outputs, and
+    --steps is the number of timed steps, so it must be at least one."""
+    import pytest
+    args = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (args.steps, args.warmup, args.full, args.dump_outputs, args.config) == (7, 2, False, None, "wgan")
+    assert bench.parse_args(["--full", "--dump-outputs", "d"]).full and bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_of_large_ones(tmp_path, monkeypatch):
+    import numpy as np
+    import pytest
+    import torch
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    big = torch.arange(5000, dtype=torch.float32).reshape(50, 100)
+    arrays = {"loss": torch.tensor(0.5), "scores": torch.linspace(-1, 1, 64).reshape(64, 1), "wide": torch.ones(3, dtype=torch.float64),
+              "counts": torch.arange(4), "params": big}
+    info = bench.write_outputs(str(tmp_path / "a"), arrays)
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == sorted(k + ".npy" for k in arrays)
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in arrays}
+    assert got["loss"].dtype == np.float32 and got["loss"].shape == () and float(got["loss"]) == 0.5
+    np.testing.assert_array_equal(got["scores"], arrays["scores"].numpy())
+    assert got["wide"].dtype == np.float64 and got["counts"].dtype == np.float32
+    assert info["params"] == ((1000,), True) and info["scores"] == ((64, 1), False)
+    sample = got["params"]           # the values of an arange are their positions: distinct, sorted, in range
+    assert len(np.unique(sample)) == 1000 and np.all(np.diff(sample) > 0) and sample[0] >= 0 and sample[-1] < 5000
+    bench.write_outputs(str(tmp_path / "b"), arrays)
+    np.testing.assert_array_equal(np.load(str(tmp_path / "b" / "params.npy")), sample)      # the same positions every run
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    with pytest.raises(ValueError):
+        bench.write_outputs(str(tmp_path / "c"), arrays)

@@ -104,3 +104,43 @@ def test_native_exchange_refuses_two_ranks_on_one_device_loudly_and_uniformly():
     comm = _check_line(line, "wgan")
     assert comm["transport"] == "torch-gloo" and comm["reason"].startswith("fallback: ")
     assert err.count("FALLING BACK to torch.distributed all-reduce") == 2, err[-3000:]      # one message per rank
+
+
+def _run_plain(dump_dir, steps=3, warmup=1):
+    """The N = 1 command as it is run for every change: `python bench.py --gpus 1 --steps K --warmup W`, here with --dump-outputs."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(dump_dir)]
+    res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, "%s failed (%d):\n%s\n%s" % (" ".join(cmd), res.returncode, res.stdout[-2000:], res.stderr[-4000:])
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run prints the headline line without the --full side measurements; --steps is the number of timed steps; the
+    dump holds the last step's loss and 2 x 64 critic scores and the updated parameter buffers, and a second run with the same
+    arguments computes the same (the inputs are seeded)."""
+    import numpy as np
+    line = _run_plain(tmp_path / "a")
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["unit"] == "steps/s" and line["ms_per_step"] > 0
+    assert abs(line["value"] - 1e3 / line["ms_per_step"]) <= 2e-3 * line["value"]
+    for key in ("roofline", "kernels", "sdfnet", "other_configs", "dropin_loop", "cpu_baseline"):
+        assert key not in line, key + " belongs to --full"
+    names = {"critic_loss": (), "critic_scores_fake": (64,), "critic_scores_real": (64,), "critic_params": None,
+             "generator_params": None}
+    a = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in names}
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k, shape in names.items():
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        assert shape is None or a[k].shape == shape, (k, a[k].shape)
+    mean_difference = float(np.mean(a["critic_scores_fake"], dtype=np.float64) - np.mean(a["critic_scores_real"], dtype=np.float64))
+    assert abs(float(a["critic_loss"]) - mean_difference) <= 1e-5 * max(1.0, abs(mean_difference))
+    assert np.abs(a["critic_params"]).max() <= 0.01 + 1e-7          # the fused weight clip of train_wgan.py
+    _run_plain(tmp_path / "b")
+    for k in names:
+        b = np.load(str(tmp_path / "b" / (k + ".npy")))
+        assert b.shape == a[k].shape, k
+        bad = np.abs(b - a[k]) > 1e-6 + 1e-3 * np.abs(a[k])
+        assert float(bad.mean()) <= 1e-3, "%s differs between two runs with the same arguments" % k
