@@ -533,6 +533,42 @@ int sg_scatter_max_fwd(const float* x, const int64_t* batch, float* out, int* ar
 int sg_scatter_max_scatter(const float* dy, const int* arg, float* dx, long N, long B, int C, hipStream_t stream);
 int sg_scatter_max_gather(const float* x, const int* arg, float* out, long N, long B, int C, hipStream_t stream);
 
+/* ---- K12: batched marching cubes and surface sampling ---------------------------------------------------------------------
+ * reference: SDFNet.get_mesh / get_uniform_surface_points, model/sdf_net.py:97-116 (skimage.measure.marching_cubes_lewiner, then
+ *            trimesh.Trimesh(...).sample), and metrics.py:31-46 (sample_point_clouds / sample_from_voxels: the same per shape, in a
+ *            Python loop) -> S grids meshed and sampled on the device in a handful of launches.
+ * grids [S][R0][R1][R2] fp32.  pad = 1 surrounds every grid with a virtual shell of one cell of value pad_value (the reference's
+ * np.pad(voxels, 1, constant_values=1)); the grid seen by the meshing then has P_k = R_k + 2 pad corners along axis k and the
+ * padded index 0 is the shell.  A corner is inside when v < level; one vertex per grid edge that crosses the level, shared by
+ * the triangles of every cell around that edge (welded), at t = (level - a) / (b - a) from the corner of lower index:
+ *   position[k] = (index[k] + t [k == edge axis]) * spacing[k] + origin[k]          (index in the padded grid),
+ *   normal = the central-difference gradient of the padded grid (one-sided at its outermost layer, divided by spacing), interpolated
+ *            with t and normalised: it points toward increasing values, outward for an SDF; (v1 - v0) x (v2 - v0) of every
+ *            triangle does too.  Ambiguous cube faces always separate their two inside corners (csrc/mc_tables.h), so every closed
+ *            surface comes out watertight.
+ * Order (deterministic, no atomics): vertices by owning corner (row-major over the padded corners), then by the axis (0, 1, 2) of
+ * the edge it owns toward +1; triangles by cell (row-major), then in table order.  vert_offsets / tri_offsets [S+1] (int64): shape
+ * s owns vertices [vert_offsets[s], vert_offsets[s+1]) and triangles [tri_offsets[s], tri_offsets[s+1]); faces [F][3] (int64)
+ * are local to their shape.  Int32 indices inside: S * P0 * P1 * P2 * 24 must not exceed 2^31 - 1 (SG_ERR_ARG; split the batch).
+ * sg_mc_count writes the offsets (and keeps per-workgroup offsets in `workspace`); the caller reads the totals vert_offsets[S],
+ * tri_offsets[S] to size the outputs and then calls sg_mc_emit with the same grids, arguments and workspace.  max_verts /
+ * max_tris: the capacity of vertices / normals [max_verts][3] and faces [max_tris][3]; nothing is written beyond them. */
+size_t sg_mc_workspace_bytes(long S, int R0, int R1, int R2, int pad);
+int sg_mc_count(const float* grids, long S, int R0, int R1, int R2, float level, int pad, float pad_value, int64_t* vert_offsets,
+                int64_t* tri_offsets, void* workspace, size_t workspace_bytes, hipStream_t stream);
+int sg_mc_emit(const float* grids, long S, int R0, int R1, int R2, float level, int pad, float pad_value, float spacing0,
+               float spacing1, float spacing2, float origin0, float origin1, float origin2, const int64_t* vert_offsets,
+               const int64_t* tri_offsets, float* vertices, float* normals, int64_t* faces, long max_verts, long max_tris,
+               void* workspace, size_t workspace_bytes, hipStream_t stream);
+/* Area-weighted surface sampling of the packed meshes above (trimesh.sample): P points per shape from caller-supplied uniforms
+ * [S][P][3] (u0, u1, u2).  Per shape: the cumulative triangle areas in double; triangle = the first whose cumulative area reaches
+ * u0 * total (numpy.searchsorted), point = v0 + (u1 (v1 - v0) + u2 (v2 - v0)) with (u1, u2) -> (1 - u1, 1 - u2) when u1 + u2 > 1.
+ * out [S][P][3]; a shape without triangles gets zeros and empty[s] = 1 (0 otherwise).  F = tri_offsets[S]. */
+size_t sg_mesh_sample_workspace_bytes(long S, long F);
+int sg_mesh_sample(const float* vertices, const int64_t* faces, const int64_t* vert_offsets, const int64_t* tri_offsets, long S,
+                   long F, const float* uniforms, long P, float* out, int* empty, void* workspace, size_t workspace_bytes,
+                   hipStream_t stream);
+
 /* ---- data-parallel gradient exchange: libshapegan_comm.so ----------------------------------------------
  * reference: nn.DataParallel's gradient reduce-add, train_hybrid_progressive_gan.py:62-68.  One process per GPU; one
  * ncclAllReduce(sum, fp32) of a slice of the flat gradient buffer per call, on the communicator's own stream, ordered after

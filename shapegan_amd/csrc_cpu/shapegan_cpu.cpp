@@ -19,6 +19,8 @@
 #include <algorithm>
 #include <vector>
 
+#include "../csrc/mc_tables.h"
+
 typedef void* hipStream_t_;
 #define SG_OK 0
 #define SG_SDFNET_PARTIAL_ROW (14 * 256 + 32)   // include/shapegan_hip.h (the twin does not include the HIP header)
@@ -1646,6 +1648,224 @@ int sg_scatter_max_scatter_cpu(const float* dy, const int* arg, float* dx, long 
 int sg_scatter_max_gather_cpu(const float* x, const int* arg, float* out, long N, long B, int C, void*) {
     CPU_CHECK(x && arg && out && N > 0 && B > 0 && C > 0);
     for (long e = 0; e < B * C; ++e) out[e] = arg[e] >= 0 ? x[(long)arg[e] * C + e % C] : 0.f;
+    return SG_OK;
+}
+
+// ---- K12: marching cubes and surface sampling (csrc/mesh.hip) ------------------------------------------------------------------
+// The same cells in the same order as the kernels: the corners of the (virtually padded) grid in row-major order, each owning the
+// crossing edges at its minimum corner (axes 0, 1, 2) and, where it exists, the cube with that minimum corner.
+struct McGridCpu {
+    const float* g;
+    int R0, R1, R2, P0, P1, P2, pad;
+    float pad_value, level;
+    float value(int a, int b, int c) const {
+        if (pad) {
+            a -= 1;
+            b -= 1;
+            c -= 1;
+            if ((unsigned)a >= (unsigned)R0 || (unsigned)b >= (unsigned)R1 || (unsigned)c >= (unsigned)R2) return pad_value;
+        }
+        return g[((long)a * R1 + b) * R2 + c];
+    }
+    // case bits of the cell at (a, b, c) (corners outside the grid read as pad_value), owned-edge crossing mask, cube or -1
+    void classify(int a, int b, int c, float v[8], int& mask, int& cube) const {
+        int cs = 0;
+        for (int n = 0; n < 8; ++n) {
+            const int x = a + ((n >> 2) & 1), y = b + ((n >> 1) & 1), z = c + (n & 1);
+            v[n] = (x < P0 && y < P1 && z < P2) ? value(x, y, z) : pad_value;
+            cs |= (v[n] < level ? 1 : 0) << n;
+        }
+        const int in0 = cs & 1;
+        mask = 0;
+        if (a + 1 < P0 && in0 != ((cs >> 4) & 1)) mask |= 1;
+        if (b + 1 < P1 && in0 != ((cs >> 2) & 1)) mask |= 2;
+        if (c + 1 < P2 && in0 != ((cs >> 1) & 1)) mask |= 4;
+        cube = (a + 1 < P0 && b + 1 < P1 && c + 1 < P2) ? cs : -1;
+    }
+    float grad(int a, int b, int c, int axis, float spacing) const {
+        const int p = axis == 0 ? a : axis == 1 ? b : c;
+        const int P = axis == 0 ? P0 : axis == 1 ? P1 : P2;
+        const int lo = p > 0 ? p - 1 : p, hi = p < P - 1 ? p + 1 : p;
+        if (hi == lo) return 0.f;
+        float vl, vh;
+        if (axis == 0) {
+            vl = value(lo, b, c);
+            vh = value(hi, b, c);
+        } else if (axis == 1) {
+            vl = value(a, lo, c);
+            vh = value(a, hi, c);
+        } else {
+            vl = value(a, b, lo);
+            vh = value(a, b, hi);
+        }
+        return (vh - vl) / ((float)(hi - lo) * spacing);
+    }
+};
+
+static bool mc_setup_cpu(McGridCpu& m, const float* grids, long S, int R0, int R1, int R2, float level, int pad, float pad_value,
+                         long& cells) {
+    if (!grids || S <= 0 || R0 <= 0 || R1 <= 0 || R2 <= 0 || (pad != 0 && pad != 1)) return false;
+    m.g = grids;
+    m.R0 = R0;
+    m.R1 = R1;
+    m.R2 = R2;
+    m.P0 = R0 + 2 * pad;
+    m.P1 = R1 + 2 * pad;
+    m.P2 = R2 + 2 * pad;
+    m.pad = pad;
+    m.pad_value = pad_value;
+    m.level = level;
+    cells = (long)m.P0 * m.P1 * m.P2;
+    const long lim = 2147483647L / 24;     // the index limit of include/shapegan_hip.h
+    return cells <= lim && S <= lim / cells;
+}
+
+int sg_mc_count_cpu(const float* grids, long S, int R0, int R1, int R2, float level, int pad, float pad_value, int64_t* vert_offsets,
+                    int64_t* tri_offsets, void*, size_t, void*) {
+    McGridCpu m;
+    long cells = 0;
+    CPU_CHECK(mc_setup_cpu(m, grids, S, R0, R1, R2, level, pad, pad_value, cells));
+    CPU_CHECK(vert_offsets && tri_offsets);
+    std::vector<int64_t> nv(S), nt(S);
+#pragma omp parallel for schedule(dynamic)
+    for (long s = 0; s < S; ++s) {
+        McGridCpu ms = m;
+        ms.g = grids + s * (long)R0 * R1 * R2;
+        int64_t v = 0, t = 0;
+        float val[8];
+        for (int a = 0; a < m.P0; ++a)
+            for (int b = 0; b < m.P1; ++b)
+                for (int c = 0; c < m.P2; ++c) {
+                    int mask, cube;
+                    ms.classify(a, b, c, val, mask, cube);
+                    v += __builtin_popcount(mask);
+                    t += cube >= 0 ? sg_mc_tri_count[cube] : 0;
+                }
+        nv[s] = v;
+        nt[s] = t;
+    }
+    vert_offsets[0] = tri_offsets[0] = 0;
+    for (long s = 0; s < S; ++s) {
+        vert_offsets[s + 1] = vert_offsets[s] + nv[s];
+        tri_offsets[s + 1] = tri_offsets[s] + nt[s];
+    }
+    return SG_OK;
+}
+
+int sg_mc_emit_cpu(const float* grids, long S, int R0, int R1, int R2, float level, int pad, float pad_value, float sx, float sy,
+                   float sz, float ox, float oy, float oz, const int64_t* vert_offsets, const int64_t* tri_offsets, float* vertices,
+                   float* normals, int64_t* faces, long max_verts, long max_tris, void*, size_t, void*) {
+    McGridCpu m;
+    long cells = 0;
+    CPU_CHECK(mc_setup_cpu(m, grids, S, R0, R1, R2, level, pad, pad_value, cells));
+    CPU_CHECK(vert_offsets && tri_offsets && max_verts >= 0 && max_tris >= 0);
+    CPU_CHECK((max_verts == 0 || (vertices && normals)) && (max_tris == 0 || faces));
+    CPU_CHECK(vert_offsets[S] <= max_verts && tri_offsets[S] <= max_tris);
+    const float sp[3] = {sx, sy, sz}, org[3] = {ox, oy, oz};
+#pragma omp parallel for schedule(dynamic)
+    for (long s = 0; s < S; ++s) {
+        McGridCpu ms = m;
+        ms.g = grids + s * (long)R0 * R1 * R2;
+        std::vector<int> first(cells), owned(cells);      // per cell: first vertex (local to the shape), crossing mask
+        long vo = 0, to = 0;
+        float v[8];
+        long cell = 0;
+        for (int a = 0; a < m.P0; ++a)
+            for (int b = 0; b < m.P1; ++b)
+                for (int c = 0; c < m.P2; ++c, ++cell) {
+                    int mask, cube;
+                    ms.classify(a, b, c, v, mask, cube);
+                    first[cell] = (int)vo;
+                    owned[cell] = mask;
+                    if (!mask) continue;
+                    const int idx[3] = {a, b, c};
+                    float g0[3];
+                    for (int k = 0; k < 3; ++k) g0[k] = ms.grad(a, b, c, k, sp[k]);
+                    for (int axis = 0; axis < 3; ++axis) {
+                        if (!((mask >> axis) & 1)) continue;
+                        const float va = v[0], vb = v[axis == 0 ? 4 : axis == 1 ? 2 : 1];
+                        const float t = (level - va) / (vb - va);
+                        const int a1 = a + (axis == 0), b1 = b + (axis == 1), c1 = c + (axis == 2);
+                        float n[3];
+                        for (int k = 0; k < 3; ++k) {
+                            const float g1 = ms.grad(a1, b1, c1, k, sp[k]);
+                            n[k] = g0[k] + t * (g1 - g0[k]);
+                        }
+                        const float len = sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+                        const long out = vert_offsets[s] + vo;
+                        for (int k = 0; k < 3; ++k) {
+                            vertices[out * 3 + k] = ((float)idx[k] + (k == axis ? t : 0.f)) * sp[k] + org[k];
+                            normals[out * 3 + k] = len > 0.f ? n[k] / len : 0.f;
+                        }
+                        ++vo;
+                    }
+                }
+        const long plane = (long)m.P1 * m.P2;
+        cell = 0;
+        for (int a = 0; a < m.P0; ++a)
+            for (int b = 0; b < m.P1; ++b)
+                for (int c = 0; c < m.P2; ++c, ++cell) {
+                    int mask, cube;
+                    ms.classify(a, b, c, v, mask, cube);
+                    if (cube < 0) continue;
+                    for (int j = 0; j < sg_mc_tri_count[cube]; ++j) {
+                        const long f = tri_offsets[s] + to + j;
+                        for (int k = 0; k < 3; ++k) {
+                            const int e = sg_mc_tri_edges[cube][3 * j + k];
+                            const int axis = e >> 2, u = (e >> 1) & 1, w = e & 1;
+                            const int oa = axis == 0 ? 0 : u, ob = axis == 1 ? 0 : (axis == 0 ? u : w), oc = axis == 2 ? 0 : w;
+                            const long owner = (long)(a + oa) * plane + (long)(b + ob) * m.P2 + (c + oc);
+                            faces[f * 3 + k] = first[owner] + __builtin_popcount(owned[owner] & ((1 << axis) - 1));
+                        }
+                    }
+                    to += sg_mc_tri_count[cube];
+                }
+    }
+    return SG_OK;
+}
+
+int sg_mesh_sample_cpu(const float* vertices, const int64_t* faces, const int64_t* vert_offsets, const int64_t* tri_offsets, long S,
+                       long F, const float* uniforms, long P, float* out, int* empty, void*, size_t, void*) {
+    CPU_CHECK(vert_offsets && tri_offsets && uniforms && out && empty && S > 0 && P > 0 && F >= 0);
+    CPU_CHECK(F == 0 || (vertices && faces));
+#pragma omp parallel for schedule(dynamic)
+    for (long s = 0; s < S; ++s) {
+        const long f0 = tri_offsets[s], f1 = tri_offsets[s + 1], vb = vert_offsets[s];
+        empty[s] = f1 > f0 ? 0 : 1;
+        if (f1 <= f0) {
+            memset(out + s * P * 3, 0, sizeof(float) * P * 3);
+            continue;
+        }
+        // cumulative doubled areas in double, added in triangle order
+        std::vector<double> cdf(f1 - f0);
+        double run = 0.0;
+        for (long f = f0; f < f1; ++f) {
+            const float* p0 = vertices + (vb + faces[f * 3]) * 3;
+            const float* p1 = vertices + (vb + faces[f * 3 + 1]) * 3;
+            const float* p2 = vertices + (vb + faces[f * 3 + 2]) * 3;
+            const double ax = (double)p1[0] - (double)p0[0], ay = (double)p1[1] - (double)p0[1], az = (double)p1[2] - (double)p0[2];
+            const double bx = (double)p2[0] - (double)p0[0], by = (double)p2[1] - (double)p0[1], bz = (double)p2[2] - (double)p0[2];
+            const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+            run += sqrt(cx * cx + cy * cy + cz * cz);
+            cdf[f - f0] = run;
+        }
+        for (long q = 0; q < P; ++q) {
+            const long i = s * P + q;
+            const float u0 = uniforms[i * 3], u1 = uniforms[i * 3 + 1], u2 = uniforms[i * 3 + 2];
+            const double x = (double)u0 * cdf.back();
+            const long k = std::min((long)(std::lower_bound(cdf.begin(), cdf.end(), x) - cdf.begin()), f1 - f0 - 1);
+            const long f = f0 + k;
+            const float* p0 = vertices + (vb + faces[f * 3]) * 3;
+            const float* p1 = vertices + (vb + faces[f * 3 + 1]) * 3;
+            const float* p2 = vertices + (vb + faces[f * 3 + 2]) * 3;
+            float p = u1, r = u2;
+            if (p + r > 1.f) {
+                p = 1.f - p;
+                r = 1.f - r;
+            }
+            for (int c = 0; c < 3; ++c) out[i * 3 + c] = p0[c] + (p * (p1[c] - p0[c]) + r * (p2[c] - p0[c]));
+        }
+    }
     return SG_OK;
 }
 

@@ -158,6 +158,11 @@ SIGNATURES = {
     "sg_scatter_max_fwd": (c_int, [_P, _P, _P, _P, _L, _L, _I, _P, _Z, _P]),
     "sg_scatter_max_scatter": (c_int, [_P, _P, _P, _L, _L, _I, _P]),
     "sg_scatter_max_gather": (c_int, [_P, _P, _P, _L, _L, _I, _P]),
+    "sg_mc_workspace_bytes": (_Z, [_L, _I, _I, _I, _I]),
+    "sg_mc_count": (c_int, [_P, _L, _I, _I, _I, _F, _I, _F, _P, _P, _P, _Z, _P]),
+    "sg_mc_emit": (c_int, [_P, _L, _I, _I, _I, _F, _I, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _L, _L, _P, _Z, _P]),
+    "sg_mesh_sample_workspace_bytes": (_Z, [_L, _L]),
+    "sg_mesh_sample": (c_int, [_P, _P, _P, _P, _L, _L, _P, _L, _P, _P, _P, _Z, _P]),
 }
 
 # libshapegan_comm.so (RCCL gradient exchange; loaded only by data-parallel runs that ask for it)

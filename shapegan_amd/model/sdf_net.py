@@ -8,6 +8,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..mesh import marching_cubes
 from ..util import get_points_in_unit_sphere, get_voxel_coordinates
 from . import LATENT_CODE_SIZE, LATENT_CODES_FILENAME, SavableModule  # noqa: F401  (re-exported: train_sdf_autodecoder.py:13)
 
@@ -97,12 +98,15 @@ class SDFNet(SavableModule):
                 result[begin:begin + chunk.shape[0]] = self.forward_shapes(chunk, z, chunk.shape[0])
         return result.cpu() if return_cpu_tensor else result
 
-    def get_voxels(self, latent_code, voxel_resolution, sphere_only=True, pad=True):
-        """SDF voxel grid; outside the |p|<1.1 sphere the grid is 1 (model/sdf_net.py:77-95)."""
+    def _helper(self, voxel_resolution, sphere_only):
         key = (voxel_resolution, sphere_only)
         if key not in sdf_voxelization_helper:
             sdf_voxelization_helper[key] = SDFVoxelizationHelperData(self.device, voxel_resolution, sphere_only)
-        helper = sdf_voxelization_helper[key]
+        return sdf_voxelization_helper[key]
+
+    def get_voxels(self, latent_code, voxel_resolution, sphere_only=True, pad=True):
+        """SDF voxel grid; outside the |p|<1.1 sphere the grid is 1 (model/sdf_net.py:77-95)."""
+        helper = self._helper(voxel_resolution, sphere_only)
         distances = self.evaluate_in_batches(helper.sample_points, latent_code).numpy()
         if sphere_only:
             voxels = np.ones((voxel_resolution,) * 3, dtype=np.float32)
@@ -113,8 +117,56 @@ class SDFNet(SavableModule):
                 voxels = np.pad(voxels, 1, mode='constant', constant_values=1)
         return voxels
 
-    def get_mesh(self, *args, **kwargs):
-        raise NotImplementedError("marching cubes (skimage/trimesh, model/sdf_net.py:97-112) is outside the hot path")
+    def grid_values(self, latent_codes, points):
+        """SDF of every shape at every point of one shared grid: latent_codes [S,L], points [P,3] -> [S,P] on the points' device.
+        One sg_sdfnet_fwd launch with points_period = P: the grid is not tiled S times."""
+        z = ops.f32c(latent_codes.detach().reshape(-1, self.latent_code_size))
+        points = ops.f32c(points)
+        S, P = z.shape[0], points.shape[0]
+        with torch.no_grad():
+            packed, zb1, zb5 = self._pack_shapes.get_with_fold(self._params(), z)
+            out = torch.empty((S, P), dtype=torch.float32, device=points.device)
+            lib = ops._lib()
+            ops.check(lib.sg_sdfnet_fwd(ops.ptr(points), P, None, None, z.shape[1], ops.ptr(packed), 3, ops.ptr(zb1), ops.ptr(zb5), P,
+                                        None, ops.ptr(out), None, S * P, S * P, ops.stream()), "sdfnet_fwd")
+        return out
+
+    def voxel_grids(self, latent_codes, voxel_resolution, sphere_only=True, pad=True):
+        """get_voxels for a batch of latent codes [S,L], built on the device without a host round trip: [S,R,R,R], or
+        [S,R+2,R+2,R+2] when not sphere_only and pad (the same values as get_voxels, shape by shape)."""
+        helper = self._helper(voxel_resolution, sphere_only)
+        R = voxel_resolution
+        d = self.grid_values(latent_codes, helper.sample_points)
+        S = d.shape[0]
+        if sphere_only:
+            if getattr(helper, "unit_sphere_mask_t", None) is None or helper.unit_sphere_mask_t.device != d.device:
+                helper.unit_sphere_mask_t = torch.from_numpy(helper.unit_sphere_mask.reshape(-1)).to(d.device)
+            grids = torch.ones((S, R * R * R), dtype=torch.float32, device=d.device)
+            grids[:, helper.unit_sphere_mask_t] = d
+            return grids.view(S, R, R, R)
+        grids = d.view(S, R, R, R)
+        if pad:
+            grids = torch.nn.functional.pad(grids, (1, 1, 1, 1, 1, 1), mode='constant', value=1.0)
+        return grids
+
+    def get_mesh(self, latent_code, voxel_resolution=64, sphere_only=True, raise_on_empty=False, level=0):
+        """Marching cubes of the SDF grid (model/sdf_net.py:97-112) on the device: a mesh.Mesh, None when the grid does not cross
+        `level` (ValueError with raise_on_empty).  Coordinates are the reference's: the grid of get_voxels padded once more with
+        1, spacing 2 / R, shifted by -1 — grid index i lands at (i + 1 + t) 2/R - 1 (sphere_only) or (i + 2 + t) 2/R - 1 (the
+        grid get_voxels pads itself)."""
+        size = 2
+        grids = self.voxel_grids(latent_code.reshape(1, -1), voxel_resolution, sphere_only=sphere_only)
+        batch = marching_cubes(grids, level=level, spacing=size / voxel_resolution, origin=-size / 2, pad=True, pad_value=1.0)
+        if batch.faces.shape[0] == 0:
+            if raise_on_empty:
+                raise ValueError("Surface level must be within volume data range.")
+            return None
+        return batch.mesh(0)
+
+    def get_uniform_surface_points(self, latent_code, point_count=1000, voxel_resolution=64, sphere_only=True, level=0):
+        """get_mesh(...).sample(point_count) (model/sdf_net.py:114-116): AttributeError when the mesh is empty, as there."""
+        mesh = self.get_mesh(latent_code, voxel_resolution=voxel_resolution, sphere_only=sphere_only, level=level)
+        return mesh.sample(point_count)
 
     def get_normals(self, latent_code, points):
         """d sdf / d points, normalised (model/sdf_net.py:118-128)."""
