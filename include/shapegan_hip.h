@@ -569,6 +569,55 @@ int sg_mesh_sample(const float* vertices, const int64_t* faces, const int64_t* v
                    long F, const float* uniforms, long P, float* out, int* empty, void* workspace, size_t workspace_bytes,
                    hipStream_t stream);
 
+/* ---- sphere tracing of SDFNet shapes (rendering/raymarching.py:render_image, get_shadows) ----------------------------------
+ * S images of the same camera, M = width^2 pixels each; ray r = s * M + pixel.  Rays live in segments with an active list each
+ * (active [2][nrays], counts [3][nseg] int32, seg_off [nseg + 1] int64): step `iter` reads list iter & 1 / counts iter % 3 and
+ * appends the rays that neither hit nor missed to list / counts iter + 1 (in no particular order: results do not depend on it).
+ * A segment that a step left with fewer than 2 rays is finished and its last ray counts as a hit (raymarching.py:119-124,
+ * :57-60), which makes a batch of images equal to the images rendered one by one.
+ *
+ * sg_raymarch_rays (raymarching.py:65-102): camera [13] (host): position, right, up, forward (float64 xyz each), focal distance.
+ * dir [M][3] = normalised float32 pixel rays; pos [S][M][3] = the entry into the sphere of `radius` (the camera position for rays
+ * that miss it); status [S*M] = 0; active list 0 of segment s (seg_off = s * M) = the rays that enter the sphere; `counts` must
+ * be zero on entry. */
+int sg_raymarch_rays(const double* camera, int width, long nshapes, double radius, float* dir, float* pos, unsigned char* status,
+                     int* active, int* counts, hipStream_t stream);
+/* `steps` march steps from iteration first_iter (raymarching.py:104-122 / :46-58), enqueued without a host synchronisation:
+ * the SDFNet forward (packed / zb1 / zb5 of sg_sdfnet_pack_shape_bias, per-shape mode) of every active ray, segment s using
+ * latent s % nshapes, sdf = clamp(tanh + sdf_offset, -clampv, clampv), pos += dir * sdf; hit (status = 1) when
+ * 0 < sdf < threshold, else dropped when |pos| > radius (shadow = 0) or pos.y > radius (shadow = 1), radius = radius0 for
+ * segments < nshapes and radius1 for the others.  dir_period > 0: ray r uses dir[r % dir_period].  evals (optional, uint64):
+ * += the number of SDFNet evaluations.  max_rays: a bound on the active rays of all segments (counts only fall from step to
+ * step: the total the caller last read, or nrays); 0 enqueues nothing.  At most 256 segments. */
+int sg_raymarch_steps(const float* packed, const float* zb1, const float* zb5, float* pos, const float* dir, long dir_period,
+                      unsigned char* status, int* active, long nrays, int* counts, const int64_t* seg_off, long nseg, long nshapes,
+                      long max_rays, long first_iter, int steps, float clampv, float threshold, float sdf_offset, float radius0, float radius1,
+                      int shadow, unsigned long long* evals, hipStream_t stream);
+/* the rays still active before step `iter` are hits (the iteration cap, raymarching.py:124 / :60) */
+int sg_raymarch_finish(unsigned char* status, const int* active, long nrays, const int* counts, const int64_t* seg_off, long nseg,
+                       long iter, hipStream_t stream);
+/* After the camera march (raymarching.py:126-130, :155-163): sg_raymarch_classify applies the vertical cutoff to status (if
+ * use_cutoff), writes ground[s] = the minimum y of image s's hits and the per-image offsets (int64 [S+1]) of the hits and of the
+ * ground rays (pixels looking down that are not hits, met with the plane y = ground[s] within |xz| < 3; none when the image has
+ * no hit).  The caller reads hit_off[S] / gnd_off[S] to size the outputs of sg_raymarch_emit (same arguments, same workspace):
+ * hits in pixel order grouped by image (hit_pos [H][3], hit_sid [H]), slot [S*M] = hit index, -2 - ground index, or -1, and the
+ * shadow rays of both get_shadows calls (raymarching.py:136, :165): rays [0, H) from the hits, [H, H + G) from the ground
+ * points, start q + 0.1 d with d the float64 direction to `light` (host [3]); 2S segments (hits of image s, then its ground rays),
+ * shadow_seg [2S + 1], shadow_counts [3][2S] and list 0 of shadow_active [2][H + G] ready for sg_raymarch_steps. */
+size_t sg_raymarch_workspace_bytes(long M, long nshapes);
+int sg_raymarch_classify(unsigned char* status, const float* pos, const float* dir, long M, long nshapes, int use_cutoff,
+                         float vertical_cutoff, float* ground, int64_t* hit_off, int64_t* gnd_off, void* workspace,
+                         size_t workspace_bytes, hipStream_t stream);
+int sg_raymarch_emit(const unsigned char* status, const float* pos, const float* dir, long M, long nshapes, const float* ground,
+                     const int64_t* hit_off, const int64_t* gnd_off, const double* light, float* hit_pos, int* hit_sid, int* slot,
+                     float* shadow_pos, float* shadow_dir, int* shadow_active, int* shadow_counts, int64_t* shadow_seg,
+                     const void* workspace, size_t workspace_bytes, hipStream_t stream);
+/* Shading (raymarching.py:132-175) in float64: grad [H][3] = d sdf / d hit_pos (normalised here), shadow = status of the shadow
+ * rays; diffuse, specular^20, rim light, color (host [3]) * (0.5 diffuse + 0.5), ground pixels darkened by 0.35 * shadow;
+ * image [S][M][3] uint8 = truncated 255 * value. */
+int sg_raymarch_shade(const int* slot, const float* hit_pos, const float* grad, const unsigned char* shadow, const float* dir, long M,
+                      long nshapes, long nhits, const double* light, const double* color, unsigned char* image, hipStream_t stream);
+
 /* ---- data-parallel gradient exchange: libshapegan_comm.so ----------------------------------------------
  * reference: nn.DataParallel's gradient reduce-add, train_hybrid_progressive_gan.py:62-68.  One process per GPU; one
  * ncclAllReduce(sum, fp32) of a slice of the flat gradient buffer per call, on the communicator's own stream, ordered after

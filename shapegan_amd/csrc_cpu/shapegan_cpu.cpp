@@ -1869,4 +1869,257 @@ int sg_mesh_sample_cpu(const float* vertices, const int64_t* faces, const int64_
     return SG_OK;
 }
 
+// ---- sphere tracing (header: sg_raymarch_*; rendering/raymarching.py:render_image, get_shadows) ------------------------------
+// The same lists, counts and segments as the HIP library; a step appends the survivors in list order (the HIP kernel in any
+// order: the sets are the same).
+#pragma GCC push_options
+#pragma GCC optimize("fp-contract=off")
+// pre-activation of the last layer for one point, per-shape mode (packed of sg_sdfnet_pack_shape_bias_cpu, kin_used = 3)
+static float rm_sdf_pre(const CpuSdf& v, const float* x, const float* zb1, const float* zb5) {
+    float h[256], h2[256];
+    dense(v.W1k, 3, x, zb1, h, true, false);
+    dense(v.W2, 256, h, v.b + 256, h2, true, false);
+    dense(v.W3, 256, h2, v.b + 512, h, true, false);
+    dense(v.W4, 256, h, v.b + 768, h2, true, false);
+    dense(v.W5x, 256, h2, zb5, h, false, false);
+    dense(v.W5i, 3, x, nullptr, h, true, true);
+    dense(v.W6, 256, h, v.b + 1280, h2, true, false);
+    dense(v.W7, 256, h2, v.b + 1536, h, true, false);
+    float s = v.b8[0];
+    for (int k = 0; k < 256; ++k) s += v.w8[k] * h[k];
+    return s;
+}
+
+int sg_raymarch_rays_cpu(const double* camera, int width, long nshapes, double radius, float* dir, float* pos, unsigned char* status,
+                         int* active, int* counts, void*) {
+    CPU_CHECK(camera && dir && pos && status && active && counts && width > 0 && nshapes > 0 && radius > 0.0);
+    const long M = (long)width * width;
+    CPU_CHECK(nshapes * M < (1L << 31));
+    const float cf[3] = {(float)camera[0], (float)camera[1], (float)camera[2]};
+    const double cc = (camera[0] * camera[0] + camera[1] * camera[1] + camera[2] * camera[2]) - radius * radius;
+    const double step = width > 1 ? 2.0 / (double)(width - 1) : 0.0;
+    for (long pix = 0; pix < M; ++pix) {
+        const long row = pix / width, col = pix - row * width;
+        const double sx = col == width - 1 && width > 1 ? 1.0 : (double)col * step + -1.0;
+        const double sy = row == width - 1 && width > 1 ? 1.0 : (double)row * step + -1.0;
+        float d[3], p[3] = {cf[0], cf[1], cf[2]};
+        for (int c = 0; c < 3; ++c) d[c] = (float)(sx * camera[3 + c] + sy * camera[6 + c] + camera[12] * camera[9 + c]);
+        const float n = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        for (int c = 0; c < 3; ++c) d[c] = d[c] / n;
+        for (int c = 0; c < 3; ++c) dir[pix * 3 + c] = d[c];
+        const float b = (p[0] * d[0] + p[1] * d[1] + p[2] * d[2]) * 2.f;
+        const double disc = (double)(b * b) - 4.0 * cc;
+        const bool inside = disc >= 0.0;
+        if (inside) {
+            const double t = (-(double)b - sqrt(disc)) / 2.0;
+            for (int c = 0; c < 3; ++c) p[c] = (float)((double)p[c] + (double)d[c] * t);
+        }
+        for (long s = 0; s < nshapes; ++s) {
+            const long r = s * M + pix;
+            for (int c = 0; c < 3; ++c) pos[r * 3 + c] = p[c];
+            status[r] = 0;
+            if (inside) active[s * M + counts[s]++] = (int)r;
+        }
+    }
+    return SG_OK;
+}
+
+int sg_raymarch_steps_cpu(const float* packed, const float* zb1, const float* zb5, float* pos, const float* dir, long dir_period,
+                          unsigned char* status, int* active, long nrays, int* counts, const int64_t* seg_off, long nseg, long nshapes,
+                          long max_rays, long first_iter, int steps, float clampv, float threshold, float sdf_offset, float radius0,
+                          float radius1, int shadow, unsigned long long* evals, void*) {
+    CPU_CHECK(packed && zb1 && zb5 && pos && dir && status && active && counts && seg_off && steps >= 0 && first_iter >= 0);
+    CPU_CHECK(nseg > 0 && nseg <= 256 && nshapes > 0 && nseg % nshapes == 0 && nrays > 0 && nrays < (1L << 31));
+    CPU_CHECK(max_rays >= 0 && max_rays <= nrays);
+    if (max_rays == 0) return SG_OK;
+    const CpuSdf v = sdf_view(packed, 3);
+    std::vector<int> ray, seg;
+    std::vector<float> sdf;
+    for (int it = 0; it < steps; ++it) {
+        const long iter = first_iter + it;
+        const int* cr = counts + (iter % 3) * nseg;
+        int* cw = counts + ((iter + 1) % 3) * nseg;
+        const int* cur = active + (iter & 1) * nrays;
+        int* next = active + ((iter + 1) & 1) * nrays;
+        ray.clear();
+        seg.clear();
+        for (long s = 0; s < nseg; ++s) {
+            const int c = cr[s];
+            if (iter > 0 && c < 2) {
+                if (c == 1) status[cur[seg_off[s]]] = 1;   // fewer than 2 left: the rest is a hit
+                continue;
+            }
+            for (int k = 0; k < c; ++k) {
+                ray.push_back(cur[seg_off[s] + k]);
+                seg.push_back((int)s);
+            }
+        }
+        for (long s = 0; s < nseg; ++s) counts[((iter + 2) % 3) * nseg + s] = 0;
+        const long n = (long)ray.size();
+        if (evals) *evals += (unsigned long long)n;
+        sdf.resize(n);
+#pragma omp parallel for schedule(dynamic, 16)
+        for (long i = 0; i < n; ++i) {
+            const long sh = seg[i] % nshapes;
+            float s = tanhf(rm_sdf_pre(v, pos + (long)ray[i] * 3, zb1 + sh * 256, zb5 + sh * 256)) + sdf_offset;
+            sdf[i] = std::min(std::max(s, -clampv), clampv);
+        }
+        for (long i = 0; i < n; ++i) {
+            const long r = ray[i];
+            const long di = dir_period > 0 ? r % dir_period : r;
+            float* p = pos + r * 3;
+            const float s = sdf[i];
+            const float x = p[0] + dir[di * 3] * s, y = p[1] + dir[di * 3 + 1] * s, z = p[2] + dir[di * 3 + 2] * s;
+            p[0] = x;
+            p[1] = y;
+            p[2] = z;
+            if (s > 0.f && s < threshold) {
+                status[r] = 1;
+                continue;
+            }
+            const float rad = seg[i] < nshapes ? radius0 : radius1;
+            if (shadow ? y > rad : sqrtf(x * x + y * y + z * z) > rad) continue;
+            next[seg_off[seg[i]] + cw[seg[i]]++] = (int)r;
+        }
+    }
+    return SG_OK;
+}
+
+int sg_raymarch_finish_cpu(unsigned char* status, const int* active, long nrays, const int* counts, const int64_t* seg_off, long nseg,
+                           long iter, void*) {
+    CPU_CHECK(status && active && counts && seg_off && nseg > 0 && nseg <= 256 && iter >= 0 && nrays > 0);
+    const int* cur = active + (iter & 1) * nrays;
+    for (long s = 0; s < nseg; ++s)
+        for (int k = 0; k < counts[(iter % 3) * nseg + s]; ++k) status[cur[seg_off[s] + k]] = 1;
+    return SG_OK;
+}
+
+static bool rm_ground_point(const unsigned char* status, const float* pos, const float* dir, long M, long s, long pix, float ground,
+                            float q[3]) {
+    const float* d = dir + pix * 3;
+    if (!(d[1] < 0.f) || status[s * M + pix]) return false;
+    const float* p = pos + (s * M + pix) * 3;
+    const float t = (p[1] - ground) / d[1];
+    for (int c = 0; c < 3; ++c) q[c] = p[c] - d[c] * t;
+    return sqrtf(q[0] * q[0] + q[2] * q[2]) < 3.f;
+}
+
+int sg_raymarch_classify_cpu(unsigned char* status, const float* pos, const float* dir, long M, long nshapes, int use_cutoff,
+                             float vertical_cutoff, float* ground, int64_t* hit_off, int64_t* gnd_off, void*, size_t, void*) {
+    CPU_CHECK(status && pos && dir && ground && hit_off && gnd_off && M > 0 && nshapes > 0 && 2 * nshapes <= 256);
+    hit_off[0] = gnd_off[0] = 0;
+    for (long s = 0; s < nshapes; ++s) {
+        long h = 0;
+        float g = INFINITY;
+        for (long pix = 0; pix < M; ++pix) {
+            const long r = s * M + pix;
+            if (!status[r]) continue;
+            const float y = pos[r * 3 + 1];
+            if (use_cutoff && (y > vertical_cutoff || y < -vertical_cutoff)) {
+                status[r] = 0;
+                continue;
+            }
+            ++h;
+            g = std::min(g, y);
+        }
+        ground[s] = g;
+        hit_off[s + 1] = hit_off[s] + h;
+        long n = 0;
+        float q[3];
+        if (h > 0)
+            for (long pix = 0; pix < M; ++pix) n += rm_ground_point(status, pos, dir, M, s, pix, g, q) ? 1 : 0;
+        gnd_off[s + 1] = gnd_off[s] + n;
+    }
+    return SG_OK;
+}
+
+static void rm_shadow_ray(const double* light, const float q[3], long j, float* spos, float* sdir, int* sactive) {
+    double d[3];
+    for (int c = 0; c < 3; ++c) d[c] = light[c] - (double)q[c];
+    const double n = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    for (int c = 0; c < 3; ++c) {
+        const float df = (float)(d[c] / n);
+        sdir[j * 3 + c] = df;
+        spos[j * 3 + c] = q[c] + df * 0.1f;
+    }
+    sactive[j] = (int)j;
+}
+
+int sg_raymarch_emit_cpu(const unsigned char* status, const float* pos, const float* dir, long M, long nshapes, const float* ground,
+                         const int64_t* hit_off, const int64_t* gnd_off, const double* light, float* hit_pos, int* hit_sid, int* slot,
+                         float* shadow_pos, float* shadow_dir, int* shadow_active, int* shadow_counts, int64_t* shadow_seg,
+                         const void*, size_t, void*) {
+    CPU_CHECK(status && pos && dir && ground && hit_off && gnd_off && light && slot && shadow_counts && shadow_seg);
+    CPU_CHECK(M > 0 && nshapes > 0 && 2 * nshapes <= 256);
+    const long S = nshapes, H = hit_off[S];
+    long h = 0, g = 0;
+    for (long s = 0; s < S; ++s) {
+        for (long pix = 0; pix < M; ++pix) {
+            const long r = s * M + pix;
+            float q[3];
+            if (status[r]) {
+                for (int c = 0; c < 3; ++c) q[c] = hit_pos[h * 3 + c] = pos[r * 3 + c];
+                hit_sid[h] = (int)s;
+                slot[r] = (int)h;
+                rm_shadow_ray(light, q, h, shadow_pos, shadow_dir, shadow_active);
+                ++h;
+            } else if (hit_off[s + 1] > hit_off[s] && rm_ground_point(status, pos, dir, M, s, pix, ground[s], q)) {
+                slot[r] = -2 - (int)g;
+                rm_shadow_ray(light, q, H + g, shadow_pos, shadow_dir, shadow_active);
+                ++g;
+            } else {
+                slot[r] = -1;
+            }
+        }
+    }
+    for (long j = 0; j <= 2 * S; ++j) shadow_seg[j] = j <= S ? hit_off[j] : H + gnd_off[j - S];
+    for (long j = 0; j < 2 * S; ++j) {
+        shadow_counts[j] = (int)(shadow_seg[j + 1] - shadow_seg[j]);
+        shadow_counts[2 * S + j] = shadow_counts[4 * S + j] = 0;
+    }
+    return SG_OK;
+}
+
+int sg_raymarch_shade_cpu(const int* slot, const float* hit_pos, const float* grad, const unsigned char* shadow, const float* dir, long M,
+                          long nshapes, long nhits, const double* light, const double* color, unsigned char* image, void*) {
+    CPU_CHECK(slot && dir && light && color && image && M > 0 && nshapes > 0 && nhits >= 0);
+    CPU_CHECK(nhits == 0 || (hit_pos && grad && shadow));
+#pragma omp parallel for schedule(static)
+    for (long r = 0; r < nshapes * M; ++r) {
+        const long pix = r % M;
+        const int k = slot[r];
+        double px[3] = {1.0, 1.0, 1.0};
+        if (k >= 0) {
+            const float* g = grad + (long)k * 3;
+            const float gn = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+            const float nf[3] = {g[0] / gn, g[1] / gn, g[2] / gn};
+            const float* d = dir + pix * 3;
+            const double seen = (double)(1.f - (float)shadow[k]);
+            double ld[3];
+            for (int c = 0; c < 3; ++c) ld[c] = light[c] - (double)hit_pos[(long)k * 3 + c];
+            const double ln = sqrt(ld[0] * ld[0] + ld[1] * ld[1] + ld[2] * ld[2]);
+            for (int c = 0; c < 3; ++c) ld[c] = ld[c] / ln;
+            const double dn = ld[0] * nf[0] + ld[1] * nf[1] + ld[2] * nf[2];
+            const double diffuse = std::min(std::max(dn, 0.0), 1.0) * seen;
+            double rf[3];
+            for (int c = 0; c < 3; ++c) rf[c] = ld[c] - dn * (double)nf[c] * 2.0;
+            const double rn = sqrt(rf[0] * rf[0] + rf[1] * rf[1] + rf[2] * rf[2]);
+            double spec = (rf[0] / rn) * d[0] + (rf[1] / rn) * d[1] + (rf[2] / rn) * d[2];
+            spec = std::min(std::max(spec, 0.0), 1.0);
+            spec = pow(spec, 20.0) * seen;
+            float rim = -(nf[0] * d[0] + nf[1] * d[1] + nf[2] * d[2]);
+            rim = 1.f - std::min(std::max(rim, 0.f), 1.f);
+            rim = rim * rim * rim * rim * 0.3f;
+            for (int c = 0; c < 3; ++c)
+                px[c] = std::min(std::max(color[c] * (diffuse * 0.5 + 0.5) + (spec * 0.3 + (double)rim), 0.0), 1.0);
+        } else if (k <= -2) {
+            const double dk = (double)(0.35f * (float)shadow[nhits + (-2 - k)]);
+            for (int c = 0; c < 3; ++c) px[c] -= dk;
+        }
+        for (int c = 0; c < 3; ++c) image[r * 3 + c] = (unsigned char)(px[c] * 255.0);
+    }
+    return SG_OK;
+}
+#pragma GCC pop_options
+
 }  // extern "C"

@@ -163,6 +163,13 @@ SIGNATURES = {
     "sg_mc_emit": (c_int, [_P, _L, _I, _I, _I, _F, _I, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _L, _L, _P, _Z, _P]),
     "sg_mesh_sample_workspace_bytes": (_Z, [_L, _L]),
     "sg_mesh_sample": (c_int, [_P, _P, _P, _P, _L, _L, _P, _L, _P, _P, _P, _Z, _P]),
+    "sg_raymarch_rays": (c_int, [_P, _I, _L, _D, _P, _P, _P, _P, _P, _P]),
+    "sg_raymarch_steps": (c_int, [_P, _P, _P, _P, _P, _L, _P, _P, _L, _P, _P, _L, _L, _L, _L, _I, _F, _F, _F, _F, _F, _I, _P, _P]),
+    "sg_raymarch_finish": (c_int, [_P, _P, _L, _P, _P, _L, _L, _P]),
+    "sg_raymarch_workspace_bytes": (_Z, [_L, _L]),
+    "sg_raymarch_classify": (c_int, [_P, _P, _P, _L, _L, _I, _F, _P, _P, _P, _P, _Z, _P]),
+    "sg_raymarch_emit": (c_int, [_P, _P, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "sg_raymarch_shade": (c_int, [_P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P]),
 }
 
 # libshapegan_comm.so (RCCL gradient exchange; loaded only by data-parallel runs that ask for it)

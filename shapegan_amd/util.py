@@ -1,7 +1,7 @@
 """Host-side helpers with the reference's `util` surface (util.py:1-85), restated.
 
 Only the pieces the hot path touches are here: `device`, `standard_normal_distribution`,
-`get_voxel_coordinates`, `get_points_in_unit_sphere`, `ensure_directory`, `create_text_slice`.
+`get_voxel_coordinates`, `get_points_in_unit_sphere`, `ensure_directory`, `create_text_slice`, `crop_image`.
 Unlike the reference, importing this module does not create plots/ models/ data/ in the CWD (util.py:11-13 does);
 `SavableModule.save` creates `models/` on demand instead.
 """
@@ -59,3 +59,22 @@ def create_text_slice(voxels):
             picked.append(lines[i])
     frame = '+' + '—' * res + '+\n'
     return frame + '\n'.join(reversed(picked)) + '\n' + frame
+
+
+def crop_image(image, background=255):
+    """Square crop around the non-background pixels, only when it is more than 200 pixels wide (util.py:41-58)."""
+    mask = image[:, :] != background
+    coords = np.array(np.nonzero(mask))
+    if coords.size != 0:
+        top_left = np.min(coords, axis=1)
+        bottom_right = np.max(coords, axis=1)
+    else:
+        top_left = np.array((0, 0))
+        bottom_right = np.array(image.shape)
+        print("Warning: Image contains only background pixels.")
+    half_size = int(max(bottom_right[0] - top_left[0], bottom_right[1] - top_left[1]) / 2)
+    center = ((top_left + bottom_right) / 2).astype(int)
+    center = (min(max(half_size, center[0]), image.shape[0] - half_size), min(max(half_size, center[1]), image.shape[1] - half_size))
+    if half_size > 100:
+        image = image[center[0] - half_size:center[0] + half_size, center[1] - half_size:center[1] + half_size]
+    return image
