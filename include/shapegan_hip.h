@@ -597,7 +597,8 @@ int sg_raymarch_steps(const float* packed, const float* zb1, const float* zb5, f
 int sg_raymarch_finish(unsigned char* status, const int* active, long nrays, const int* counts, const int64_t* seg_off, long nseg,
                        long iter, hipStream_t stream);
 /* After the camera march (raymarching.py:126-130, :155-163): sg_raymarch_classify applies the vertical cutoff to status (if
- * use_cutoff), writes ground[s] = the minimum y of image s's hits and the per-image offsets (int64 [S+1]) of the hits and of the
+ * use_cutoff), writes ground[s] = the minimum y of image s's hits (+inf, the minimum over nothing, for an image without hits)
+ * and the per-image offsets (int64 [S+1]) of the hits and of the
  * ground rays (pixels looking down that are not hits, met with the plane y = ground[s] within |xz| < 3; none when the image has
  * no hit).  The caller reads hit_off[S] / gnd_off[S] to size the outputs of sg_raymarch_emit (same arguments, same workspace):
  * hits in pixel order grouped by image (hit_pos [H][3], hit_sid [H]), slot [S*M] = hit index, -2 - ground index, or -1, and the

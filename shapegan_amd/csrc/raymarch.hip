@@ -350,7 +350,8 @@ __global__ void __launch_bounds__(1024) raymarch_scan_kernel(const int* __restri
     if (threadIdx.x == 0) offsets[S] = all;
     if (block_min) {
         __syncthreads();
-        for (int s = threadIdx.x; s < S; s += 1024) ground[s] = key_float(smin[s]);
+        // (an image without hits keeps the initial key, a NaN pattern: the minimum over nothing is +inf)
+        for (int s = threadIdx.x; s < S; s += 1024) ground[s] = smin[s] == 0x7fffffff ? INFINITY : key_float(smin[s]);
     }
 }
 

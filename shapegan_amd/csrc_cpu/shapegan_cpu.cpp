@@ -1895,8 +1895,11 @@ int sg_raymarch_rays_cpu(const double* camera, int width, long nshapes, double r
     CPU_CHECK(camera && dir && pos && status && active && counts && width > 0 && nshapes > 0 && radius > 0.0);
     const long M = (long)width * width;
     CPU_CHECK(nshapes * M < (1L << 31));
-    const float cf[3] = {(float)camera[0], (float)camera[1], (float)camera[2]};
-    const double cc = (camera[0] * camera[0] + camera[1] * camera[1] + camera[2] * camera[2]) - radius * radius;
+    // (through a volatile: g++ 11 -O3's SLP vectoriser otherwise carries the double x and y of the camera past this rounding into
+    // the start positions, 3e-8 off the float32 camera position that the header and the HIP kernel start from)
+    const volatile float cfv[3] = {(float)camera[0], (float)camera[1], (float)camera[2]};
+    const float cf[3] = {cfv[0], cfv[1], cfv[2]};
+    const double cc =(camera[0] * camera[0] + camera[1] * camera[1] + camera[2] * camera[2]) - radius * radius;
     const double step = width > 1 ? 2.0 / (double)(width - 1) : 0.0;
     for (long pix = 0; pix < M; ++pix) {
         const long row = pix / width, col = pix - row * width;

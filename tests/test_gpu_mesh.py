@@ -6,6 +6,8 @@ import torch
 from shapegan_amd import metrics
 from shapegan_amd.mesh import marching_cubes, sample_packed
 from shapegan_amd.model.sdf_net import SDFNet
+import geometry_reference as R
+import test_mesh_reference as T
 from test_mesh import closed_and_oriented, sphere_grid, torus_grid
 
 pytestmark = pytest.mark.gpu
@@ -76,6 +78,25 @@ def test_gpu_sampling_matches_twin():
     assert float((diff > 1e-5).float().mean()) < 1e-3
     for s, r in enumerate((0.3, 0.5, 0.7, 0.9)):
         assert float((pg[s].norm(dim=1) - r).abs().max()) < 0.02
+
+
+@pytest.mark.parametrize("shape", R.MC_SHAPES)
+def test_gpu_marching_cubes_against_reference(shape):
+    """csrc/mesh.hip against the direct numpy reference (vertex order, faces and offsets exact; positions and normals in float64)
+    and, on the same non-cubic shapes, levels and pad values, against the twin."""
+    _, done = T.body_mc("cuda", shape)
+    for grids, kw, gpu in done:
+        assert_same_meshes(gpu, marching_cubes(grids, spacing=R.MC_SPACING, origin=R.MC_ORIGIN, **kw))
+
+
+def test_gpu_marching_cubes_many_blocks():
+    _, done = T.body_mc("cuda", (33, 32, 31), S=7, combos={(True, 0)})
+    for grids, kw, gpu in done:
+        assert_same_meshes(gpu, marching_cubes(grids, spacing=R.MC_SPACING, origin=R.MC_ORIGIN, **kw))
+
+
+def test_gpu_surface_sampling_against_reference():
+    T.body_sampling("cuda")
 
 
 def test_gpu_sample_surface_reproducible():
