@@ -569,6 +569,42 @@ int sg_mesh_sample(const float* vertices, const int64_t* faces, const int64_t* v
                    long F, const float* uniforms, long P, float* out, int* empty, void* workspace, size_t workspace_bytes,
                    hipStream_t stream);
 
+/* ---- K13: point-cloud evaluation: Chamfer matrices, nearest neighbours, occupancy histograms -----------------------------------
+ * Clouds are [S][P][3] fp32, contiguous.  Every pair (a, b) of points has ONE value, in f32:
+ *   dx = ax - bx, dy = ay - by, dz = az - bz;   d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx))
+ * (three roundings of the differences, one of the product, two fused steps; written with explicit fmaf, contraction off).  It is
+ * bitwise the same with a and b exchanged, and a minimum of such values does not depend on the order it is taken in: dist_*,
+ * idx_* and every minimum inside sg_chamfer_matrix are the same bit for bit on the GPU, in the twin and under any tiling.  A
+ * tie takes the LOWEST index.  Non-finite coordinates give unspecified values in the rows and columns they touch, but no fault
+ * and no index outside [0, Q) / [0, P).
+ *
+ * sg_chamfer_matrix: A [Sa][P][3], B [Sb][Q][3] -> ab, ba [Sa][Sb] float64 (either may be NULL):
+ *   ab[i][j] = mean over the points a of A_i of  min over the points b of B_j of d2(a, b),   ba[i][j] = the same from B_j to A_i.
+ * The Chamfer distance is ab + ba (squared distances, the convention of Achlioptas et al.'s evaluation code).  Means are float64
+ * sums of the f32 minima m[0..n) in ONE order, shared by the GPU and the twin, so ab and ba are bit-identical between them:
+ *   per tile t of 2048 points:  s[l] = ((0 + m[t*2048 + l]) + m[t*2048 + 256 + l]) + ... (k = 0..7, indices >= n skipped),
+ *                               l = 0..255;  then for off = 128, 64, .., 1:  s[l] += s[l + off] for l < off;  T[t] = s[0];
+ *   mean = (T[0] + T[1] + ...) / n      (tiles added in increasing t, one float64 division).
+ * Any Sa, Sb, P, Q >= 1 (Sa, Sb <= 65535 per call: split the batch; P, Q <= 2^26; beyond either SG_ERR_ARG, on the GPU and in
+ * the twin alike).  workspace: the per-tile sums.
+ *
+ * sg_chamfer_nearest: matched batches A [S][P][3], B [S][Q][3] -> dist_a [S][P] fp32 / idx_a [S][P] int32: for every point of
+ * A_s the smallest d2 to a point of B_s and the lowest index that attains it; dist_b / idx_b [S][Q] the same from B_s to A_s.
+ * Either pair may be NULL (both of a pair or neither).
+ *
+ * sg_occupancy_histogram: hist [R][R][R] int64 += the number of points of clouds [S][P][3] per cell of the grid with centres
+ * c_i = -0.5 + i / (R - 1) per axis (the caller zeroes hist; 2 <= R <= 1024).  The index along an axis is, in f32 without contraction,
+ *   t = (x + 0.5f) * (float)(R - 1);   i = (int) min(max(floorf(t + 0.5f), 0.f), (float)(R - 1))      (max(NaN, 0) = 0)
+ * i.e. the nearest centre, clamped; cell = (i_x * R + i_y) * R + i_z.  Integer atomics only: the counts do not depend on order.
+ * reference: metrics.py:18-46 (sample_point_clouds / sample_from_voxels write the clouds, rescaled to the half unit sphere, that
+ *            these entry points consume; the reference leaves the scoring to an outside tool). */
+size_t sg_chamfer_matrix_workspace_bytes(long Sa, long Sb, long P, long Q);
+int sg_chamfer_matrix(const float* A, const float* B, long Sa, long Sb, long P, long Q, double* ab, double* ba, void* workspace,
+                      size_t workspace_bytes, hipStream_t stream);
+int sg_chamfer_nearest(const float* A, const float* B, long S, long P, long Q, float* dist_a, int* idx_a, float* dist_b, int* idx_b,
+                       hipStream_t stream);
+int sg_occupancy_histogram(const float* clouds, long S, long P, int R, int64_t* hist, hipStream_t stream);
+
 /* ---- sphere tracing of SDFNet shapes (rendering/raymarching.py:render_image, get_shadows) ----------------------------------
  * S images of the same camera, M = width^2 pixels each; ray r = s * M + pixel.  Rays live in segments with an active list each
  * (active [2][nrays], counts [3][nseg] int32, seg_off [nseg + 1] int64): step `iter` reads list iter & 1 / counts iter % 3 and

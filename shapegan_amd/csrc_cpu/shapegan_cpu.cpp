@@ -2125,4 +2125,105 @@ int sg_raymarch_shade_cpu(const int* slot, const float* hit_pos, const float* gr
 }
 #pragma GCC pop_options
 
+// ---- K13: point-cloud evaluation (include/shapegan_hip.h) -------------------------------------------------------------------
+#pragma GCC push_options
+#pragma GCC optimize("fp-contract=off")
+static inline float cd_pair(const float* a, const float* b) {
+    const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
+    return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+}
+
+// the header's summation order of the minima m[0..n): tiles of 2048, 256 strided partial sums, a halving tree, tiles in order
+static double cd_mean(const float* m, long n) {
+    double total = 0.0;
+    for (long t0 = 0; t0 < n; t0 += 2048) {
+        double s[256];
+        for (int l = 0; l < 256; ++l) s[l] = 0.0;
+        for (int k = 0; k < 8; ++k)
+            for (int l = 0; l < 256; ++l) {
+                const long p = t0 + (long)k * 256 + l;
+                if (p < n) s[l] += (double)m[p];
+            }
+        for (int off = 128; off > 0; off >>= 1)
+            for (int l = 0; l < off; ++l) s[l] += s[l + off];
+        total += s[0];
+    }
+    return total / (double)n;
+}
+
+int sg_chamfer_matrix_cpu(const float* A, const float* B, long Sa, long Sb, long P, long Q, double* ab, double* ba, void*, size_t,
+                          hipStream_t_) {
+    CPU_CHECK(A && B && (ab || ba) && Sa >= 1 && Sb >= 1 && P >= 1 && Q >= 1 && Sa <= 65535 && Sb <= 65535 && P <= (1L << 26) &&
+              Q <= (1L << 26));
+#pragma omp parallel
+    {
+        std::vector<float> ma((size_t)P), mb((size_t)Q);
+#pragma omp for schedule(dynamic)
+        for (long e = 0; e < Sa * Sb; ++e) {
+            const float* a = A + (e / Sb) * P * 3;
+            const float* b = B + (e % Sb) * Q * 3;
+            std::fill(mb.begin(), mb.end(), INFINITY);
+            for (long p = 0; p < P; ++p) {
+                float best = INFINITY;
+                for (long q = 0; q < Q; ++q) {
+                    const float d = cd_pair(a + p * 3, b + q * 3);
+                    best = d < best ? d : best;
+                    mb[q] = d < mb[q] ? d : mb[q];
+                }
+                ma[p] = best;
+            }
+            if (ab) ab[e] = cd_mean(ma.data(), P);
+            if (ba) ba[e] = cd_mean(mb.data(), Q);
+        }
+    }
+    return SG_OK;
+}
+
+static void cd_nearest(const float* A, const float* B, long S, long P, long Q, float* dist, int* idx) {
+#pragma omp parallel for schedule(static)
+    for (long r = 0; r < S * P; ++r) {
+        const float* a = A + r * 3;
+        const float* b = B + (r / P) * Q * 3;
+        float best = INFINITY;
+        int arg = 0;
+        for (long q = 0; q < Q; ++q) {
+            const float d = cd_pair(a, b + q * 3);
+            if (d < best) {      // increasing index, strict: the lowest index of a tie stays
+                best = d;
+                arg = (int)q;
+            }
+        }
+        dist[r] = best;
+        idx[r] = arg;
+    }
+}
+
+int sg_chamfer_nearest_cpu(const float* A, const float* B, long S, long P, long Q, float* dist_a, int* idx_a, float* dist_b, int* idx_b,
+                           hipStream_t_) {
+    CPU_CHECK(A && B && S >= 1 && S <= 65535 && P >= 1 && Q >= 1 && P <= (1L << 26) && Q <= (1L << 26));
+    CPU_CHECK((dist_a != nullptr) == (idx_a != nullptr) && (dist_b != nullptr) == (idx_b != nullptr) && (dist_a || dist_b));
+    if (dist_a) cd_nearest(A, B, S, P, Q, dist_a, idx_a);
+    if (dist_b) cd_nearest(B, A, S, Q, P, dist_b, idx_b);
+    return SG_OK;
+}
+
+static inline int occupancy_axis(float x, float rm1) {
+    const float t = (x + 0.5f) * rm1;
+    float f = floorf(t + 0.5f);
+    f = f > 0.f ? f : 0.f;       // NaN -> 0
+    return (int)(f < rm1 ? f : rm1);
+}
+
+int sg_occupancy_histogram_cpu(const float* clouds, long S, long P, int R, int64_t* hist, hipStream_t_) {
+    CPU_CHECK(clouds && hist && S >= 1 && P >= 1 && R >= 2 && R <= 1024 && S * P <= (1L << 38));
+    const float rm1 = (float)(R - 1);
+    for (long i = 0; i < S * P; ++i) {
+        const int ix = occupancy_axis(clouds[i * 3], rm1), iy = occupancy_axis(clouds[i * 3 + 1], rm1),
+                  iz = occupancy_axis(clouds[i * 3 + 2], rm1);
+        hist[((long)ix * R + iy) * R + iz] += 1;
+    }
+    return SG_OK;
+}
+#pragma GCC pop_options
+
 }  // extern "C"

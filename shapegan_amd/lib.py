@@ -163,6 +163,10 @@ SIGNATURES = {
     "sg_mc_emit": (c_int, [_P, _L, _I, _I, _I, _F, _I, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _L, _L, _P, _Z, _P]),
     "sg_mesh_sample_workspace_bytes": (_Z, [_L, _L]),
     "sg_mesh_sample": (c_int, [_P, _P, _P, _P, _L, _L, _P, _L, _P, _P, _P, _Z, _P]),
+    "sg_chamfer_matrix_workspace_bytes": (_Z, [_L, _L, _L, _L]),
+    "sg_chamfer_matrix": (c_int, [_P, _P, _L, _L, _L, _L, _P, _P, _P, _Z, _P]),
+    "sg_chamfer_nearest": (c_int, [_P, _P, _L, _L, _L, _P, _P, _P, _P, _P]),
+    "sg_occupancy_histogram": (c_int, [_P, _L, _L, _I, _P, _P]),
     "sg_raymarch_rays": (c_int, [_P, _I, _L, _D, _P, _P, _P, _P, _P, _P]),
     "sg_raymarch_steps": (c_int, [_P, _P, _P, _P, _P, _L, _P, _P, _L, _P, _P, _L, _L, _L, _L, _I, _F, _F, _F, _F, _F, _I, _P, _P]),
     "sg_raymarch_finish": (c_int, [_P, _P, _L, _P, _P, _L, _L, _P]),
