@@ -605,6 +605,77 @@ int sg_chamfer_nearest(const float* A, const float* B, long S, long P, long Q, f
                        hipStream_t stream);
 int sg_occupancy_histogram(const float* clouds, long S, long P, int R, int64_t* hist, hipStream_t stream);
 
+/* ---- K14: tiled triangle rasteriser: the headless MeshRenderer -----------------------------------------------------------------
+ * reference: rendering/__init__.py (MeshRenderer: _render_shadow_texture, _render, _draw_floor) with vertex.glsl / fragment.glsl ->
+ *            S shapes drawn in a handful of launches, no window and no GL context.
+ * Input: S triangle soups packed as the reference's _update_buffers takes them: positions [T][3][3] fp32, normals [T][3][3] fp32 or
+ * NULL (flat shading), tri_offsets [S+1] int64 (shape s owns triangles [tri_offsets[s], tri_offsets[s+1])).  Any S >= 1
+ * (<= 65535), any T >= 0, any shape may be empty; width, height <= 16384.  A view is a 4x4 row-major `vp` of 16 host doubles,
+ * rounded ONCE to fp32.  All arithmetic below is fp32 with the fused steps written out (contraction off) or integer, and exists
+ * once (csrc/raster_core.h): the GPU and the twin agree bit for bit on every output, bins compared as sets.
+ *
+ * sg_raster_setup, per triangle and view:
+ *   clip[k][i] = fmaf(M[i][2], z, fmaf(M[i][1], y, fmaf(M[i][0], x, M[i][3])))           corner k = (x, y, z), i = 0..3, w = clip[k][3]
+ *   window, snapped to 8 sub-pixel bits (int32; y runs DOWN, row 0 is NDC y = +1; sample (px, py) has its centre at px*256+128):
+ *     X = rint(fmaf(clip_x / w, 128 width, 128 width)),   Y = rint(fmaf(clip_y / w, -128 height, 128 height))
+ *   z = clip_z / w (NDC depth), iw = 1 / w.   recs [T][16] int32 words: X0 X1 X2 Y0 Y1 Y2 | z0 z1 z2 | iw0 iw1 iw2 (float bits) |
+ *   px0 py0 px1 py1 = the samples whose centres lie in the snapped bounding box, clamped to the image.
+ *   flags [T] int32, the FIRST that applies: 1 a corner has w <= near_w (no clipping: the triangle is dropped; near_w = the near
+ *   distance of rendering/math.py's PROJECTION_MATRIX, 0.1); 2 a snapped coordinate would leave +-2^22 (keeps the 64-bit edge
+ *   products exact); 4 zero area; 8 back face, only when cull_back: front = counter-clockwise on the screen (GL's default) =
+ *   (v1 - v0) x (v2 - v0) faces the camera, K12's orientation; the shadow pass culls nothing; 16 kept, but no sample centre in its
+ *   box.  Flags 1..8 are DROPPED: their record is zeros with an empty box, dropped[s] (int32 [S]) counts them per shape.
+ *   clip (may be NULL): [T][3][4].  ground (may be NULL): [S] fp32 = min over the shape's corners of y, found with integer atomicMin
+ *   on the order-preserving image of the float, no host read; -1 for an empty shape.  tile_counts [S][nty][ntx] int32 = the number
+ *   of kept triangles whose box touches each tile of 16 x 16 samples (ntx = ceil(width / 16), nty likewise; integer atomics).
+ * sg_raster_scan: tile_offsets [n+1] int64 = exclusive sum of the n = S nty ntx counts; cursor [n] int32 = 0; active [n] int32 = the
+ *   non-empty tiles in increasing order (first totals[1] entries); totals [2] int64 = {tile_offsets[n], number of non-empty tiles}.
+ *   The caller reads totals (the one device -> host read of a view) to size `lists` and the visibility launch.
+ * sg_raster_fill: lists [capacity] int32: the triangles of tile g are lists[tile_offsets[g] .. tile_offsets[g+1]), as a SET: the
+ *   order inside a list is not specified (the GPU takes slots from an atomic cursor, the twin fills in triangle order) and no
+ *   result depends on it.  Nothing is written outside [0, capacity).
+ * sg_raster_visibility: id [S][H][W] int32 (-1 = nothing; NULL in the shadow pass), depth [S][H][W] fp32 (1.0 = cleared).  Sample
+ *   (px, py) is covered by a triangle when the three int64 edge functions at its centre, signed so that the inside is positive,
+ *   are > 0, or = 0 on a top or left edge (edge vector (dx, dy) along the inside-positive orientation: dy < 0, or dy = 0 and
+ *   dx > 0) — a sample on an edge shared by two triangles on opposite sides belongs to exactly one.  Depth of a covered sample:
+ *     inv = 1 / (float)|2 area|,  l1 = (float)e1 * inv,  l2 = (float)e2 * inv,  z = fmaf(l2, z2 - z0, fmaf(l1, z1 - z0, z0))
+ *   (screen-space barycentrics, as GL interpolates gl_FragCoord.z; e_i = the edge function opposite corner i).  Winner = smallest z,
+ *   a tie goes to the lowest triangle index; depth is not clipped to the far plane.  shadow != 0: depth = fmaf(0.5, z, 0.5).
+ *   An entry of `active` or `lists` that names no tile / no triangle of the tile's shape is skipped.
+ * sg_raster_shade: image [S][H][W][3] uint8 = floor(fmaf(clamp(c, 0, 1), 255, 0.5)).  params: 60 host doubles, rounded once to fp32:
+ *   VP [16], lightVP [16], VP^-1 [16], camera position [3], lightPosition = xyz of VP lightVP^-1 (0, 0, -1, 1) [3], albedo [3],
+ *   background [3].  shadow_map [S][N][N] = the depth of the light pass (N = shadow_size).  For a sample with id >= 0:
+ *     perspective-correct barycentrics b_i = q_i / ((q0 + q1) + q2), q_i = ((float)e_i * inv) * iw_i;  world p = fmaf(b2, v2, fmaf(b1,
+ *     v1, b0 v0)); n = the corner normals interpolated the same way, or (v1 - v0) x (v2 - v0) (each component fmaf(a, b, -(c d)));
+ *     position = (VP (p, 1)).xyz, shadowPosition = lightVP (p, 1) (rows as clip above), normal = normalize((VP (n, 0)).xyz),
+ *     L = normalize(lightPosition - position), V = normalize(-position), R = -normalize(L - 2 (n.L) n), d = clamp(n.L, 0, 1);
+ *     colour = ((a/2 + (a/2 d) lit) + (0.3 s^20) lit) + 0.3 m^4 per channel, a = albedo, lit = 1 - shadow, s = max(0, R.V) with
+ *     s^20 = ((((s^2)^2)^2)^2) (s^2)^2, m = 1 - clamp(-n_z, 0, 1) with m^4 = (m^2)^2; dot(a, b) = fmaf(a2, b2, fmaf(a1, b1, a0 b0)).
+ *   shadow(shadowPosition sp, d): c = fmaf(sp.xyz / sp.w, 0.5, 0.5); 0 unless c.z <= 1; ref = c.z - max(0.002 (1 - d), 0.001) / sp.w;
+ *     the mean over the offsets (ox, oy) in {-1, 0, 1}^2 (ox outer) of the bilinear blend, t = fmaf(fmaf(o, 1/N, c), N, 0.5) per axis,
+ *     weights t - floor(t), of the four comparisons ref > map at texels floor(t) + {0, 1} (clamped to the edge; texel row v counts
+ *     from NDC y = -1), mix(a, b, f) = fmaf(b - a, f, a); clamped to [0, 1].
+ *   The floor is analytic and is tested first: the eye ray from the camera position through VP^-1 (nx, ny, 1, 1) (nx, ny = the NDC
+ *   of the sample centre) meets y = ground[s] at t > 0; it is a floor sample when the camera is above the plane, |x|, |z| <= 6, its
+ *   clip w > 0, its NDC depth is in [-1, 1] and smaller than depth at the sample (1.0 where nothing was drawn); colour =
+ *   fmaf(shadow, -0.6, 1) with d from the normal normalize(VP (0, 1, 0, 0)).  A sample that is neither is the background colour.
+ * sg_raster_resolve: image [S][H][W][3] = the rounded mean of ssaa x ssaa blocks of samples [S][H ssaa][W ssaa][3], in integers
+ *   ((2 sum + n) / (2 n), n = ssaa^2). */
+int sg_raster_setup(const float* positions, const int64_t* tri_offsets, long S, long T, const double* vp, int width, int height,
+                    int cull_back, double near_w, int* recs, int* flags, float* clip, int* dropped, float* ground, int* tile_counts,
+                    hipStream_t stream);
+int sg_raster_scan(const int* tile_counts, long ntiles, int64_t* tile_offsets, int* cursor, int* active, int64_t* totals,
+                   hipStream_t stream);
+int sg_raster_fill(const int* recs, const int* flags, const int64_t* tri_offsets, long S, long T, int width, int height,
+                   const int64_t* tile_offsets, int* cursor, int* lists, long capacity, hipStream_t stream);
+int sg_raster_visibility(const int* recs, const int64_t* tri_offsets, long S, int width, int height, const int64_t* tile_offsets,
+                         const int* lists, long capacity, const int* active, long nactive, int* id, float* depth, int shadow,
+                         hipStream_t stream);
+int sg_raster_shade(const float* positions, const float* normals, long T, const int* recs, const int* id, const float* depth,
+                    const float* shadow_map, int shadow_size, const float* ground, const double* params, long S, int width, int height,
+                    unsigned char* image, hipStream_t stream);
+int sg_raster_resolve(const unsigned char* samples, long S, int width, int height, int ssaa, unsigned char* image, hipStream_t stream);
+
 /* ---- sphere tracing of SDFNet shapes (rendering/raymarching.py:render_image, get_shadows) ----------------------------------
  * S images of the same camera, M = width^2 pixels each; ray r = s * M + pixel.  Rays live in segments with an active list each
  * (active [2][nrays], counts [3][nseg] int32, seg_off [nseg + 1] int64): step `iter` reads list iter & 1 / counts iter % 3 and

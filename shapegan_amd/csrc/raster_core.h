@@ -1,0 +1,272 @@
+// shapegan_amd/csrc/raster_core.h — the per-triangle and per-sample arithmetic of the rasteriser (K14, include/shapegan_hip.h).
+//
+// Plain C++ without HIP types: csrc/raster.hip and the twin (csrc_cpu/shapegan_cpu.cpp) both include it, like mc_tables.h, so the
+// fp32 formulas the header states exist ONCE and the two libraries agree bit for bit.  Every fused step is an explicit
+// __builtin_fmaf; the including file switches contraction off before the include.  Division and square root are IEEE (hipcc's
+// default for fp32, and g++'s).  Nothing here touches memory other than through the pointers it is given.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define SG_RS_FN __host__ __device__ __forceinline__
+#else
+#define SG_RS_FN static inline
+#endif
+
+enum {
+    SG_RS_SUB = 256,              // fixed-point units per sample: 8 sub-pixel bits
+    SG_RS_HALF = 128,             // a sample centre sits at index * 256 + 128
+    SG_RS_GUARD = 1 << 22,        // |snapped coordinate| <= 2^22: edge products stay below 2^47
+    SG_RS_TILE = 16,              // samples per tile side
+    SG_RS_TILE_SHIFT = 4,
+    SG_RS_CHUNK = 256,            // triangle records staged per LDS chunk
+    SG_RS_NEAR = 1, SG_RS_GUARDED = 2, SG_RS_ZERO_AREA = 4, SG_RS_BACK = 8, SG_RS_DROPPED = 15, SG_RS_OFFSCREEN = 16,
+    SG_RS_PARAMS = 60             // doubles of the shading parameter block
+};
+
+// One triangle under one view: 16 words.
+struct SgRasterRec {
+    int x[3], y[3];               // snapped window coordinates (y down: row 0 is NDC y = +1)
+    float z[3], iw[3];            // NDC depth and 1 / w of the corners
+    int px0, py0, px1, py1;       // the samples whose centres lie in the snapped bounding box, clamped to the image (empty: px0 > px1)
+};
+
+struct SgRasterParams {           // the parameter block rounded to fp32: layout in include/shapegan_hip.h
+    float vp[16], lvp[16], ivp[16], cam[3], light[3], albedo[3], background[3];
+};
+
+SG_RS_FN void sg_rs_params_from_host(const double* p, SgRasterParams* q) {
+    float* f = (float*)q;
+    for (int i = 0; i < SG_RS_PARAMS; ++i) f[i] = (float)p[i];
+}
+
+// row i of M (row-major 4x4) times (x, y, z, 1) resp. (x, y, z, 0): the constant term first, then x, y, z
+SG_RS_FN float sg_rs_row_point(const float* M, int i, float x, float y, float z) {
+    return __builtin_fmaf(M[i * 4 + 2], z, __builtin_fmaf(M[i * 4 + 1], y, __builtin_fmaf(M[i * 4], x, M[i * 4 + 3])));
+}
+SG_RS_FN float sg_rs_row_dir(const float* M, int i, float x, float y, float z) {
+    return __builtin_fmaf(M[i * 4 + 2], z, __builtin_fmaf(M[i * 4 + 1], y, M[i * 4] * x));
+}
+SG_RS_FN float sg_rs_dot(const float* a, const float* b) { return __builtin_fmaf(a[2], b[2], __builtin_fmaf(a[1], b[1], a[0] * b[0])); }
+SG_RS_FN void sg_rs_normalize(float* v) {
+    const float len = __builtin_sqrtf(sg_rs_dot(v, v));
+    v[0] = v[0] / len;
+    v[1] = v[1] / len;
+    v[2] = v[2] / len;
+}
+SG_RS_FN float sg_rs_clamp01(float v) { return __builtin_fminf(__builtin_fmaxf(v, 0.f), 1.f); }      // NaN -> 0
+
+// the order-preserving integer image of a float (signed compare) and back
+SG_RS_FN int sg_rs_float_key(float f) {
+    const int b = __builtin_bit_cast(int, f);
+    return b >= 0 ? b : b ^ 0x7fffffff;
+}
+SG_RS_FN float sg_rs_key_float(int k) { return __builtin_bit_cast(float, k >= 0 ? k : k ^ 0x7fffffff); }
+
+SG_RS_FN int64_t sg_rs_area2(const SgRasterRec& r) {
+    return (int64_t)(r.x[1] - r.x[0]) * (r.y[2] - r.y[0]) - (int64_t)(r.x[2] - r.x[0]) * (r.y[1] - r.y[0]);
+}
+
+// Setup of one triangle: p = its nine coordinates, M = the view's VP in fp32.  Returns the flags; a dropped triangle gets a record of
+// zeros with an empty sample box.  clip (may be NULL) receives the twelve clip coordinates.
+SG_RS_FN int sg_rs_setup(const float* p, const float* M, int W, int H, int cull_back, float near_w, SgRasterRec* r, float* clip) {
+    float c[3][4];
+    for (int k = 0; k < 3; ++k)
+        for (int i = 0; i < 4; ++i) {
+            c[k][i] = sg_rs_row_point(M, i, p[k * 3], p[k * 3 + 1], p[k * 3 + 2]);
+            if (clip) clip[k * 4 + i] = c[k][i];
+        }
+    SgRasterRec t;
+    int flags = 0;
+    for (int k = 0; k < 3; ++k)
+        if (!(c[k][3] > near_w)) flags = SG_RS_NEAR;
+    if (!flags) {
+        const float hw = (float)(W * SG_RS_HALF), hh = (float)(H * SG_RS_HALF);
+        for (int k = 0; k < 3; ++k) {
+            const float w = c[k][3];
+            const float fx = __builtin_fmaf(c[k][0] / w, hw, hw), fy = __builtin_fmaf(c[k][1] / w, -hh, hh);
+            t.z[k] = c[k][2] / w;
+            t.iw[k] = 1.0f / w;
+            if (!(__builtin_fabsf(fx) <= (float)SG_RS_GUARD) || !(__builtin_fabsf(fy) <= (float)SG_RS_GUARD)) {
+                flags = SG_RS_GUARDED;
+                t.x[k] = t.y[k] = 0;
+            } else {
+                t.x[k] = (int)__builtin_rintf(fx);
+                t.y[k] = (int)__builtin_rintf(fy);
+            }
+        }
+    }
+    if (!flags) {
+        const int64_t a2 = sg_rs_area2(t);
+        if (a2 == 0) flags = SG_RS_ZERO_AREA;
+        else if (cull_back && a2 > 0) flags = SG_RS_BACK;      // y runs down: counter-clockwise on the screen is a2 < 0
+    }
+    if (flags) {
+        for (int k = 0; k < 3; ++k) {
+            r->x[k] = r->y[k] = 0;
+            r->z[k] = r->iw[k] = 0.f;
+        }
+        r->px0 = r->py0 = 1;
+        r->px1 = r->py1 = 0;
+        return flags;
+    }
+    int x0 = t.x[0] < t.x[1] ? t.x[0] : t.x[1], x1 = t.x[0] < t.x[1] ? t.x[1] : t.x[0];
+    int y0 = t.y[0] < t.y[1] ? t.y[0] : t.y[1], y1 = t.y[0] < t.y[1] ? t.y[1] : t.y[0];
+    x0 = x0 < t.x[2] ? x0 : t.x[2];
+    x1 = x1 > t.x[2] ? x1 : t.x[2];
+    y0 = y0 < t.y[2] ? y0 : t.y[2];
+    y1 = y1 > t.y[2] ? y1 : t.y[2];
+    // centres index * 256 + 128 inside [lo, hi]: index from ceil((lo - 128) / 256) to floor((hi - 128) / 256)
+    t.px0 = (x0 + SG_RS_HALF - 1) >> 8;
+    t.px1 = (x1 - SG_RS_HALF) >> 8;
+    t.py0 = (y0 + SG_RS_HALF - 1) >> 8;
+    t.py1 = (y1 - SG_RS_HALF) >> 8;
+    t.px0 = t.px0 < 0 ? 0 : t.px0;
+    t.py0 = t.py0 < 0 ? 0 : t.py0;
+    t.px1 = t.px1 > W - 1 ? W - 1 : t.px1;
+    t.py1 = t.py1 > H - 1 ? H - 1 : t.py1;
+    if (t.px0 > t.px1 || t.py0 > t.py1) {
+        flags = SG_RS_OFFSCREEN;
+        t.px0 = t.py0 = 1;
+        t.px1 = t.py1 = 0;
+    }
+    *r = t;
+    return flags;
+}
+
+// Coverage of the sample (px, py) by the triangle: e[i] = the edge function opposite corner i, signed so that the inside is
+// positive, their sum = |2 area|.  A sample exactly on an edge belongs to the triangle only if that edge is a top or a left one.
+SG_RS_FN bool sg_rs_cover(const int* x, const int* y, int px, int py, int64_t* e, int64_t* area2) {
+    const int sx = px * SG_RS_SUB + SG_RS_HALF, sy = py * SG_RS_SUB + SG_RS_HALF;
+    const int64_t a2 = (int64_t)(x[1] - x[0]) * (y[2] - y[0]) - (int64_t)(x[2] - x[0]) * (y[1] - y[0]);
+    const int s = a2 < 0 ? -1 : 1;
+    bool in = true;
+    for (int i = 0; i < 3; ++i) {
+        const int a = (i + 1) % 3, b = (i + 2) % 3;
+        const int dx = (x[b] - x[a]) * s, dy = (y[b] - y[a]) * s;
+        const int64_t v = (int64_t)dx * (sy - y[a]) - (int64_t)dy * (sx - x[a]);
+        const bool top_left = dy < 0 || (dy == 0 && dx > 0);
+        in = in && (v > 0 || (v == 0 && top_left));
+        e[i] = v;
+    }
+    *area2 = a2 < 0 ? -a2 : a2;
+    return in;
+}
+
+// NDC depth at a covered sample: screen-space barycentrics l1 = e1 * inv, l2 = e2 * inv (inv = 1 / (float)|2 area|)
+SG_RS_FN float sg_rs_depth(const int64_t* e, float inv, float z0, float dz1, float dz2) {
+    const float l1 = (float)e[1] * inv, l2 = (float)e[2] * inv;
+    return __builtin_fmaf(l2, dz2, __builtin_fmaf(l1, dz1, z0));
+}
+
+// ---- shading ----------------------------------------------------------------------------------------------------------------------
+// one nearest-texel comparison of the shadow map (rows run down, texture v runs up), coordinates clamped to the edge
+SG_RS_FN float sg_rs_shadow_tap(const float* smap, int N, int ix, int iy, float ref) {
+    ix = ix < 0 ? 0 : (ix > N - 1 ? N - 1 : ix);
+    iy = iy < 0 ? 0 : (iy > N - 1 ? N - 1 : iy);
+    return ref > smap[(long)(N - 1 - iy) * N + ix] ? 1.f : 0.f;
+}
+SG_RS_FN int sg_rs_texel(float t, int N) {      // floor(t) as an int, kept within [-1, N] (NaN -> -1)
+    return (int)__builtin_fminf(__builtin_fmaxf(__builtin_floorf(t), -1.f), (float)N);
+}
+// sp = lightVP * (p, 1); d = clamp(n . L, 0, 1)
+SG_RS_FN float sg_rs_shadow(const float* sp, float d, const float* smap, int N) {
+    const float cx = __builtin_fmaf(sp[0] / sp[3], 0.5f, 0.5f), cy = __builtin_fmaf(sp[1] / sp[3], 0.5f, 0.5f),
+                cz = __builtin_fmaf(sp[2] / sp[3], 0.5f, 0.5f);
+    if (!(cz <= 1.0f)) return 0.f;
+    const float ref = cz - __builtin_fmaxf(0.002f * (1.0f - d), 0.001f) / sp[3];
+    const float fN = (float)N, invN = 1.0f / fN;
+    float sum = 0.f;
+    for (int ox = -1; ox <= 1; ++ox)
+        for (int oy = -1; oy <= 1; ++oy) {
+            const float tx = __builtin_fmaf(__builtin_fmaf((float)ox, invN, cx), fN, 0.5f);
+            const float ty = __builtin_fmaf(__builtin_fmaf((float)oy, invN, cy), fN, 0.5f);
+            const float fx = tx - __builtin_floorf(tx), fy = ty - __builtin_floorf(ty);
+            const int ix = sg_rs_texel(tx, N), iy = sg_rs_texel(ty, N);
+            const float lb = sg_rs_shadow_tap(smap, N, ix, iy, ref), lt = sg_rs_shadow_tap(smap, N, ix, iy + 1, ref);
+            const float rb = sg_rs_shadow_tap(smap, N, ix + 1, iy, ref), rt = sg_rs_shadow_tap(smap, N, ix + 1, iy + 1, ref);
+            const float a = __builtin_fmaf(lt - lb, fy, lb), b = __builtin_fmaf(rt - rb, fy, rb);
+            sum += __builtin_fmaf(b - a, fx, a);
+        }
+    return sg_rs_clamp01(sum / 9.0f);
+}
+
+SG_RS_FN unsigned char sg_rs_byte(float c) { return (unsigned char)(int)__builtin_floorf(__builtin_fmaf(sg_rs_clamp01(c), 255.f, 0.5f)); }
+
+// The colour of one sample.  id / depth: the camera pass's result at the sample; recs: the camera pass's records; positions / normals:
+// the packed soup (normals may be NULL); smap: this shape's shadow map [N][N]; ground: this shape's ground level.
+SG_RS_FN void sg_rs_shade(int px, int py, int W, int H, int id, float depth, long T, const SgRasterRec* recs, const float* positions,
+                          const float* normals, const float* smap, int N, float ground, const SgRasterParams& P, unsigned char* rgb) {
+    // the floor: the eye ray through the sample centre against the plane y = ground; it wins where it is nearer than the mesh
+    if (P.cam[1] > ground) {
+        const float nx = __builtin_fmaf((float)px + 0.5f, 2.0f / (float)W, -1.0f), ny = __builtin_fmaf((float)py + 0.5f, -2.0f / (float)H, 1.0f);
+        float h[4];
+        for (int i = 0; i < 4; ++i) h[i] = sg_rs_row_point(P.ivp, i, nx, ny, 1.0f);
+        const float dx = h[0] / h[3] - P.cam[0], dy = h[1] / h[3] - P.cam[1], dz = h[2] / h[3] - P.cam[2];
+        const float t = (ground - P.cam[1]) / dy;
+        const float fx = __builtin_fmaf(t, dx, P.cam[0]), fz = __builtin_fmaf(t, dz, P.cam[2]);
+        if (t > 0.f && __builtin_fabsf(fx) <= 6.0f && __builtin_fabsf(fz) <= 6.0f) {
+            float pos[4], sp[4], up[3], L[3];
+            for (int i = 0; i < 4; ++i) pos[i] = sg_rs_row_point(P.vp, i, fx, ground, fz);
+            const float zf = pos[2] / pos[3];
+            if (pos[3] > 0.f && zf >= -1.0f && zf <= 1.0f && zf < depth) {
+                for (int i = 0; i < 4; ++i) sp[i] = sg_rs_row_point(P.lvp, i, fx, ground, fz);
+                for (int i = 0; i < 3; ++i) {
+                    up[i] = P.vp[i * 4 + 1];
+                    L[i] = P.light[i] - pos[i];
+                }
+                sg_rs_normalize(up);
+                sg_rs_normalize(L);
+                const float shadow = sg_rs_shadow(sp, sg_rs_clamp01(sg_rs_dot(up, L)), smap, N);
+                rgb[0] = rgb[1] = rgb[2] = sg_rs_byte(__builtin_fmaf(shadow, -0.6f, 1.0f));
+                return;
+            }
+        }
+    }
+    if (id >= 0 && id < T) {
+        const SgRasterRec r = recs[id];
+        int64_t e[3], a2;
+        sg_rs_cover(r.x, r.y, px, py, e, &a2);
+        const float inv = 1.0f / (float)a2;
+        const float q0 = ((float)e[0] * inv) * r.iw[0], q1 = ((float)e[1] * inv) * r.iw[1], q2 = ((float)e[2] * inv) * r.iw[2];
+        const float qs = (q0 + q1) + q2;
+        const float b0 = q0 / qs, b1 = q1 / qs, b2 = q2 / qs;
+        const float* v = positions + (long)id * 9;
+        float p[3], n[3];
+        for (int c = 0; c < 3; ++c) p[c] = __builtin_fmaf(b2, v[6 + c], __builtin_fmaf(b1, v[3 + c], b0 * v[c]));
+        if (normals) {
+            const float* m = normals + (long)id * 9;
+            for (int c = 0; c < 3; ++c) n[c] = __builtin_fmaf(b2, m[6 + c], __builtin_fmaf(b1, m[3 + c], b0 * m[c]));
+        } else {
+            const float ax = v[3] - v[0], ay = v[4] - v[1], az = v[5] - v[2], bx = v[6] - v[0], by = v[7] - v[1], bz = v[8] - v[2];
+            n[0] = __builtin_fmaf(ay, bz, -(az * by));
+            n[1] = __builtin_fmaf(az, bx, -(ax * bz));
+            n[2] = __builtin_fmaf(ax, by, -(ay * bx));
+        }
+        float pos[3], sp[4], nv[3], L[3], V[3], R[3];
+        for (int i = 0; i < 3; ++i) pos[i] = sg_rs_row_point(P.vp, i, p[0], p[1], p[2]);
+        for (int i = 0; i < 4; ++i) sp[i] = sg_rs_row_point(P.lvp, i, p[0], p[1], p[2]);
+        for (int i = 0; i < 3; ++i) nv[i] = sg_rs_row_dir(P.vp, i, n[0], n[1], n[2]);
+        sg_rs_normalize(nv);
+        for (int i = 0; i < 3; ++i) {
+            L[i] = P.light[i] - pos[i];
+            V[i] = -pos[i];
+        }
+        sg_rs_normalize(L);
+        sg_rs_normalize(V);
+        const float nl = sg_rs_dot(nv, L);
+        for (int i = 0; i < 3; ++i) R[i] = __builtin_fmaf(-2.0f * nl, nv[i], L[i]);      // reflect(L, n)
+        sg_rs_normalize(R);
+        for (int i = 0; i < 3; ++i) R[i] = -R[i];
+        const float d = sg_rs_clamp01(nl);
+        const float lit = 1.0f - sg_rs_shadow(sp, d, smap, N);
+        const float s1 = __builtin_fmaxf(0.f, sg_rs_dot(R, V)), s2 = s1 * s1, s4 = s2 * s2, s8 = s4 * s4, s16 = s8 * s8, s20 = s16 * s4;
+        const float m1 = 1.0f - sg_rs_clamp01(-nv[2]), m2 = m1 * m1, m4 = m2 * m2;
+        for (int c = 0; c < 3; ++c) {
+            const float t1 = P.albedo[c] * 0.5f;
+            rgb[c] = sg_rs_byte(((t1 + (t1 * d) * lit) + (0.3f * s20) * lit) + 0.3f * m4);
+        }
+        return;
+    }
+    for (int c = 0; c < 3; ++c) rgb[c] = sg_rs_byte(P.background[c]);
+}

@@ -2227,3 +2227,176 @@ int sg_occupancy_histogram_cpu(const float* clouds, long S, long P, int R, int64
 #pragma GCC pop_options
 
 }  // extern "C"
+
+// ---- K14: tiled rasteriser (include/shapegan_hip.h) --------------------------------------------------------------------------------
+// The per-triangle and per-sample arithmetic is csrc/raster_core.h, the file the HIP kernels include: one statement of every fp32
+// formula.  What is written here is the part the header leaves to each library: the loops, the bins (filled in triangle order) and
+// the search for the winner.
+#pragma GCC push_options
+#pragma GCC optimize("fp-contract=off")
+#include "../csrc/raster_core.h"
+
+static inline int rs_cdiv(int a, int b) { return (a + b - 1) / b; }
+static inline bool rs_view_ok(long S, long T, int W, int H) {
+    return S >= 1 && S <= 65535 && T >= 0 && T <= 2147483647L && W >= 1 && H >= 1 && W <= 16384 && H <= 16384 &&
+           S * (long)rs_cdiv(W, SG_RS_TILE) * rs_cdiv(H, SG_RS_TILE) <= 2147483647L;
+}
+
+extern "C" {
+
+int sg_raster_setup_cpu(const float* positions, const int64_t* tri_offsets, long S, long T, const double* vp, int width, int height,
+                        int cull_back, double near_w, int* recs, int* flags, float* clip, int* dropped, float* ground, int* tile_counts,
+                        hipStream_t_) {
+    CPU_CHECK(rs_view_ok(S, T, width, height) && tri_offsets && vp && dropped && tile_counts);
+    CPU_CHECK(T == 0 || (positions && recs && flags));
+    float M[16];
+    for (int i = 0; i < 16; ++i) M[i] = (float)vp[i];
+    const int ntx = rs_cdiv(width, SG_RS_TILE), nty = rs_cdiv(height, SG_RS_TILE);
+    std::fill(tile_counts, tile_counts + S * (long)ntx * nty, 0);
+    SgRasterRec* R = (SgRasterRec*)recs;
+#pragma omp parallel for schedule(static)
+    for (long t = 0; t < T; ++t) flags[t] = sg_rs_setup(positions + t * 9, M, width, height, cull_back, (float)near_w, &R[t], clip ? clip + t * 12 : nullptr);
+    for (long s = 0; s < S; ++s) {
+        dropped[s] = 0;
+        float g = INFINITY;
+        int* counts = tile_counts + s * (long)ntx * nty;
+        const long t0 = std::max<long>(tri_offsets[s], 0), t1 = std::min<long>(tri_offsets[s + 1], T);
+        for (long t = t0; t < t1; ++t) {
+            for (int k = 0; k < 3; ++k) g = std::min(g, positions[t * 9 + k * 3 + 1]);
+            if (flags[t] & SG_RS_DROPPED) dropped[s] += 1;
+            if (flags[t]) continue;
+            for (int ty = R[t].py0 >> SG_RS_TILE_SHIFT; ty <= R[t].py1 >> SG_RS_TILE_SHIFT; ++ty)
+                for (int tx = R[t].px0 >> SG_RS_TILE_SHIFT; tx <= R[t].px1 >> SG_RS_TILE_SHIFT; ++tx) counts[ty * ntx + tx] += 1;
+        }
+        if (ground) ground[s] = t1 > t0 ? g : -1.0f;
+    }
+    return SG_OK;
+}
+
+int sg_raster_scan_cpu(const int* tile_counts, long ntiles, int64_t* tile_offsets, int* cursor, int* active, int64_t* totals,
+                       hipStream_t_) {
+    CPU_CHECK(tile_counts && tile_offsets && cursor && active && totals && ntiles >= 1 && ntiles <= 2147483647L);
+    int64_t run = 0, nact = 0;
+    for (long i = 0; i < ntiles; ++i) {
+        const int c = tile_counts[i] > 0 ? tile_counts[i] : 0;
+        tile_offsets[i] = run;
+        cursor[i] = 0;
+        if (c > 0) active[nact++] = (int)i;
+        run += c;
+    }
+    tile_offsets[ntiles] = run;
+    totals[0] = run;
+    totals[1] = nact;
+    return SG_OK;
+}
+
+int sg_raster_fill_cpu(const int* recs, const int* flags, const int64_t* tri_offsets, long S, long T, int width, int height,
+                       const int64_t* tile_offsets, int* cursor, int* lists, long capacity, hipStream_t_) {
+    CPU_CHECK(rs_view_ok(S, T, width, height) && tri_offsets && tile_offsets && cursor && capacity >= 0);
+    if (T == 0 || capacity == 0) return SG_OK;
+    CPU_CHECK(recs && flags && lists);
+    const SgRasterRec* R = (const SgRasterRec*)recs;
+    const int ntx = rs_cdiv(width, SG_RS_TILE), nty = rs_cdiv(height, SG_RS_TILE);
+    for (long s = 0; s < S; ++s) {
+        const long t0 = std::max<long>(tri_offsets[s], 0), t1 = std::min<long>(tri_offsets[s + 1], T);
+        for (long t = t0; t < t1; ++t) {
+            if (flags[t]) continue;
+            const SgRasterRec& r = R[t];
+            if (r.px0 < 0 || r.py0 < 0 || (r.px1 >> SG_RS_TILE_SHIFT) >= ntx || (r.py1 >> SG_RS_TILE_SHIFT) >= nty) continue;
+            for (int ty = r.py0 >> SG_RS_TILE_SHIFT; ty <= r.py1 >> SG_RS_TILE_SHIFT; ++ty)
+                for (int tx = r.px0 >> SG_RS_TILE_SHIFT; tx <= r.px1 >> SG_RS_TILE_SHIFT; ++tx) {
+                    const long g = s * (long)ntx * nty + ty * ntx + tx;
+                    const long at = tile_offsets[g] + cursor[g]++;
+                    if (at >= tile_offsets[g] && at < tile_offsets[g + 1] && at < capacity) lists[at] = (int)t;
+                }
+        }
+    }
+    return SG_OK;
+}
+
+int sg_raster_visibility_cpu(const int* recs, const int64_t* tri_offsets, long S, int width, int height, const int64_t* tile_offsets,
+                             const int* lists, long capacity, const int* active, long nactive, int* id, float* depth, int shadow,
+                             hipStream_t_) {
+    CPU_CHECK(rs_view_ok(S, 0, width, height) && tri_offsets && tile_offsets && depth && capacity >= 0 && nactive >= 0);
+    const int ntx = rs_cdiv(width, SG_RS_TILE), nty = rs_cdiv(height, SG_RS_TILE);
+    const long ntiles = (long)ntx * nty;
+    CPU_CHECK(nactive <= S * ntiles && (nactive == 0 || (recs && lists && active)));
+    const SgRasterRec* R = (const SgRasterRec*)recs;
+    const long n = S * (long)height * width;
+    for (long i = 0; i < n; ++i) {
+        if (id) id[i] = -1;
+        depth[i] = 1.0f;
+    }
+#pragma omp parallel for schedule(dynamic)
+    for (long a = 0; a < nactive; ++a) {
+        const long g = active[a];
+        if (g < 0 || g >= S * ntiles) continue;
+        const long s = g / ntiles;
+        const int tile = (int)(g - s * ntiles), tx = tile % ntx, ty = tile / ntx;
+        const long begin = std::max<long>(tile_offsets[g], 0), end = std::min<long>(tile_offsets[g + 1], capacity);
+        for (int ly = 0; ly < SG_RS_TILE; ++ly)
+            for (int lx = 0; lx < SG_RS_TILE; ++lx) {
+                const int px = tx * SG_RS_TILE + lx, py = ty * SG_RS_TILE + ly;
+                if (px >= width || py >= height) continue;
+                float best = INFINITY;
+                int best_id = -1;
+                for (long c = begin; c < end; ++c) {
+                    const long t = lists[c];
+                    if (t < tri_offsets[s] || t >= tri_offsets[s + 1]) continue;
+                    const SgRasterRec& r = R[t];
+                    if (px < r.px0 || px > r.px1 || py < r.py0 || py > r.py1) continue;
+                    int64_t e[3], a2;
+                    if (!sg_rs_cover(r.x, r.y, px, py, e, &a2)) continue;
+                    const float z = sg_rs_depth(e, 1.0f / (float)a2, r.z[0], r.z[1] - r.z[0], r.z[2] - r.z[0]);
+                    if (z < best || (z == best && (int)t < best_id)) {
+                        best = z;
+                        best_id = (int)t;
+                    }
+                }
+                const long o = (s * height + py) * width + px;
+                if (id) id[o] = best_id;
+                depth[o] = best_id < 0 ? 1.0f : (shadow ? fmaf(0.5f, best, 0.5f) : best);
+            }
+    }
+    return SG_OK;
+}
+
+int sg_raster_shade_cpu(const float* positions, const float* normals, long T, const int* recs, const int* id, const float* depth,
+                        const float* shadow_map, int shadow_size, const float* ground, const double* params, long S, int width,
+                        int height, unsigned char* image, hipStream_t_) {
+    CPU_CHECK(rs_view_ok(S, T, width, height) && id && depth && shadow_map && shadow_size >= 1 && shadow_size <= 16384 && ground &&
+              params && image);
+    CPU_CHECK(T == 0 || (positions && recs));
+    SgRasterParams P;
+    sg_rs_params_from_host(params, &P);
+    const long n = S * (long)height * width;
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < n; ++i) {
+        const long s = i / ((long)height * width);
+        const int rem = (int)(i - s * height * width), py = rem / width, px = rem - py * width;
+        sg_rs_shade(px, py, width, height, id[i], depth[i], T, (const SgRasterRec*)recs, positions, normals,
+                    shadow_map + s * (long)shadow_size * shadow_size, shadow_size, ground[s], P, image + i * 3);
+    }
+    return SG_OK;
+}
+
+int sg_raster_resolve_cpu(const unsigned char* samples, long S, int width, int height, int ssaa, unsigned char* image, hipStream_t_) {
+    CPU_CHECK(samples && image && S >= 1 && width >= 1 && height >= 1 && ssaa >= 1 && ssaa <= 16 && (long)width * ssaa <= 16384 &&
+              (long)height * ssaa <= 16384);
+    const long Wi = (long)width * ssaa, n = ssaa * ssaa;
+#pragma omp parallel for schedule(static)
+    for (long q = 0; q < S * (long)height * width; ++q) {
+        const long s = q / ((long)height * width);
+        const int rem = (int)(q - s * height * width), y = rem / width, x = rem - y * width;
+        for (int c = 0; c < 3; ++c) {
+            long sum = 0;
+            for (int a = 0; a < ssaa; ++a)
+                for (int b = 0; b < ssaa; ++b) sum += samples[((s * height * ssaa + (long)y * ssaa + a) * Wi + (long)x * ssaa + b) * 3 + c];
+            image[q * 3 + c] = (unsigned char)((2 * sum + n) / (2 * n));
+        }
+    }
+    return SG_OK;
+}
+
+}  // extern "C"
+#pragma GCC pop_options

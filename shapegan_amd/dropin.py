@@ -2,6 +2,11 @@
 
     python -m shapegan_amd.dropin /path/to/shapegan/train_wgan.py nogui
     python -m shapegan_amd.dropin --epochs 1 /path/to/shapegan/train_autoencoder.py classic nogui
+    python -m shapegan_amd.dropin --epochs 1 --viewer-dir shots /path/to/shapegan/train_wgan.py
+
+Without `nogui` the scripts create a `rendering.MeshRenderer` and show it the current sample (train_wgan.py:22-24,79-80).  The
+native one (shapegan_amd.rendering) is headless; `--viewer-dir DIR` makes it leave a PNG in DIR for every shape it is shown, by
+setting the class-level default `MeshRenderer.snapshot_directory` before the script runs.
 
 The reference has no plugin interface: its scripts import `model.*`, `util` and `datasets` by name (train_wgan.py:13-17,
 train_autoencoder.py:6,18-20, train_sdf_autodecoder.py:13-14, train_hybrid_progressive_gan.py:15-19,
@@ -30,6 +35,9 @@ ALIASES = {
     "model.point_sdf_net": "shapegan_amd.model.point_sdf_net",
     "util": "shapegan_amd.util",
     "datasets": "shapegan_amd.datasets",
+    "rendering": "shapegan_amd.rendering",
+    "rendering.math": "shapegan_amd.rendering.math",
+    "rendering.raymarching": "shapegan_amd.rendering.raymarching",
 }
 
 # train_sdf_autodecoder.py:78 — true division of an int64 index tensor; torch >= 1.5 returns floats, which cannot index
@@ -100,8 +108,12 @@ def run_script(path, argv=(), epochs=None, replace=None, aliases=True):
 def main():
     args = sys.argv[1:]
     epochs = None
-    if args and args[0] == "--epochs":
-        epochs = int(args[1])
+    while args and args[0] in ("--epochs", "--viewer-dir"):
+        if args[0] == "--epochs":
+            epochs = int(args[1])
+        else:
+            from shapegan_amd.rendering import MeshRenderer
+            MeshRenderer.snapshot_directory = os.path.abspath(args[1])
         args = args[2:]
     if not args:
         print(__doc__)

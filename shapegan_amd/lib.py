@@ -167,6 +167,12 @@ SIGNATURES = {
     "sg_chamfer_matrix": (c_int, [_P, _P, _L, _L, _L, _L, _P, _P, _P, _Z, _P]),
     "sg_chamfer_nearest": (c_int, [_P, _P, _L, _L, _L, _P, _P, _P, _P, _P]),
     "sg_occupancy_histogram": (c_int, [_P, _L, _L, _I, _P, _P]),
+    "sg_raster_setup": (c_int, [_P, _P, _L, _L, _P, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P]),
+    "sg_raster_scan": (c_int, [_P, _L, _P, _P, _P, _P, _P]),
+    "sg_raster_fill": (c_int, [_P, _P, _P, _L, _L, _I, _I, _P, _P, _P, _L, _P]),
+    "sg_raster_visibility": (c_int, [_P, _P, _L, _I, _I, _P, _P, _L, _P, _L, _P, _P, _I, _P]),
+    "sg_raster_shade": (c_int, [_P, _P, _L, _P, _P, _P, _P, _I, _P, _P, _L, _I, _I, _P, _P]),
+    "sg_raster_resolve": (c_int, [_P, _L, _I, _I, _I, _P, _P]),
     "sg_raymarch_rays": (c_int, [_P, _I, _L, _D, _P, _P, _P, _P, _P, _P]),
     "sg_raymarch_steps": (c_int, [_P, _P, _P, _P, _P, _L, _P, _P, _L, _P, _P, _L, _L, _L, _L, _I, _F, _F, _F, _F, _F, _I, _P, _P]),
     "sg_raymarch_finish": (c_int, [_P, _P, _L, _P, _P, _L, _L, _P]),
