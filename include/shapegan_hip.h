@@ -676,6 +676,60 @@ int sg_raster_shade(const float* positions, const float* normals, long T, const 
                     unsigned char* image, hipStream_t stream);
 int sg_raster_resolve(const unsigned char* samples, long S, int width, int height, int ssaa, unsigned char* image, hipStream_t stream);
 
+/* ---- K15: earth mover's distance between point clouds: forward auction with eps-scaling ------------------------------------------
+ * The second family of scores of Achlioptas et al.'s evaluation code (MMD-EMD, COV-EMD; K13 is the Chamfer family).  Two clouds a, b
+ * [P][3] fp32 of the SAME point count P, 1 <= P <= SG_EMD_MAX_POINTS.  d(i, j) = sqrtf(d2(a_i, b_j)) in f32, d2 exactly K13's value
+ * (sqrtf and the f32 division below are the correctly rounded IEEE operations).  Distances are Euclidean, NOT squared:
+ *   emd*(a, b) = min over the permutations pi of (1/P) sum_i d(i, pi(i))        (that code's match_cost / P)
+ * The library returns a permutation `match` and emd = (1/P) sum_i d(i, match[i]), the float64 sum of the f32 d in K13's order
+ * (s[l] = d[l] + d[256 + l] + ..., halving tree over l = 0..255, one division by P).
+ * GUARANTEE (status 0): match is a permutation of [0, P) and emd <= emd* + eps; eps > 0 is the caller's absolute bound, in
+ * coordinate units per point.
+ *
+ * Arithmetic: all of the auction is int32, so the GPU and the twin execute the same rounds and agree BIT FOR BIT on match, emd,
+ * rounds and status.  u = the largest f32 that is not above eps / 4; the cost of a pair is  q = d / u (f32);  k = q < 2^22 ? (int) floorf(q) : 2^22
+ * (SG_EMD_MAX_COST; NaN and inf land there: the comparison is false).  kmax = the largest k of the pair of clouds.
+ * Phases: e = max(1, kmax >> 4); a phase runs with e; after it e = max(1, e >> 2); the phase with e = 1 is the last.  Prices p[j]
+ * (int32, 0 at the start) are KEPT between phases, the assignment is RESET (everybody unassigned, nothing owned).
+ * Round (Jacobi: every bid of a round is computed from the prices at its start): each unassigned i finds over the objects j
+ *   v(j) = -k(i, j) - p[j];   w1 = max v,  j1 = the LOWEST j with v(j) = w1,  w2 = max over j != j1 of v(j)  (w2 = w1 when P = 1)
+ * and bids  p[j1] + (w1 - w2) + e  for j1.  An object that received bids takes the HIGHEST, from the LOWEST bidder index on a tie:
+ * its price becomes the bid, the bidder its owner, the previous owner unassigned.  A phase ends when nobody is unassigned.  These
+ * maxima do not depend on the order they are taken in.
+ * Bound: the last phase ends with sum k(match) <= sum k(pi*) + P (Bertsekas: within P e of the optimum of the integer problem).
+ * k u <= d < (k + 1) u up to ONE unit of k for the rounding of d / u (q < 2^22, so |fl(q) - q| < 1/2), hence per point
+ * d(match) < (k(match) + 2) u and k(pi*) u <= d(pi*) + u:  emd < emd* + (1 + 2 + 1) u = emd* + eps.
+ * Prices stay below 2^28: a phase raises the largest by at most 2 (2^22 + e) and there are at most 11 phases.
+ * Every loop is bounded: a phase that has not ended after SG_EMD_ROUND_CAP rounds stops the pair.
+ * status (int32 per pair): 0 ok; SG_EMD_STATUS_ROUND_CAP: emd = NaN, match in range but no permutation; SG_EMD_STATUS_EPS: a FINITE
+ * d of the pair has d / u >= 2^22 — eps is smaller than the arithmetic supports for these clouds (the smallest accepted is
+ * 2^-20 x their largest distance: 1.7e-6 inside the unit cube); no auction is run, emd = NaN, match[i] = i.  Non-finite coordinates
+ * are no error: status 0 and a valid permutation, the value unspecified, no fault and no index outside [0, P).
+ *
+ * sg_emd_match: matched batches A, B [S][P][3] -> emd [S] float64, status [S], match [S][P] int32 (match[s][i] = the point of B_s
+ *   that point i of A_s is sent to; may be NULL), rounds [S] int32 (all phases; may be NULL).  S <= 65535 per call.
+ * sg_emd_matrix: A [Sa][P][3], B [Sb][P][3] -> emd, status [Sa][Sb]: entry [i][j] has A_i as bidders and B_j as objects and is
+ *   BITWISE sg_emd_match's value of that pair.  symmetric != 0: the caller passes the same set twice (Sa = Sb); only i < j is
+ *   computed, [j][i] is its copy and the diagonal exact 0 with status 0.  workspace: rounds [Sa][Sb] int32, written like status
+ *   (a count for the caller to read, never an index).  Sa, Sb <= 65535 per call.
+ * Errors (SG_ERR_ARG): P < 1, P > SG_EMD_MAX_POINTS: larger clouds are refused, not mishandled;, eps <= 0 or not finite.
+ * One workgroup per pair, all auction state in LDS; sg_emd_match_impl (testing / tuning) sets the number of bidders of a round
+ * at or below which a whole wave scans the objects for one bidder (wave_scan_at <= 256; above it: one lane per bidder) and the
+ * number at or below which the whole workgroup does (block_scan_at <= 16); < 0 = the default.  The results do not depend on them.
+ * reference: metrics.py:18-46 (as K13: the clouds are written for that evaluation code). */
+#define SG_EMD_MAX_POINTS 2048
+#define SG_EMD_MAX_COST 4194304   /* 2^22 */
+#define SG_EMD_ROUND_CAP 1048576   /* 2^20 */
+#define SG_EMD_STATUS_ROUND_CAP 1
+#define SG_EMD_STATUS_EPS 2
+int sg_emd_match(const float* A, const float* B, long S, long P, double eps, int* match, double* emd, int* rounds, int* status,
+                 hipStream_t stream);
+int sg_emd_match_impl(const float* A, const float* B, long S, long P, double eps, int* match, double* emd, int* rounds, int* status,
+                      int wave_scan_at, int block_scan_at, hipStream_t stream);
+size_t sg_emd_matrix_workspace_bytes(long Sa, long Sb, long P);
+int sg_emd_matrix(const float* A, const float* B, long Sa, long Sb, long P, double eps, int symmetric, double* emd, int* status,
+                  void* workspace, size_t workspace_bytes, hipStream_t stream);
+
 /* ---- sphere tracing of SDFNet shapes (rendering/raymarching.py:render_image, get_shadows) ----------------------------------
  * S images of the same camera, M = width^2 pixels each; ray r = s * M + pixel.  Rays live in segments with an active list each
  * (active [2][nrays], counts [3][nseg] int32, seg_off [nseg + 1] int64): step `iter` reads list iter & 1 / counts iter % 3 and

@@ -2224,6 +2224,152 @@ int sg_occupancy_histogram_cpu(const float* clouds, long S, long P, int R, int64
     }
     return SG_OK;
 }
+
+// ---- K15: earth mover's distance (include/shapegan_hip.h): the same rounds as csrc/emd.hip, from a table of the integer costs ----
+#define SG_EMD_MAX_POINTS 2048
+#define SG_EMD_MAX_COST (1 << 22)
+#define SG_EMD_ROUND_CAP (1 << 20)
+
+// the largest f32 that is not above eps / 4; 0 when eps is not a positive finite number or eps / 4 is below the normal range
+static float emd_unit(double eps) {
+    if (!(eps > 0.0) || !(eps < INFINITY) || eps / 4 < 1.17549435e-38) return 0.f;
+    float u = (float)(eps / 4);
+    if ((double)u > eps / 4) u = nextafterf(u, 0.f);
+    return u;
+}
+
+struct EmdScratch {
+    std::vector<int> cost, price, owner, asg, list;
+    std::vector<uint64_t> bid;
+    std::vector<float> d;
+};
+
+static void emd_pair(const float* a, const float* b, int P, float u, int* match, double* emd, int* rounds, int* status, EmdScratch& w) {
+    w.cost.resize((size_t)P * P);
+    int kmax = 0;
+    bool too_small = false;
+    for (int i = 0; i < P; ++i)
+        for (int j = 0; j < P; ++j) {
+            const float d = sqrtf(cd_pair(a + i * 3, b + j * 3));
+            const float q = d / u;
+            const int k = q < (float)SG_EMD_MAX_COST ? (int)floorf(q) : SG_EMD_MAX_COST;      // NaN: the comparison is false
+            too_small |= d < INFINITY && q >= (float)SG_EMD_MAX_COST;
+            w.cost[(size_t)i * P + j] = k;
+            kmax = k > kmax ? k : kmax;
+        }
+    w.asg.resize(P);
+    for (int i = 0; i < P; ++i) w.asg[i] = i;
+    int total = 0, st = too_small ? 2 : 0;
+    if (!too_small) {
+        w.price.assign(P, 0);
+        w.bid.assign(P, 0);
+        w.owner.resize(P);
+        for (int e = kmax >> 4 > 1 ? kmax >> 4 : 1; st == 0; e = e >> 2 > 1 ? e >> 2 : 1) {
+            for (int i = 0; i < P; ++i) w.owner[i] = -1, w.asg[i] = i;
+            for (int r = 0;; ++r) {
+                w.list.clear();
+                for (int i = 0; i < P; ++i)
+                    if (w.owner[w.asg[i]] != i) w.list.push_back(i);
+                if (w.list.empty()) break;
+                if (r == SG_EMD_ROUND_CAP) {
+                    st = 1;
+                    break;
+                }
+                ++total;
+                for (int i : w.list) {
+                    const int* c = &w.cost[(size_t)i * P];
+                    int w1 = INT32_MIN, w2 = INT32_MIN, j1 = 0;
+                    for (int j = 0; j < P; ++j) {       // increasing j, strict: the lowest j of a tie stays
+                        const int v = -c[j] - w.price[j];
+                        if (v > w1) {
+                            w2 = w1;
+                            w1 = v;
+                            j1 = j;
+                        } else if (v > w2) {
+                            w2 = v;
+                        }
+                    }
+                    if (w2 == INT32_MIN) w2 = w1;       // P = 1
+                    // (bid, 65535 - bidder): one maximum picks the highest bid and, among equals, the lowest bidder
+                    const uint64_t word = ((uint64_t)(uint32_t)(w.price[j1] + (w1 - w2) + e) << 32) | (uint32_t)(0xFFFF - i);
+                    w.bid[j1] = word > w.bid[j1] ? word : w.bid[j1];
+                    w.asg[i] = j1;
+                }
+                for (int j = 0; j < P; ++j)
+                    if (w.bid[j]) {
+                        w.price[j] = (int)(w.bid[j] >> 32);
+                        w.owner[j] = 0xFFFF - (int)(w.bid[j] & 0xFFFF);
+                        w.bid[j] = 0;
+                    }
+            }
+            if (e == 1) break;
+        }
+    }
+    if (st == 0) {
+        w.d.resize(P);
+        for (int i = 0; i < P; ++i) w.d[i] = sqrtf(cd_pair(a + i * 3, b + w.asg[i] * 3));
+        *emd = cd_mean(w.d.data(), P);
+    } else {
+        *emd = NAN;
+    }
+    if (match)
+        for (int i = 0; i < P; ++i) match[i] = w.asg[i];
+    if (rounds) *rounds = total;
+    *status = st;
+}
+
+static bool emd_args_ok(long S, long P, double eps, const char* who) {
+    if (P < 1 || P > SG_EMD_MAX_POINTS || S < 1 || S > 65535) {
+        snprintf(g_err, sizeof(g_err), "%s: 1 <= P <= %d points per cloud and at most 65535 clouds per call, got P = %ld", who,
+                 SG_EMD_MAX_POINTS, P);
+        return false;
+    }
+    if (emd_unit(eps) == 0.f) {
+        snprintf(g_err, sizeof(g_err), "%s: eps must be a finite number of at least 4.8e-38, got %g", who, eps);
+        return false;
+    }
+    return true;
+}
+
+int sg_emd_match_cpu(const float* A, const float* B, long S, long P, double eps, int* match, double* emd, int* rounds, int* status,
+                     hipStream_t_) {
+    CPU_CHECK(A && B && emd && status);
+    if (!emd_args_ok(S, P, eps, __func__)) return SG_ERR_ARG;
+    const float u = emd_unit(eps);
+#pragma omp parallel
+    {
+        EmdScratch w;
+#pragma omp for schedule(dynamic)
+        for (long s = 0; s < S; ++s)
+            emd_pair(A + s * P * 3, B + s * P * 3, (int)P, u, match ? match + s * P : nullptr, emd + s, rounds ? rounds + s : nullptr,
+                     status + s, w);
+    }
+    return SG_OK;
+}
+
+int sg_emd_matrix_cpu(const float* A, const float* B, long Sa, long Sb, long P, double eps, int symmetric, double* emd, int* status,
+                      void* workspace, size_t workspace_bytes, hipStream_t_) {
+    CPU_CHECK(A && B && emd && status && workspace && Sb >= 1 && Sb <= 65535 && (!symmetric || Sa == Sb));
+    if (!emd_args_ok(Sa, P, eps, __func__)) return SG_ERR_ARG;
+    CPU_CHECK(workspace_bytes >= (size_t)(Sa * Sb) * sizeof(int));
+    const float u = emd_unit(eps);
+    int* rounds = (int*)workspace;
+#pragma omp parallel
+    {
+        EmdScratch w;
+#pragma omp for schedule(dynamic)
+        for (long e = 0; e < Sa * Sb; ++e) {
+            const long i = e / Sb, j = e % Sb;
+            if (symmetric && i >= j) {
+                if (i == j) emd[e] = 0.0, status[e] = 0, rounds[e] = 0;
+                continue;
+            }
+            emd_pair(A + i * P * 3, B + j * P * 3, (int)P, u, nullptr, emd + e, rounds + e, status + e, w);
+            if (symmetric) emd[j * Sb + i] = emd[e], status[j * Sb + i] = status[e], rounds[j * Sb + i] = rounds[e];
+        }
+    }
+    return SG_OK;
+}
 #pragma GCC pop_options
 
 }  // extern "C"

@@ -167,6 +167,10 @@ SIGNATURES = {
     "sg_chamfer_matrix": (c_int, [_P, _P, _L, _L, _L, _L, _P, _P, _P, _Z, _P]),
     "sg_chamfer_nearest": (c_int, [_P, _P, _L, _L, _L, _P, _P, _P, _P, _P]),
     "sg_occupancy_histogram": (c_int, [_P, _L, _L, _I, _P, _P]),
+    "sg_emd_match": (c_int, [_P, _P, _L, _L, _D, _P, _P, _P, _P, _P]),
+    "sg_emd_match_impl": (c_int, [_P, _P, _L, _L, _D, _P, _P, _P, _P, _I, _I, _P]),
+    "sg_emd_matrix_workspace_bytes": (_Z, [_L, _L, _L]),
+    "sg_emd_matrix": (c_int, [_P, _P, _L, _L, _L, _D, _I, _P, _P, _P, _Z, _P]),
     "sg_raster_setup": (c_int, [_P, _P, _L, _L, _P, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P]),
     "sg_raster_scan": (c_int, [_P, _L, _P, _P, _P, _P, _P]),
     "sg_raster_fill": (c_int, [_P, _P, _P, _L, _L, _I, _I, _P, _P, _P, _L, _P]),
