@@ -1041,6 +1041,9 @@ int halo_dgrad_try(const float* dy, const float* w, const float* bias, float* dx
 constexpr int kWROWD = 368;                 // 18 rows x 20 floats, padded so that a kd step shifts banks by 16
 constexpr int kWHS = kHD * kWROWD;          // floats per channel box
 constexpr int kWNF = (2 * kHD * kHH + 7) / 8;  // 18 copy elements per thread per stage (2 channels x 72 rows / 8 half-waves)
+// Plane stride of the static-skip form (conv_wgrad_halo_kernel<2, true>, below): its column tiles hold all four kd of both channels, so
+// a kd step has to shift banks by 12 and a channel step (4 planes = 1456) by 16 — see the bank table above the kernel.
+constexpr int kWROWD_SKIP = 364;
 
 struct HaloWgradArgs {
     const float4* ap;   // packed dy: [mt][slice][8 groups][64 lanes]
@@ -1083,12 +1086,43 @@ __global__ void __launch_bounds__(256) pack_wgrad_dy_kernel(const float* __restr
 // padding and the gather GEMM — 0.42 of the matrix peak — was the faster choice): every wave owns ONE of four channels and the
 // SAME two row tiles, i.e. 64 output rows x (4 channels x 64 taps): the same 4 x 4 MFMA tiles per k-group and wave, no empty row
 // tile.  The four channels' boxes share their per-thread copy offsets (the channel is a scalar offset of the load); Cin % 4 == 0.
-template <int NCH>
-__global__ void __launch_bounds__(256) conv_wgrad_halo_kernel(HaloWgradArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float wbox[];  // [2 buffers][2 channels][kHD][kWROWD]
+//
+// SKIP (NCH 2, grids with OH == 8: the 8x8 tile spans the whole H extent, so box row 0 is ih = -1 and box row 17 is ih = 16 in EVERY
+// stage of every workgroup): the MFMAs whose B operand is all padding are not issued.  A k-pair of an MFMA is two neighbouring ow at one
+// (od, oh = gq), so an MFMA is all padding when its whole 32-column tile has the tap row kh with 2 gq + kh - 1 outside [0, 16).  The
+// workgroup's 128 columns are therefore mapped so that a tile is uniform in kh:
+//     tile (wn, tn) = tap row kh = 2 wn + tn of BOTH channels,   lane r -> (ci_l = r >> 4, kd = (r >> 2) & 3, kw = r & 3)
+// and wave wn = 0 drops tile tn = 0 (kh 0) in k-group gq = 0 (ih = -1), wave wn = 1 drops tile tn = 1 (kh 3) in gq = 7 (ih = 16): 8 of
+// the 128 MFMAs of a stage each (1/16), with the four ds_read_b32 that fed them — the same for both column waves, every stage, every
+// workgroup and every K split.  The variant is chosen ONCE, by a wave-uniform branch on wn at the top of the kernel into two
+// instantiations of the whole body (conv_wgrad_halo_body<2, 0 / 1>: sharing the prologue and epilogue around two copies of the loop
+// takes 256 VGPRs + 91 AGPRs and the second wave per SIMD — the allocator then moves the accumulators between register classes
+// around the two loops); the stage body itself stays one basic block, and both instantiations execute the same barriers in the same order.  The A
+// ring, the copy schedule, the barrier count and the element of `ws` a (co, ci, tap) goes to are those of the generic form.  Code:
+// 35.8 KB against 17.7 KB (a wave runs one half of it), 183 VGPRs + 64 AGPRs, two waves per SIMD as the generic form.
+//   Exact: a dropped product has B = 0 (the copy's out-of-range loads return 0), fma(a, 0, acc) = acc, and the k order of every
+//   accumulator is unchanged, so for finite dy the result is bit-identical to the generic form up to the sign of a zero (acc = -0 would
+//   have become +0 by adding a +0 product).  For a non-finite dy the generic form produces 0 * Inf = NaN at the taps that touch the
+//   padding; this form does not — it returns what the convolution's definition gives, the sum over the in-range positions.
+//   Banks (ds_read_b32: bank = dword address % 32, conflicts inside a 32-lane half only; kpar is constant in a half): a lane reads
+//   ci_l * 4 P + kd * P + kh * 20 + (kw & 1) * 10 + (kw >> 1) + uniform, P = the plane stride.  kw gives {0, 10, 1, 11}; with
+//   P = kWROWD_SKIP = 364 = 12 mod 32, kd adds {0, 12, 24, 4}: 16 distinct banks {0-5, 10-15, 22-25}, and the channel step 1456 = 16
+//   mod 32 maps them onto the other 16 — conflict-free.  (P = kWROWD = 368 = 16 would put kd 0 / 2 and 1 / 3 on the same banks, 4-way
+//   with the channel step 1472 = 0.)  The copy's ds_write_b32 pattern is independent of P inside the box: a half-wave stores one row,
+//   18 lanes on (w & 1) * 10 + (w >> 1) = 18 distinct banks; its 14 out-of-box lanes store to 7 other rows' pad slots (9 and 19 of a
+//   row), which land on busy banks 2- or 3-way for either P (of the 36 store instructions of a stage, worst half: 24 x 2-way and
+//   12 x 3-way at P = 368, 20 and 16 at P = 364) — 18 stores per thread against 128 MFMAs of 64 cycles.
+// V: the static-skip variant of the calling wave — -1 none (the generic form), 0 / 1: column wave wn = V of the SKIP form.
+template <int NCH, int V>
+__device__ __forceinline__ void conv_wgrad_halo_body(const HaloWgradArgs& a) {
+    constexpr bool SKIP = V >= 0;
+    static_assert(!SKIP || NCH == 2, "the static-skip column map is the 2-channel form's");
+    constexpr int WROWD = SKIP ? kWROWD_SKIP : kWROWD;  // per-variant plane and channel strides of the box
+    constexpr int WHS = kHD * WROWD;
+    extern __shared__ __attribute__((aligned(16))) float wbox[];  // [2 buffers][NCH channels][kHD][WROWD]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = NCH == 2 ? wave >> 1 : 0, wn = NCH == 2 ? wave & 1 : wave, r = lane & 31, kpar = lane >> 5;
+    const int wm = NCH == 2 ? wave >> 1 : 0, wn = SKIP ? V : (NCH == 2 ? wave & 1 : wave), r = lane & 31, kpar = lane >> 5;
     const int ci0 = blockIdx.x * NCH;                  // the input channels (64 output columns each) of this workgroup
     const int mt0 = blockIdx.y * (NCH == 2 ? 4 : 2);   // 128 (64) output rows = 4 (2) row tiles of 32
     constexpr int NF = NCH == 2 ? kWNF : 2 * kWNF;     // copy elements per thread per stage
@@ -1096,13 +1130,15 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo_kernel(HaloWgradArgs a) {
     const int split = blockIdx.z;
     const int s_beg = split * a.per_split, s_end = min(a.nslice, s_beg + a.per_split);
 
-    // lane -> tap of its column inside each of the wave's two 32-column tiles: col = wn*64 + tn*32 + r
+    // lane -> (channel, tap) of its column inside each of the wave's two 32-column tiles: col = wn*64 + tn*32 + r is
+    // (ci_l = wn, tap = tn*32 + r); SKIP: tile = tap row kh = 2 wn + tn, lane r = (ci_l, kd, kw)
+    auto col_ci = [&](int tn) { return SKIP ? r >> 4 : (wn * 64 + tn * 32 + r) >> 6; };
+    auto col_tap = [&](int tn) { return SKIP ? ((r >> 2) & 3) * 16 + (2 * wn + tn) * 4 + (r & 3) : (tn * 32 + r) & 63; };
     int lanebase[2];
 #pragma unroll
     for (int tn = 0; tn < 2; ++tn) {
-        const int col = wn * 64 + tn * 32 + r;  // == (ci_l = wn, tap = tn*32 + r)
-        const int tap = col & 63, kd = tap >> 4, kh = (tap >> 2) & 3, kw = tap & 3;
-        lanebase[tn] = (col >> 6) * kWHS + kd * kWROWD + kh * kROWH + (kw & 1) * kHWH + (kw >> 1) + kpar;
+        const int tap = col_tap(tn), kd = tap >> 4, kh = (tap >> 2) & 3, kw = tap & 3;
+        lanebase[tn] = col_ci(tn) * WHS + kd * WROWD + kh * kROWH + (kw & 1) * kHWH + (kw >> 1) + kpar;
     }
 
     f32x16 acc[2][2];
@@ -1120,12 +1156,15 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo_kernel(HaloWgradArgs a) {
     // through six edge flags (first / last tile in D, H, W): the element's class bits sit in bits 26..31 of `cls`, the
     // stage's flags in the same bits of a scalar, and (cls & flags) | voff is >= num_records (2^26) exactly for padding —
     // one v_and_or_b32 per element per stage is all the vector work the copy needs; the hardware returns 0 for those.
-    // Threads outside the box store to an unread pad slot (column 9 of a half row). ----
+    // Threads outside the box store to an unread pad slot (column 9 of a half row).
+    // SKIP: the H flags (bits 28, 29) are set in every stage, so the class bits ride in the offset word itself — voff | cls, an
+    // always-outside element is the bare bit 28 — and the stage's offsets are voff & (flags | 0x03ffffff): the same values with half
+    // the registers, which is what keeps this form at two waves per SIMD. ----
     const int I3 = a.g.ID * a.g.IH * a.g.IW;
     const int fl_w = tid & 31, frow = tid >> 5;
     const int lds_w = (fl_w & 1) * kHWH + (fl_w >> 1);
     const int prow = (tid >> 1) % (kHD * kHH);
-    const int pad = (prow / kHH) * kWROWD + (prow % kHH) * kROWH + (tid & 1) * kHWH + (kHWH - 1);
+    const int pad = (prow / kHH) * WROWD + (prow % kHH) * kROWH + (tid & 1) * kHWH + (kHWH - 1);
     lds_float* const wl = (lds_float*)wbox;
     lds_float* sdst[kWNF / 2];   // LDS destination of the row inside (buffer 0, channel 0); identical for both channels
     unsigned voff[NV], cls[NV];
@@ -1134,7 +1173,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo_kernel(HaloWgradArgs a) {
         const int row = 8 * f + frow;
         const int hd = row / kHH, hh = row - hd * kHH;
         const bool inbox = fl_w < kHWF && row < kHD * kHH;
-        sdst[f] = wl + (inbox ? hd * kWROWD + hh * kROWH + lds_w : pad);
+        sdst[f] = wl + (inbox ? hd * WROWD + hh * kROWH + lds_w : pad);
         pin_vgpr(sdst[f]);
 #pragma unroll
         for (int c = 0; c < (NCH == 2 ? 2 : 1); ++c) {
@@ -1143,8 +1182,12 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo_kernel(HaloWgradArgs a) {
             cls[c * (kWNF / 2) + f] = (hd == 0 ? 1u << 26 : 0u) | (hd == kHD - 1 ? 1u << 27 : 0u) | (hh == 0 ? 1u << 28 : 0u) |
                                       (hh == kHH - 1 ? 1u << 29 : 0u) | (fl_w == 0 ? 1u << 30 : 0u) |
                                       (fl_w == kHWF - 1 ? 1u << 31 : 0u);
+            if constexpr (SKIP) {
+                voff[c * (kWNF / 2) + f] = ok ? voff[c * (kWNF / 2) + f] | cls[c * (kWNF / 2) + f] : 1u << 28;
+            } else {
+                pin_vgpr(cls[c * (kWNF / 2) + f]);
+            }
             pin_vgpr(voff[c * (kWNF / 2) + f]);
-            pin_vgpr(cls[c * (kWNF / 2) + f]);
         }
     }
     float fv[NF];
@@ -1173,7 +1216,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo_kernel(HaloWgradArgs a) {
                                ((int)thi == nth_ - 1 ? 1u << 29 : 0u) | (twi == 0 ? 1u << 30 : 0u) |
                                ((int)twi == ntw_ - 1 ? 1u << 31 : 0u);
 #pragma unroll
-        for (int f = 0; f < NV; ++f) eoff[f] = (cls[f] & flags) | voff[f];
+        for (int f = 0; f < NV; ++f) eoff[f] = SKIP ? voff[f] & (flags | 0x03ffffffu) : (cls[f] & flags) | voff[f];
     };
 
     const int nst = s_end - s_beg;
@@ -1184,17 +1227,29 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo_kernel(HaloWgradArgs a) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) ares[t] = make_rsrc(a.ap + ((long)(mt0 + wm * 2 + t) * a.nslice + s_beg) * 8 * 64);
         const unsigned avoff = lane * 16;
-        // B-fragment read addresses: (buffer, column tile, k-groups 0-3 / 4-7); the rest are immediates
+        // B-fragment read addresses: (buffer, column tile, k-groups 0-3 / 4-7); the rest are immediates.  SKIP: the wave's two
+        // tiles are one tap row (kROWH) apart, so one address serves and all of (buffer, tile, k-group) is immediate.
         const lds_float* bb[2][2][2];
+        if constexpr (SKIP) {
+            const lds_float* b0 = wl + lanebase[0];
+            pin_vgpr(b0);
 #pragma unroll
-        for (int b = 0; b < 2; ++b)
+            for (int b = 0; b < 2; ++b)
 #pragma unroll
-            for (int tn = 0; tn < 2; ++tn)
+                for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    bb[b][tn][h] = wl + b * (NCH * kWHS) + lanebase[tn] + h * (8 * kROWH);
-                    pin_vgpr(bb[b][tn][h]);
-                }
+                    for (int h = 0; h < 2; ++h) bb[b][tn][h] = b0 + b * (NCH * WHS) + tn * kROWH + h * (8 * kROWH);
+        } else {
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        bb[b][tn][h] = wl + b * (NCH * WHS) + lanebase[tn] + h * (8 * kROWH);
+                        pin_vgpr(bb[b][tn][h]);
+                    }
+        }
 
         copy_prepare(s_beg);
 #pragma unroll
@@ -1205,15 +1260,19 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo_kernel(HaloWgradArgs a) {
 #pragma unroll
             for (int t = 0; t < 2; ++t) aring[u][t] = buf_load4(ares[t], avoff, (unsigned)(u < G ? u : G - 1) * 1024u);
 #pragma unroll
-        for (int f = 0; f < NF; ++f) sdst[f % (kWNF / 2)][(f / (kWNF / 2)) * kWHS] = fv[f];
+        for (int f = 0; f < NF; ++f) sdst[f % (kWNF / 2)][(f / (kWNF / 2)) * WHS] = fv[f];
         __syncthreads();
 
+        // V 0: tile 0 (kh 0) is padding in k-group 0, V 1: tile 1 (kh 3) in k-group 7.  dead(tn, gq) folds after unrolling: a dead
+        // tile's LDS reads and MFMAs are simply not emitted.
         auto stage = [&](auto tag, int st) {
             constexpr int CUR = decltype(tag)::value, NXT = CUR ^ 1;
+            auto dead = [](int tn, int gq) { return (V == 0 && tn == 0 && gq == 0) || (V == 1 && tn == 1 && gq == 7); };
             const int snext = st + 1 < nst ? st + 1 : st;   // last stage: re-copy into the idle buffer
-            float bq[2][4];
+            float bq[2][4] = {};
 #pragma unroll
             for (int tn = 0; tn < 2; ++tn) {
+                if (dead(tn, 0)) continue;
                 const lds_float* hb = bb[CUR][tn][0];
                 bq[tn][0] = hb[0];
                 bq[tn][1] = hb[2];
@@ -1239,6 +1298,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo_kernel(HaloWgradArgs a) {
                 if (gq + 1 < 8) {
 #pragma unroll
                     for (int tn = 0; tn < 2; ++tn) {
+                        if (dead(tn, gq + 1)) continue;
                         const lds_float* hb = bb[CUR][tn][(gq + 1) >> 2] + 2 * ((gq + 1) & 3) * kROWH;
                         bq[tn][0] = hb[0];
                         bq[tn][1] = hb[2];
@@ -1250,17 +1310,21 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo_kernel(HaloWgradArgs a) {
 #pragma unroll
                 for (int f = 0; f < NF; ++f) {
                     if (f * 4 / NF == gq) fv[f] = copy_load(f);
-                    if (f * 4 / NF + 4 == gq) sdst[f % (kWNF / 2)][NXT * (NCH * kWHS) + (f / (kWNF / 2)) * kWHS] = fv[f];
+                    if (f * 4 / NF + 4 == gq) sdst[f % (kWNF / 2)][NXT * (NCH * WHS) + (f / (kWNF / 2)) * WHS] = fv[f];
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float a0 = j == 0 ? a_cur[0].x : (j == 1 ? a_cur[0].y : (j == 2 ? a_cur[0].z : a_cur[0].w));
                     const float a1 = j == 0 ? a_cur[1].x : (j == 1 ? a_cur[1].y : (j == 2 ? a_cur[1].z : a_cur[1].w));
-                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b[0][j], acc[0][0], 0, 0, 0);
-                    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b[0][j], acc[1][0], 0, 0, 0);
-                    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b[1][j], acc[0][1], 0, 0, 0);
-                    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b[1][j], acc[1][1], 0, 0, 0);
+                    if (!dead(0, gq)) {
+                        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b[0][j], acc[0][0], 0, 0, 0);
+                        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b[0][j], acc[1][0], 0, 0, 0);
+                    }
+                    if (!dead(1, gq)) {
+                        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b[1][j], acc[0][1], 0, 0, 0);
+                        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b[1][j], acc[1][1], 0, 0, 0);
+                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -1277,10 +1341,9 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo_kernel(HaloWgradArgs a) {
     float* out = a.ws + (long)split * a.Cout * a.ldw;
 #pragma unroll
     for (int tn = 0; tn < 2; ++tn) {
-        const int col = wn * 64 + tn * 32 + r;
-        const int ci = ci0 + (col >> 6);
+        const int ci = ci0 + col_ci(tn);
         if (ci >= a.Cin) continue;
-        const long cbase = (long)ci * 64 + (col & 63);
+        const long cbase = (long)ci * 64 + col_tap(tn);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
 #pragma unroll
@@ -1292,11 +1355,38 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo_kernel(HaloWgradArgs a) {
     }
 }
 
+template <int NCH, bool SKIP = false>
+__global__ void __launch_bounds__(256) conv_wgrad_halo_kernel(HaloWgradArgs a) {
+    if constexpr (!SKIP) {
+        conv_wgrad_halo_body<NCH, -1>(a);
+    } else {   // wave-uniform: each column wave runs its own instantiation; the barriers of the two pair up one to one
+        if ((__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) == 0) conv_wgrad_halo_body<NCH, 0>(a);
+        else conv_wgrad_halo_body<NCH, 1>(a);
+    }
+}
+
 // ---- wgrad form on 4^3 output grids (8^3 inputs) -----------------------------------------------------------------
 // Same structure as conv_wgrad_halo_kernel with the geometry of conv_fwd_halo4_kernel: a slice is a whole sample (its 64
 // output positions = 8 k-groups), the box is the zero-padded 10^3 sample of the workgroup's two input channels (padding
 // written once, a stage copies 2 x 512 contiguous floats), positions of a group: od = gq >> 1, oh = 2 (gq & 1) + (j >> 1),
 // ow = 2 (j & 1) + kpar.
+//
+// Static padding skip: od = gq >> 1 of every MFMA is a compile-time constant, so with column tiles that are uniform in kd,
+//     tile (wn, tn) = tap plane kd = 2 wn + tn of BOTH channels,   lane r -> (ci_l = r >> 4, kh = (r >> 2) & 3, kw = r & 3),
+// tile kd = 0 reads the zero plane id = -1 in k-groups 0, 1 (od 0) and tile kd = 3 reads id = 8 in k-groups 6, 7 (od 3).  Wave wn = 0
+// drops tile tn = 0 in groups 0, 1, wave wn = 1 drops tile tn = 1 in groups 6, 7: 16 of the 128 MFMAs of a stage each (1/8), with their
+// eight ds_read_b32 — the same in both column waves, every stage, workgroup and K split.  As in conv_wgrad_halo_kernel<2, true> the
+// variant is chosen once by a wave-uniform branch into two instantiations of the body (conv_wgrad_halo4_body<0 / 1>; 26.0 KB of code
+// against 13.1 KB, 164 VGPRs + 64 AGPRs), and the same exactness statement holds: the dropped products
+// have B = 0 (the box's zero planes 0 and 9, which are now never read), the k order of every accumulator is unchanged, so the result
+// is bit-identical for finite dy up to the sign of a zero; a non-finite dy no longer yields the 0 * Inf = NaN of the padded product.
+//   The box has its own strides (conv_fwd_halo4_kernel keeps k4*): half 6, row 12, plane 120, channel 1200.  Banks (dword address
+//   % 32 inside a 32-lane half): a lane reads ci_l * 1200 + kh * 12 + (kw & 1) * 6 + (kw >> 1) + uniform.  kw gives {0, 6, 1, 7}, kh adds
+//   {0, 12, 24, 4}: 16 distinct banks {0, 1, 4-7, 10-13, 18, 19, 24, 25, 30, 31}, and the channel step 1200 = 16 mod 32 maps them onto
+//   the other 16 — conflict-free (half 5 / row 10 has no channel step that does; the former tap-major tiles were 2-way on it).  The
+//   copy's ds_write_b32 (a half-wave = 4 rows of 8 consecutive iw) is 2-way with these strides as it was with k4*.  LDS 19 200 B
+//   (was 16 640): not what limits the workgroups per CU.
+constexpr int kW4HALF = 6, kW4ROW = 12, kW4PLANE = 120, kW4CH = 10 * kW4PLANE;
 // ap[((mt*nslice + sl)*8 + gq)*64 + lane] = float4{ dy[sl][mt*32 + (lane&31)][pos(gq, j, lane>>5)], j = 0..3 }
 __global__ void __launch_bounds__(256) pack_wgrad_dy4_kernel(const float* __restrict__ dy, float4* __restrict__ ap, int Cout,
                                                              int MT, int nslice) {
@@ -1318,13 +1408,14 @@ __global__ void __launch_bounds__(256) pack_wgrad_dy4_kernel(const float* __rest
     }
 }
 
-__global__ void __launch_bounds__(256) conv_wgrad_halo4_kernel(HaloWgradArgs a) {
-    constexpr int kBUF = 2 * k4CH;  // two channels per buffer
-    extern __shared__ __attribute__((aligned(16))) float wbox[];  // [2 buffers][2 channels][k4CH]
+template <int V>   // V = the column wave wn of the caller
+__device__ __forceinline__ void conv_wgrad_halo4_body(const HaloWgradArgs& a) {
+    constexpr int kBUF = 2 * kW4CH;  // two channels per buffer
+    extern __shared__ __attribute__((aligned(16))) float wbox[];  // [2 buffers][2 channels][kW4CH]
     lds_float* const wl = (lds_float*)wbox;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1, r = lane & 31, kpar = lane >> 5;
+    const int wm = wave >> 1, wn = V, r = lane & 31, kpar = lane >> 5;
     const int ci0 = blockIdx.x * 2, mt0 = blockIdx.y * 4, split = blockIdx.z;
     const int s_beg = split * a.per_split, s_end = min(a.nslice, s_beg + a.per_split);
     const int nst = s_end - s_beg;
@@ -1340,17 +1431,17 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo4_kernel(HaloWgradArgs a) 
     for (int e = tid; e < 2 * kBUF; e += 256) wl[e] = 0.f;   // the padding, once
 
     if (nst > 0) {
-        // lane = tap of its column: col = wn*64 + tn*32 + r = (channel wn, tap tn*32 + r); one address per (buffer, tn, od)
+        // tile (wn, tn) = tap plane kd = 2 wn + tn of both channels, lane r = (ci_l, kh, kw); one address per (buffer, tn, od)
         const lds_float* bb[2][2][4];
 #pragma unroll
         for (int tn = 0; tn < 2; ++tn) {
-            const int tap = tn * 32 + r, kd = tap >> 4, kh = (tap >> 2) & 3, kw = tap & 3;
-            const int lb = wn * k4CH + kd * k4PLANE + kh * k4ROW + (kw & 1) * k4HALF + (kw >> 1) + kpar;
+            const int kd = 2 * wn + tn, kh = (r >> 2) & 3, kw = r & 3;
+            const int lb = (r >> 4) * kW4CH + kd * kW4PLANE + kh * kW4ROW + (kw & 1) * kW4HALF + (kw >> 1) + kpar;
 #pragma unroll
             for (int b = 0; b < 2; ++b)
 #pragma unroll
                 for (int od = 0; od < 4; ++od) {
-                    bb[b][tn][od] = wl + b * kBUF + lb + od * (2 * k4PLANE);
+                    bb[b][tn][od] = wl + b * kBUF + lb + od * (2 * kW4PLANE);
                     pin_vgpr(bb[b][tn][od]);
                 }
         }
@@ -1362,7 +1453,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo4_kernel(HaloWgradArgs a) 
             const int e = tid + 256 * f, c = e >> 9, idx = e & 511;
             const int id = idx >> 6, ih = (idx >> 3) & 7, iw = idx & 7;
             voff[f] = (ci0 + c) < a.Cin ? (unsigned)e * 4u : kBufOutside;
-            sdst[f] = wl + c * k4CH + (id + 1) * k4PLANE + (ih + 1) * k4ROW + ((iw + 1) & 1) * k4HALF + ((iw + 1) >> 1);
+            sdst[f] = wl + c * kW4CH + (id + 1) * kW4PLANE + (ih + 1) * kW4ROW + ((iw + 1) & 1) * kW4HALF + ((iw + 1) >> 1);
             pin_vgpr(voff[f]);
             pin_vgpr(sdst[f]);
         }
@@ -1390,18 +1481,22 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo4_kernel(HaloWgradArgs a) 
         for (int f = 0; f < 4; ++f) *sdst[f] = fv[f];
         __syncthreads();
 
+        // V 0: tile 0 (kd 0) is padding in k-groups 0, 1 (od 0), V 1: tile 1 (kd 3) in k-groups 6, 7 (od 3).  dead(tn, gq) folds
+        // after unrolling: a dead tile's LDS reads and MFMAs are simply not emitted.
         auto stage = [&](auto tag, int st) {
             constexpr int CUR = decltype(tag)::value, NXT = CUR ^ 1;
+            auto dead = [](int tn, int gq) { return (V == 0 && tn == 0 && gq < 2) || (V == 1 && tn == 1 && gq >= 6); };
             const int snext = st + 1 < nst ? st + 1 : st;   // last stage: re-copy into the idle buffer
             const __amdgpu_buffer_rsrc_t xres = make_rsrc(xb + (long)snext * slice_floats);
-            float bq[2][4];
+            float bq[2][4] = {};
 #pragma unroll
             for (int tn = 0; tn < 2; ++tn) {
+                if (dead(tn, 0)) continue;
                 const lds_float* hb = bb[CUR][tn][0];
                 bq[tn][0] = hb[0];
                 bq[tn][1] = hb[2];
-                bq[tn][2] = hb[2 * k4ROW];
-                bq[tn][3] = hb[2 * k4ROW + 2];
+                bq[tn][2] = hb[2 * kW4ROW];
+                bq[tn][3] = hb[2 * kW4ROW + 2];
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -1421,11 +1516,12 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo4_kernel(HaloWgradArgs a) 
                 if (gq + 1 < 8) {
 #pragma unroll
                     for (int tn = 0; tn < 2; ++tn) {
-                        const lds_float* hb = bb[CUR][tn][(gq + 1) >> 1] + ((gq + 1) & 1) * (4 * k4ROW);
+                        if (dead(tn, gq + 1)) continue;
+                        const lds_float* hb = bb[CUR][tn][(gq + 1) >> 1] + ((gq + 1) & 1) * (4 * kW4ROW);
                         bq[tn][0] = hb[0];
                         bq[tn][1] = hb[2];
-                        bq[tn][2] = hb[2 * k4ROW];
-                        bq[tn][3] = hb[2 * k4ROW + 2];
+                        bq[tn][2] = hb[2 * kW4ROW];
+                        bq[tn][3] = hb[2 * kW4ROW + 2];
                     }
                 }
                 if (gq < 4) fv[gq] = buf_load(xres, voff[gq], 0);                 // copy of the next sample: loads ...
@@ -1435,10 +1531,14 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo4_kernel(HaloWgradArgs a) 
                 for (int j = 0; j < 4; ++j) {
                     const float a0 = j == 0 ? a_cur[0].x : (j == 1 ? a_cur[0].y : (j == 2 ? a_cur[0].z : a_cur[0].w));
                     const float a1 = j == 0 ? a_cur[1].x : (j == 1 ? a_cur[1].y : (j == 2 ? a_cur[1].z : a_cur[1].w));
-                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b[0][j], acc[0][0], 0, 0, 0);
-                    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b[0][j], acc[1][0], 0, 0, 0);
-                    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b[1][j], acc[0][1], 0, 0, 0);
-                    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b[1][j], acc[1][1], 0, 0, 0);
+                    if (!dead(0, gq)) {
+                        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b[0][j], acc[0][0], 0, 0, 0);
+                        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b[0][j], acc[1][0], 0, 0, 0);
+                    }
+                    if (!dead(1, gq)) {
+                        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b[1][j], acc[0][1], 0, 0, 0);
+                        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b[1][j], acc[1][1], 0, 0, 0);
+                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -1455,10 +1555,9 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo4_kernel(HaloWgradArgs a) 
     float* out = a.ws + (long)split * a.Cout * a.ldw;
 #pragma unroll
     for (int tn = 0; tn < 2; ++tn) {
-        const int col = wn * 64 + tn * 32 + r;
-        const int ci = ci0 + (col >> 6);
+        const int ci = ci0 + (r >> 4);
         if (ci >= a.Cin) continue;
-        const long cbase = (long)ci * 64 + (col & 63);
+        const long cbase = (long)ci * 64 + (2 * wn + tn) * 16 + (r & 15);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
 #pragma unroll
@@ -1468,6 +1567,12 @@ __global__ void __launch_bounds__(256) conv_wgrad_halo4_kernel(HaloWgradArgs a) 
             }
         }
     }
+}
+
+__global__ void __launch_bounds__(256) conv_wgrad_halo4_kernel(HaloWgradArgs a) {
+    // wave-uniform: each column wave runs its own instantiation; the barriers of the two pair up one to one
+    if ((__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) == 0) conv_wgrad_halo4_body<0>(a);
+    else conv_wgrad_halo4_body<1>(a);
 }
 
 // sums the split partials [nsplit][Cout][Cin*64] into dw[Cout][Cin_total*64]
@@ -1631,14 +1736,20 @@ int halo_wgrad_try(const float* dy, const float* x, float* dw, int batch, int Ci
     a.ldw = direct ? (long)Cin_total * 64 : (long)Cin * 64;
     if (mode4) {
         hipLaunchKernelGGL(conv_wgrad_halo4_kernel, dim3((Cin + 1) / 2, mtiles, nsplit), dim3(256),
-                           (size_t)2 * 2 * k4CH * sizeof(float), stream, a);
+                           (size_t)2 * 2 * kW4CH * sizeof(float), stream, a);
     } else {
         if (rows64) {
             const size_t lds = (size_t)2 * 4 * kWHS * sizeof(float);
-            hipLaunchKernelGGL(conv_wgrad_halo_kernel<4>, dim3(Cin / 4, mtiles, nsplit), dim3(256), lds, stream, a);
+            hipLaunchKernelGGL((conv_wgrad_halo_kernel<4, false>), dim3(Cin / 4, mtiles, nsplit), dim3(256), lds, stream, a);
         } else {
-            const size_t lds = (size_t)2 * 2 * kWHS * sizeof(float);
-            hipLaunchKernelGGL(conv_wgrad_halo_kernel<2>, dim3((Cin + 1) / 2, mtiles, nsplit), dim3(256), lds, stream, a);
+            // OH == 8: the 8x8 tile spans H, which rows of the box are padding is static -> the form that skips them
+            if (g.OH == 8) {
+                const size_t lds = (size_t)2 * 2 * kHD * kWROWD_SKIP * sizeof(float);
+                hipLaunchKernelGGL((conv_wgrad_halo_kernel<2, true>), dim3((Cin + 1) / 2, mtiles, nsplit), dim3(256), lds, stream, a);
+            } else {
+                const size_t lds = (size_t)2 * 2 * kWHS * sizeof(float);
+                hipLaunchKernelGGL((conv_wgrad_halo_kernel<2, false>), dim3((Cin + 1) / 2, mtiles, nsplit), dim3(256), lds, stream, a);
+            }
         }
     }
     if (!direct) {
