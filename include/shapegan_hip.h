@@ -127,8 +127,9 @@ int sg_convT3d_k4s2p1_to1_pre(const float* x, const float* w, const float* bias,
                               const float* in_shift, int in_act, float in_slope, int batch, int C, int ID, int IH, int IW, int act,
                               float slope, hipStream_t stream);
 /* the same with the kernel form chosen by the caller (tests / tuning; the library reads no environment variable): form 0 = the
- * dispatch rule, 1 / 2 = one output-row parity per workgroup with one / two plane walks, 3 / 4 = both row parities per workgroup
- * with one / two plane walks.  Every form computes the same sums in the same order (bit-identical results). */
+ * dispatch rule, 1 / 2 = one output-row parity per workgroup with one / two plane walks, 5 = all 64 taps per workgroup with the
+ * plane ranges per sample chosen by the library, 6 / 7 / 8 = the same with 1 / 2 / 4 plane ranges.  Forms 3 / 4 (both row parities
+ * per workgroup) were retired: SG_ERR_ARG.  Every form computes the same sums in the same order (bit-identical results). */
 int sg_convT3d_k4s2p1_to1_pre_impl(const float* x, const float* w, const float* bias, float* y, const float* in_scale,
                                    const float* in_shift, int in_act, float in_slope, int batch, int C, int ID, int IH, int IW,
                                    int act, float slope, int form, hipStream_t stream);

@@ -7,7 +7,7 @@ from shapegan_amd import ops
 wt = torch.randn(64, 1, 4, 4, 4, device="cuda") / 23.0
 bt = torch.randn(1, device="cuda")
 sc, sh = torch.ones(64, device="cuda"), torch.zeros(64, device="cuda")
-forms = [int(f) for f in sys.argv[1:]] or [1, 3, 5]
+forms = [int(f) for f in sys.argv[1:]] or [1, 5]
 for nb in (256, 64):
     y = torch.randn(nb, 64, 16, 16, 16, device="cuda")
     for form in forms:

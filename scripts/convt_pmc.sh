@@ -2,7 +2,7 @@
 # rocprofv3 counter passes for the ConvT(64->1) kernel (each counter group in its own run, kernel-trace only)
 repo=$(pwd); out=$repo/gpurun_out/convt_pmc; mkdir -p $out
 echo "# rocprofv3 --kernel-trace --pmc <group> -- python scripts/convt_pmc.py: median counter value and dispatch time per grid size"
-echo "# (kernel name + grid size identify the form and the batch: stream = one h parity, stream2 = both, all = all 64 taps per workgroup)"
+echo "# (kernel name + grid size identify the form and the batch: stream = one h parity, all = all 64 taps per workgroup)"
 cd /tmp && export TMPDIR=/tmp
 run_pmc() { name=$1; ctrs=$2
   rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d /tmp/cp/$name -o $name -- python $repo/scripts/convt_pmc.py > $out/$name.log 2>&1

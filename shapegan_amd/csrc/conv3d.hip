@@ -981,6 +981,8 @@ static int convT_to1_pre(const float* x, const float* w, const float* bias, floa
     SG_CHECK_ARG(in_act == SG_ACT_NONE || in_act == SG_ACT_RELU || (in_act == SG_ACT_LEAKY && in_slope >= 0.f && in_slope <= 1.f));
     ConvGeom g;
     if (make_geom(g, 2 * ID, 2 * IH, 2 * IW, 1, C)) SG_FAIL(SG_ERR_ARG, "sg_convT3d_k4s2p1_to1_pre: bad spatial dims");
+    if (form == 3 || form == 4)
+        SG_FAIL(SG_ERR_ARG, "sg_convT3d_k4s2p1_to1_pre_impl: forms 3 and 4 (both h parities per workgroup) were retired");
     if (edge_dgrad_stream_try(x, w, bias, y, batch, 1, 1, g, C, act, slope, stream, in_scale, in_shift, in_act, in_slope,
                               samples_per_group, y_group_stride, form) != 1)
         SG_FAIL(SG_ERR_ARG, "sg_convT3d_k4s2p1_to1_pre: not served");
@@ -994,7 +996,8 @@ int sg_convT3d_k4s2p1_to1_pre_grouped(const float* x, const float* w, const floa
                          y_group_stride, 0, stream);
 }
 // the same with the kernel form chosen by the caller (tests / tuning): 0 the dispatch rule, 1 / 2 one h parity per workgroup with
-// one / two plane walks, 3 / 4 both h parities per workgroup with one / two plane walks
+// one / two plane walks, 5 all 64 taps per workgroup with the plane ranges per sample chosen by the library, 6 / 7 / 8 the same
+// with 1 / 2 / 4 plane ranges; 3 / 4 (both h parities per workgroup) were retired and are refused
 int sg_convT3d_k4s2p1_to1_pre_impl(const float* x, const float* w, const float* bias, float* y, const float* in_scale,
                                    const float* in_shift, int in_act, float in_slope, int batch, int C, int ID, int IH, int IW,
                                    int act, float slope, int form, hipStream_t stream) {

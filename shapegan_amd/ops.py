@@ -631,7 +631,9 @@ def conv_transpose3d_to1_pre_raw(x, scale, shift, in_act, in_slope, w, b, act=AC
     the producing layer and the last transposed convolution ride in this kernel's loads (no autograd).
     outs (with scale / shift [groups, C]): x holds `groups` independent batches; batch g is written to outs[g] (equally spaced
     contiguous fp32 tensors [N / groups, 1, 2D, 2H, 2W], e.g. the fake halves of consecutive critic batches).
-    form (GPU only, tests / tuning): a kernel form of sg_convT3d_k4s2p1_to1_pre_impl instead of the dispatch rule."""
+    form (GPU only, tests / tuning): a kernel form of sg_convT3d_k4s2p1_to1_pre_impl instead of the dispatch rule: 1 / 2 one
+    output parity pair per workgroup with one / two plane walks, 5 - 8 all 64 taps per workgroup with the plane ranges per sample
+    chosen by the library / 1 / 2 / 4 (3 and 4 were retired and raise)."""
     x, w = f32c(x), f32c(w)
     N, C, D, H, W = x.shape
     if outs is not None:

@@ -343,9 +343,9 @@ def test_conv_transpose3d_to_one_channel_streaming_kernel_random_shapes():
         assert got2.data_ptr() == out.data_ptr() and torch.equal(got2, got.detach()) and bool((out[N] == 7.0).all())
     # the kernel forms of sg_convT3d_k4s2p1_to1_pre_impl (selected through the ABI; the library reads no environment variable):
     # 1 = one h parity per workgroup, 2 = the same with two plane walks per (sample, pd, ph) (the second workgroup recomputes the
-    # plane in front of its half for the carried sum), 3 / 4 = both h parities per workgroup (convT_c1_stream2_kernel, the default
-    # from 192 samples on) with one / two walks, 5 - 8 = all four (pd, ph) pairs per workgroup (convT_c1_all_kernel): the same sums
-    # in the same order, bit for bit, at any batch size
+    # plane in front of its half for the carried sum), 5 - 8 = all four (pd, ph) pairs per workgroup (convT_c1_all_kernel, the
+    # default from 192 samples on; plane ranges chosen / 1 / 2 / 4 per sample): the same sums in the same order, bit for bit, at
+    # any batch size.  Forms 3 / 4 (both h parities per workgroup) were retired and are refused.
     if DEV == "cuda":
         for N, C, R in ((9, 64, 16), (5, 24, 6), (3, 7, 4), (50, 64, 8)):
             torch.manual_seed(N + R)
@@ -353,20 +353,47 @@ def test_conv_transpose3d_to_one_channel_streaming_kernel_random_shapes():
             scale, shift = dev(torch.randn(C)), dev(torch.randn(C) * 0.3)
             one = ops.conv_transpose3d_to1_pre_raw(x, scale, shift, ACT_LEAKY, 0.2, w, b, ACT_TANH, 0.0, form=1)
             assert torch.equal(one, ops.conv_transpose3d_to1_pre_raw(x, scale, shift, ACT_LEAKY, 0.2, w, b, ACT_TANH, 0.0))
-            for form in (2, 3, 4, 5, 6, 7, 8):     # (5 - 8: all 64 taps per workgroup, plane ranges chosen / 1 / 2 / 4 per sample)
+            for form in (2, 5, 6, 7, 8):
                 other = ops.conv_transpose3d_to1_pre_raw(x, scale, shift, ACT_LEAKY, 0.2, w, b, ACT_TANH, 0.0, form=form)
                 assert torch.equal(one, other), "form %d differs from form 1 at N=%d C=%d R=%d" % (form, N, C, R)
-        # 200 samples: the dispatch rule takes the both-parity form; directly against ATen and against form 1
+            for form in (3, 4):
+                with pytest.raises(RuntimeError, match="retired"):
+                    ops.conv_transpose3d_to1_pre_raw(x, scale, shift, ACT_LEAKY, 0.2, w, b, ACT_TANH, 0.0, form=form)
+        # every output activation form of both kernels (compiled-in tanh, none, run-time), with the input transform, at partial
+        # and at full channels / planes: forms 1, 5 and 8 bit-equal, and equal to ATen
+        for N, C, R in ((3, 7, 4), (9, 64, 16)):
+            torch.manual_seed(N + C)
+            xc, wc, bc = torch.randn(N, C, R, R, R), torch.randn(C, 1, 4, 4, 4) / (C * 8) ** 0.5, torch.randn(1)
+            sc, hc = torch.randn(C), torch.randn(C) * 0.3
+            pre = F.conv_transpose3d(F.leaky_relu(xc * sc.view(1, C, 1, 1, 1) + hc.view(1, C, 1, 1, 1), 0.2), wc, bc, stride=2, padding=1)
+            x, w, b, scale, shift = dev(xc), dev(wc), dev(bc), dev(sc), dev(hc)
+            for act, fn in ((ACT_TANH, torch.tanh), (ACT_NONE, lambda t: t), (ACT_SIGMOID, torch.sigmoid)):
+                one = ops.conv_transpose3d_to1_pre_raw(x, scale, shift, ACT_LEAKY, 0.2, w, b, act, 0.0, form=1)
+                close(one, fn(pre), what="convT C->1 form 1 act=%d N=%d C=%d R=%d" % (act, N, C, R))
+                for form in (5, 8):
+                    other = ops.conv_transpose3d_to1_pre_raw(x, scale, shift, ACT_LEAKY, 0.2, w, b, act, 0.0, form=form)
+                    assert torch.equal(one, other), "form %d differs from form 1 at act=%d N=%d C=%d R=%d" % (form, act, N, C, R)
+        # the plain entry from 192 samples on: the all-taps kernel without the input transform, with channel clamps and a partial
+        # position block (C = 5, R = 3) and at full channels (C = 64, R = 2)
+        for C, R in ((5, 3), (64, 2)):
+            torch.manual_seed(C + R)
+            xc, wc, bc = torch.randn(192, C, R, R, R), torch.randn(C, 1, 4, 4, 4) / (C * 8) ** 0.5, torch.randn(1)
+            pre = F.conv_transpose3d(xc, wc, bc, stride=2, padding=1)
+            for act, fn in ((ACT_TANH, torch.tanh), (ACT_NONE, lambda t: t)):
+                got = ops.conv_transpose3d_k4s2p1(dev(xc), dev(wc), dev(bc), act, 0.0)
+                close(got, fn(pre), what="convT C->1 plain entry at 192 samples act=%d C=%d R=%d" % (act, C, R))
+        # 200 samples: the dispatch rule takes the all-taps form; directly against ATen and against form 1
         xc = torch.randn(200, 64, 16, 16, 16)
         wc, bc = torch.randn(64, 1, 4, 4, 4) / 23.0, torch.randn(1)
         x, w, b = dev(xc), dev(wc), dev(bc)
         got = ops.conv_transpose3d_k4s2p1(x, w, b, ACT_TANH, 0.0)
-        close(got, torch.tanh(F.conv_transpose3d(xc, wc, bc, stride=2, padding=1)), what="convT 64->1 at 200 samples (default: both-parity form) vs ATen")
+        close(got, torch.tanh(F.conv_transpose3d(xc, wc, bc, stride=2, padding=1)), what="convT 64->1 at 200 samples (default: all-taps form) vs ATen")
         ident_s, ident_h = dev(torch.ones(64)), dev(torch.zeros(64))
         ref1 = ops.conv_transpose3d_to1_pre_raw(x, ident_s, ident_h, ACT_NONE, 1.0, w, b, ACT_TANH, 0.0, form=1)
-        ref3 = ops.conv_transpose3d_to1_pre_raw(x, ident_s, ident_h, ACT_NONE, 1.0, w, b, ACT_TANH, 0.0, form=3)
-        assert torch.equal(ref1, ref3)
-        close(ref3, got, what="both-parity form through the input-transform entry vs the plain entry")
+        ref5 = ops.conv_transpose3d_to1_pre_raw(x, ident_s, ident_h, ACT_NONE, 1.0, w, b, ACT_TANH, 0.0, form=5)
+        assert torch.equal(ref1, ref5)
+        assert torch.equal(ref1, ops.conv_transpose3d_to1_pre_raw(x, ident_s, ident_h, ACT_NONE, 1.0, w, b, ACT_TANH, 0.0))
+        close(ref5, got, what="all-taps form through the input-transform entry vs the plain entry")
 
 
 def test_pack_group_rebuilds_every_stale_image_in_one_launch_and_only_then(monkeypatch):
