@@ -15,8 +15,10 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libshapegan_hip.so")
 SOURCES = ["conv3d.hip", "conv3d_halo.hip", "conv3d_edge.hip", "gemm.hip", "sdfnet.hip", "batchnorm.hip", "elementwise.hip", "pointnet.hip", "losses.hip", "sdf_batch.hip", "head.hip", "mesh.hip", "raymarch.hip", "pointcloud.hip", "raster.hip", "emd.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "mfma_tile.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "sdfnet_tile.h"), os.path.join(CSRC, "raster_core.h"),
-           os.path.join(HERE, "..", "include", "shapegan_hip.h")]
+ABI_HEADER = os.path.join(HERE, "..", "include", "shapegan_hip.h")
+# the arithmetic the HIP kernels share with the twin: an edit rebuilds both libraries
+CORE_HEADERS = [os.path.join(CSRC, h) for h in ("core_fn.h", "mc_tables.h", "mesh_core.h", "raymarch_core.h", "pointcloud_core.h", "raster_core.h")]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "mfma_tile.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "sdfnet_tile.h")] + CORE_HEADERS + [ABI_HEADER]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 
@@ -76,7 +78,7 @@ CPU_LIB = os.path.join(HERE, "libshapegan_cpu.so")
 def build_cpu(force=False, verbose=True):
     """libshapegan_cpu.so: the plain-C++ twin of the C ABI (csrc_cpu/shapegan_cpu.cpp), g++ + OpenMP, no GPU code."""
     src = os.path.join(HERE, "csrc_cpu", "shapegan_cpu.cpp")
-    if not (force or _stale(CPU_LIB, [src, os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "raster_core.h")])):
+    if not (force or _stale(CPU_LIB, [src, ABI_HEADER] + CORE_HEADERS)):
         return CPU_LIB
     cmd = [os.environ.get("CXX", "g++"), "-O3", "-fopenmp", "-fPIC", "-shared", "-std=c++17", "-Wall", src, "-o", CPU_LIB]
     if verbose:
@@ -93,7 +95,7 @@ COMM_LIB = os.path.join(HERE, "libshapegan_comm.so")
 def build_comm(force=False, verbose=True):
     """libshapegan_comm.so: the RCCL gradient exchange of the C ABI (csrc/comm.cpp); RCCL itself is bound at run time."""
     src = os.path.join(CSRC, "comm.cpp")
-    if not (force or _stale(COMM_LIB, [src, HEADERS[-1]])):
+    if not (force or _stale(COMM_LIB, [src, ABI_HEADER])):
         return COMM_LIB
     # host code only: g++, no -lrccl (RCCL is bound at run time, csrc/comm.cpp) and no RUNPATH into the toolchain's ROCm — the HIP
     # runtime it needs is the one the host process (PyTorch) has already mapped

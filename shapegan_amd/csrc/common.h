@@ -89,6 +89,29 @@ __device__ __forceinline__ double sg_wave_sum_d(double v) {
     return v;
 }
 
+// exclusive scan of one int per thread over a 256-thread workgroup (wave64 shuffles, then the 4 wave totals through LDS)
+__device__ __forceinline__ int sg_block_exclusive_256(int x, int* lds_waves, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = x;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int y = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += y;
+    }
+    if (lane == 63) lds_waves[wave] = incl;
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int t = lds_waves[w];
+        before += w < wave ? t : 0;
+        total += t;
+    }
+    __syncthreads();
+    return before + incl - x;
+}
+
 // ---- zero-VALU addressing helpers (see conv3d_halo.hip for the rationale) ------------------------------------------
 namespace sg {
 typedef __attribute__((address_space(3))) float lds_float;

@@ -26,6 +26,7 @@
 
 // the costs are compared bit for bit with the twin: d2 is K13's, with its two explicit fmaf
 #pragma clang fp contract(off)
+#include "pointcloud_core.h"   // distance, integer cost, unit and the argument predicate, shared with the twin
 
 namespace sg {
 
@@ -53,16 +54,6 @@ struct EmdShared {
 };
 static_assert(sizeof(EmdShared) <= 64 * 1024, "static LDS");
 static_assert(kEmdBlockScanMax * kEmdWaves * 3 * sizeof(int) <= sizeof(double) * kEmdBlock, "the partial triples fit sh.red");
-
-__device__ __forceinline__ float emd_dist(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = ax - bx, dy = ay - by, dz = az - bz;
-    return sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
-}
-
-__device__ __forceinline__ int emd_cost(float d, float u) {
-    const float q = d / u;
-    return q < (float)SG_EMD_MAX_COST ? (int)floorf(q) : SG_EMD_MAX_COST;      // NaN: the comparison is false
-}
 
 // (w1, j1, w2) of the header; objects arrive in increasing j, the strict comparison keeps the lowest j of a tie
 struct EmdTop {
@@ -126,13 +117,13 @@ __device__ __forceinline__ void emd_bid_lanes(EmdShared& sh, const float* __rest
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
-            for (int m = 0; m < M; ++m) top[m].take(-emd_cost(emd_dist(ax[m], ay[m], az[m], bx[t], by[t], bz[t]), u) - prs[t], q + t);
+            for (int m = 0; m < M; ++m) top[m].take(-sg_emd_cost(sg_emd_dist(ax[m], ay[m], az[m], bx[t], by[t], bz[t]), u) - prs[t], q + t);
     }
     for (int q = P4; q < P; ++q) {
         const float bx = sh.b[0][q], by = sh.b[1][q], bz = sh.b[2][q];
         const int pr = sh.price[q];
 #pragma unroll
-        for (int m = 0; m < M; ++m) top[m].take(-emd_cost(emd_dist(ax[m], ay[m], az[m], bx, by, bz), u) - pr, q);
+        for (int m = 0; m < M; ++m) top[m].take(-sg_emd_cost(sg_emd_dist(ax[m], ay[m], az[m], bx, by, bz), u) - pr, q);
     }
 #pragma unroll
     for (int m = 0; m < M; ++m)
@@ -154,7 +145,7 @@ __device__ __forceinline__ void emd_bid_waves(EmdShared& sh, const float* __rest
         EmdTop top;
         top.w1 = top.w2 = kEmdMin;
         top.j1 = kEmdMaxP + lane;                      // a lane without objects loses every merge
-        for (int j = lane; j < P; j += 64) top.take(-emd_cost(emd_dist(ax, ay, az, sh.b[0][j], sh.b[1][j], sh.b[2][j]), u) - sh.price[j], j);
+        for (int j = lane; j < P; j += 64) top.take(-sg_emd_cost(sg_emd_dist(ax, ay, az, sh.b[0][j], sh.b[1][j], sh.b[2][j]), u) - sh.price[j], j);
         emd_wave_reduce(top);
         if (lane == t) {
             ei = i;
@@ -177,7 +168,7 @@ __device__ __forceinline__ void emd_bid_block(EmdShared& sh, const float* __rest
         EmdTop top;
         top.w1 = top.w2 = kEmdMin;
         top.j1 = kEmdMaxP + tid;
-        for (int j = tid; j < P; j += kEmdBlock) top.take(-emd_cost(emd_dist(ax, ay, az, sh.b[0][j], sh.b[1][j], sh.b[2][j]), u) - sh.price[j], j);
+        for (int j = tid; j < P; j += kEmdBlock) top.take(-sg_emd_cost(sg_emd_dist(ax, ay, az, sh.b[0][j], sh.b[1][j], sh.b[2][j]), u) - sh.price[j], j);
         emd_wave_reduce(top);
         if (lane == 0) {
             int* slot = part + (ent * kEmdWaves + wave) * 3;
@@ -240,9 +231,9 @@ __global__ void __launch_bounds__(kEmdBlock) emd_auction_kernel(const float* __r
         for (int i = tid; i < P; i += kEmdBlock) {
             const float ax = a[i * 3], ay = a[i * 3 + 1], az = a[i * 3 + 2];
             for (int j = 0; j < P; ++j) {
-                const float d = emd_dist(ax, ay, az, sh.b[0][j], sh.b[1][j], sh.b[2][j]);
-                const int k = emd_cost(d, u);
-                too_small |= (d < __builtin_inff() && d / u >= (float)SG_EMD_MAX_COST) ? 1 : 0;
+                const float d = sg_emd_dist(ax, ay, az, sh.b[0][j], sh.b[1][j], sh.b[2][j]);
+                const int k = sg_emd_cost(d, u);
+                too_small |= sg_emd_too_small(d, u) ? 1 : 0;
                 kmax = k > kmax ? k : kmax;
             }
         }
@@ -321,7 +312,7 @@ __global__ void __launch_bounds__(kEmdBlock) emd_auction_kernel(const float* __r
     for (int i = tid; i < P; i += kEmdBlock) {
         const int j = asg[i];
         if (match) match[ci * P + i] = j;
-        s += (double)emd_dist(a[i * 3], a[i * 3 + 1], a[i * 3 + 2], sh.b[0][j], sh.b[1][j], sh.b[2][j]);
+        s += (double)sg_emd_dist(a[i * 3], a[i * 3 + 1], a[i * 3 + 2], sh.b[0][j], sh.b[1][j], sh.b[2][j]);
     }
     sh.red[tid] = s;
     __syncthreads();
@@ -344,18 +335,11 @@ __global__ void __launch_bounds__(kEmdBlock) emd_auction_kernel(const float* __r
     }
 }
 
-// the largest f32 that is not above eps / 4; 0 when eps is not a positive finite number or eps / 4 is below the normal range
-static float emd_unit(double eps) {
-    if (!(eps > 0.0) || !(eps < (double)__builtin_inff()) || eps / 4 < 1.17549435e-38) return 0.f;
-    float u = (float)(eps / 4);
-    if ((double)u > eps / 4) u = nextafterf(u, 0.f);
-    return u;
-}
-
 static int emd_check(long S, long P, double eps, const char* who) {
-    if (P < 1 || P > SG_EMD_MAX_POINTS || S < 1 || S > 65535)
+    const int refused = sg_emd_refused(S, P, eps);
+    if (refused == 1)
         SG_FAIL(SG_ERR_ARG, "%s: 1 <= P <= %d points per cloud and at most 65535 clouds per call, got P = %ld", who, SG_EMD_MAX_POINTS, P);
-    if (emd_unit(eps) == 0.f) SG_FAIL(SG_ERR_ARG, "%s: eps must be a finite number of at least 4.8e-38, got %g", who, eps);
+    if (refused) SG_FAIL(SG_ERR_ARG, "%s: eps must be a finite number of at least 4.8e-38, got %g", who, eps);
     return SG_OK;
 }
 
@@ -377,7 +361,7 @@ int sg_emd_match_impl(const float* A, const float* B, long S, long P, double eps
                       int wave_scan_at, int block_scan_at, hipStream_t stream) {
     SG_CHECK_ARG(A && B && emd && status);
     if (int rc = emd_check(S, P, eps, __func__)) return rc;
-    hipLaunchKernelGGL(emd_auction_kernel, dim3((unsigned)S), dim3(kEmdBlock), 0, stream, A, B, (int)P, emd_unit(eps), 0,
+    hipLaunchKernelGGL(emd_auction_kernel, dim3((unsigned)S), dim3(kEmdBlock), 0, stream, A, B, (int)P, sg_emd_unit(eps), 0,
                        emd_wave_scan_at(wave_scan_at), emd_block_scan_at(block_scan_at), match, emd, rounds, status);
     SG_CHECK_LAUNCH();
     return SG_OK;
@@ -398,7 +382,7 @@ int sg_emd_matrix(const float* A, const float* B, long Sa, long Sb, long P, doub
     SG_CHECK_ARG(A && B && emd && status && workspace && Sb >= 1 && Sb <= 65535 && (!symmetric || Sa == Sb));
     if (int rc = emd_check(Sa, P, eps, __func__)) return rc;
     if (workspace_bytes < sg_emd_matrix_workspace_bytes(Sa, Sb, P)) SG_FAIL(SG_ERR_WORKSPACE, "sg_emd_matrix: workspace too small");
-    hipLaunchKernelGGL(emd_auction_kernel, dim3((unsigned)Sb, (unsigned)Sa), dim3(kEmdBlock), 0, stream, A, B, (int)P, emd_unit(eps),
+    hipLaunchKernelGGL(emd_auction_kernel, dim3((unsigned)Sb, (unsigned)Sa), dim3(kEmdBlock), 0, stream, A, B, (int)P, sg_emd_unit(eps),
                        symmetric ? 2 : 1, emd_wave_scan_at(-1), emd_block_scan_at(-1), (int*)nullptr, emd, (int*)workspace, status);
     SG_CHECK_LAUNCH();
     return SG_OK;

@@ -19,6 +19,7 @@
 
 // d2 is compared bit for bit with the twin: the only fused steps are the two explicit fmaf
 #pragma clang fp contract(off)
+#include "pointcloud_core.h"   // d2 and the occupancy cell, shared with the twin
 
 namespace sg {
 
@@ -83,6 +84,7 @@ __global__ void __launch_bounds__(kCdBlock) chamfer_rows_kernel(const float* __r
                 for (int u = 0; u < 4; ++u) {
 #pragma unroll
                     for (int k = 0; k < kCdK / 2; ++k) {
+                        // sg_pc_d2 (pointcloud_core.h) on two points at once: the packed form has no scalar statement to share
                         const f32x2 dx = ax[k] - (f32x2)(bx[u]), dy = ay[k] - (f32x2)(by[u]), dz = az[k] - (f32x2)(bz[u]);
                         const f32x2 d = __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
                         mn[k] = __builtin_elementwise_min(mn[k], d);
@@ -147,8 +149,7 @@ __global__ void __launch_bounds__(kCdBlock) chamfer_nearest_kernel(const float* 
                 const int qi = (int)q0 + q + u;
 #pragma unroll
                 for (int k = 0; k < kNnK; ++k) {
-                    const float dx = ax[k] - bx[u], dy = ay[k] - by[u], dz = az[k] - bz[u];
-                    const float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+                    const float d = sg_pc_d2(ax[k], ay[k], az[k], bx[u], by[u], bz[u]);
                     const bool lt = d < best[k];     // increasing index, strict: the lowest index of a tie stays
                     best[k] = lt ? d : best[k];
                     arg[k] = lt ? qi : arg[k];
@@ -166,17 +167,12 @@ __global__ void __launch_bounds__(kCdBlock) chamfer_nearest_kernel(const float* 
     }
 }
 
-__device__ __forceinline__ int occupancy_axis(float x, float rm1) {
-    const float t = (x + 0.5f) * rm1;
-    return (int)fminf(fmaxf(floorf(t + 0.5f), 0.f), rm1);
-}
-
 __global__ void __launch_bounds__(256) occupancy_histogram_kernel(const float* __restrict__ pts, long n, int R,
                                                                   unsigned long long* __restrict__ hist) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float rm1 = (float)(R - 1);
-    const int ix = occupancy_axis(pts[i * 3], rm1), iy = occupancy_axis(pts[i * 3 + 1], rm1), iz = occupancy_axis(pts[i * 3 + 2], rm1);
+    const int ix = sg_pc_occupancy_axis(pts[i * 3], rm1), iy = sg_pc_occupancy_axis(pts[i * 3 + 1], rm1), iz = sg_pc_occupancy_axis(pts[i * 3 + 2], rm1);
     atomicAdd(&hist[((long)ix * R + iy) * R + iz], 1ull);
 }
 

@@ -70,7 +70,7 @@ __global__ void __launch_bounds__(256) rs_setup_kernel(const float* __restrict__
         for (int k = 0; k < 12; ++k) clip[t * 12 + k] = c[k];
     const long s = rs_shape_of(tri_offsets, S, t);
     if (s < 0) return;
-    if (ground_key) atomicMin(&ground_key[s], sg_rs_float_key(fminf(fminf(p[1], p[4]), p[7])));
+    if (ground_key) atomicMin(&ground_key[s], sg_float_key(fminf(fminf(p[1], p[4]), p[7])));
     if (f & SG_RS_DROPPED) atomicAdd(&dropped[s], 1);
     if (f) return;
     int* __restrict__ counts = tile_counts + s * (long)ntx * nty;
@@ -82,7 +82,7 @@ __global__ void __launch_bounds__(256) rs_ground_kernel(float* __restrict__ grou
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= S) return;
     const int k = ((const int*)ground)[i];
-    ground[i] = k == 0x7fffffff ? -1.0f : sg_rs_key_float(k);
+    ground[i] = k == 0x7fffffff ? -1.0f : sg_key_float(k);
 }
 
 // One workgroup of 1024: lane l owns the contiguous run [l * per, (l + 1) * per) of the n tiles.

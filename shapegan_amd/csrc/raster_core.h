@@ -5,13 +5,7 @@
 // __builtin_fmaf; the including file switches contraction off before the include.  Division and square root are IEEE (hipcc's
 // default for fp32, and g++'s).  Nothing here touches memory other than through the pointers it is given.
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define SG_RS_FN __host__ __device__ __forceinline__
-#else
-#define SG_RS_FN static inline
-#endif
+#include "core_fn.h"
 
 enum {
     SG_RS_SUB = 256,              // fixed-point units per sample: 8 sub-pixel bits
@@ -35,41 +29,34 @@ struct SgRasterParams {           // the parameter block rounded to fp32: layout
     float vp[16], lvp[16], ivp[16], cam[3], light[3], albedo[3], background[3];
 };
 
-SG_RS_FN void sg_rs_params_from_host(const double* p, SgRasterParams* q) {
+SG_CORE_FN void sg_rs_params_from_host(const double* p, SgRasterParams* q) {
     float* f = (float*)q;
     for (int i = 0; i < SG_RS_PARAMS; ++i) f[i] = (float)p[i];
 }
 
 // row i of M (row-major 4x4) times (x, y, z, 1) resp. (x, y, z, 0): the constant term first, then x, y, z
-SG_RS_FN float sg_rs_row_point(const float* M, int i, float x, float y, float z) {
+SG_CORE_FN float sg_rs_row_point(const float* M, int i, float x, float y, float z) {
     return __builtin_fmaf(M[i * 4 + 2], z, __builtin_fmaf(M[i * 4 + 1], y, __builtin_fmaf(M[i * 4], x, M[i * 4 + 3])));
 }
-SG_RS_FN float sg_rs_row_dir(const float* M, int i, float x, float y, float z) {
+SG_CORE_FN float sg_rs_row_dir(const float* M, int i, float x, float y, float z) {
     return __builtin_fmaf(M[i * 4 + 2], z, __builtin_fmaf(M[i * 4 + 1], y, M[i * 4] * x));
 }
-SG_RS_FN float sg_rs_dot(const float* a, const float* b) { return __builtin_fmaf(a[2], b[2], __builtin_fmaf(a[1], b[1], a[0] * b[0])); }
-SG_RS_FN void sg_rs_normalize(float* v) {
+SG_CORE_FN float sg_rs_dot(const float* a, const float* b) { return __builtin_fmaf(a[2], b[2], __builtin_fmaf(a[1], b[1], a[0] * b[0])); }
+SG_CORE_FN void sg_rs_normalize(float* v) {
     const float len = __builtin_sqrtf(sg_rs_dot(v, v));
     v[0] = v[0] / len;
     v[1] = v[1] / len;
     v[2] = v[2] / len;
 }
-SG_RS_FN float sg_rs_clamp01(float v) { return __builtin_fminf(__builtin_fmaxf(v, 0.f), 1.f); }      // NaN -> 0
+SG_CORE_FN float sg_rs_clamp01(float v) { return __builtin_fminf(__builtin_fmaxf(v, 0.f), 1.f); }      // NaN -> 0
 
-// the order-preserving integer image of a float (signed compare) and back
-SG_RS_FN int sg_rs_float_key(float f) {
-    const int b = __builtin_bit_cast(int, f);
-    return b >= 0 ? b : b ^ 0x7fffffff;
-}
-SG_RS_FN float sg_rs_key_float(int k) { return __builtin_bit_cast(float, k >= 0 ? k : k ^ 0x7fffffff); }
-
-SG_RS_FN int64_t sg_rs_area2(const SgRasterRec& r) {
+SG_CORE_FN int64_t sg_rs_area2(const SgRasterRec& r) {
     return (int64_t)(r.x[1] - r.x[0]) * (r.y[2] - r.y[0]) - (int64_t)(r.x[2] - r.x[0]) * (r.y[1] - r.y[0]);
 }
 
 // Setup of one triangle: p = its nine coordinates, M = the view's VP in fp32.  Returns the flags; a dropped triangle gets a record of
 // zeros with an empty sample box.  clip (may be NULL) receives the twelve clip coordinates.
-SG_RS_FN int sg_rs_setup(const float* p, const float* M, int W, int H, int cull_back, float near_w, SgRasterRec* r, float* clip) {
+SG_CORE_FN int sg_rs_setup(const float* p, const float* M, int W, int H, int cull_back, float near_w, SgRasterRec* r, float* clip) {
     float c[3][4];
     for (int k = 0; k < 3; ++k)
         for (int i = 0; i < 4; ++i) {
@@ -136,7 +123,7 @@ SG_RS_FN int sg_rs_setup(const float* p, const float* M, int W, int H, int cull_
 
 // Coverage of the sample (px, py) by the triangle: e[i] = the edge function opposite corner i, signed so that the inside is
 // positive, their sum = |2 area|.  A sample exactly on an edge belongs to the triangle only if that edge is a top or a left one.
-SG_RS_FN bool sg_rs_cover(const int* x, const int* y, int px, int py, int64_t* e, int64_t* area2) {
+SG_CORE_FN bool sg_rs_cover(const int* x, const int* y, int px, int py, int64_t* e, int64_t* area2) {
     const int sx = px * SG_RS_SUB + SG_RS_HALF, sy = py * SG_RS_SUB + SG_RS_HALF;
     const int64_t a2 = (int64_t)(x[1] - x[0]) * (y[2] - y[0]) - (int64_t)(x[2] - x[0]) * (y[1] - y[0]);
     const int s = a2 < 0 ? -1 : 1;
@@ -154,23 +141,23 @@ SG_RS_FN bool sg_rs_cover(const int* x, const int* y, int px, int py, int64_t* e
 }
 
 // NDC depth at a covered sample: screen-space barycentrics l1 = e1 * inv, l2 = e2 * inv (inv = 1 / (float)|2 area|)
-SG_RS_FN float sg_rs_depth(const int64_t* e, float inv, float z0, float dz1, float dz2) {
+SG_CORE_FN float sg_rs_depth(const int64_t* e, float inv, float z0, float dz1, float dz2) {
     const float l1 = (float)e[1] * inv, l2 = (float)e[2] * inv;
     return __builtin_fmaf(l2, dz2, __builtin_fmaf(l1, dz1, z0));
 }
 
 // ---- shading ----------------------------------------------------------------------------------------------------------------------
 // one nearest-texel comparison of the shadow map (rows run down, texture v runs up), coordinates clamped to the edge
-SG_RS_FN float sg_rs_shadow_tap(const float* smap, int N, int ix, int iy, float ref) {
+SG_CORE_FN float sg_rs_shadow_tap(const float* smap, int N, int ix, int iy, float ref) {
     ix = ix < 0 ? 0 : (ix > N - 1 ? N - 1 : ix);
     iy = iy < 0 ? 0 : (iy > N - 1 ? N - 1 : iy);
     return ref > smap[(long)(N - 1 - iy) * N + ix] ? 1.f : 0.f;
 }
-SG_RS_FN int sg_rs_texel(float t, int N) {      // floor(t) as an int, kept within [-1, N] (NaN -> -1)
+SG_CORE_FN int sg_rs_texel(float t, int N) {      // floor(t) as an int, kept within [-1, N] (NaN -> -1)
     return (int)__builtin_fminf(__builtin_fmaxf(__builtin_floorf(t), -1.f), (float)N);
 }
 // sp = lightVP * (p, 1); d = clamp(n . L, 0, 1)
-SG_RS_FN float sg_rs_shadow(const float* sp, float d, const float* smap, int N) {
+SG_CORE_FN float sg_rs_shadow(const float* sp, float d, const float* smap, int N) {
     const float cx = __builtin_fmaf(sp[0] / sp[3], 0.5f, 0.5f), cy = __builtin_fmaf(sp[1] / sp[3], 0.5f, 0.5f),
                 cz = __builtin_fmaf(sp[2] / sp[3], 0.5f, 0.5f);
     if (!(cz <= 1.0f)) return 0.f;
@@ -191,11 +178,11 @@ SG_RS_FN float sg_rs_shadow(const float* sp, float d, const float* smap, int N) 
     return sg_rs_clamp01(sum / 9.0f);
 }
 
-SG_RS_FN unsigned char sg_rs_byte(float c) { return (unsigned char)(int)__builtin_floorf(__builtin_fmaf(sg_rs_clamp01(c), 255.f, 0.5f)); }
+SG_CORE_FN unsigned char sg_rs_byte(float c) { return (unsigned char)(int)__builtin_floorf(__builtin_fmaf(sg_rs_clamp01(c), 255.f, 0.5f)); }
 
 // The colour of one sample.  id / depth: the camera pass's result at the sample; recs: the camera pass's records; positions / normals:
 // the packed soup (normals may be NULL); smap: this shape's shadow map [N][N]; ground: this shape's ground level.
-SG_RS_FN void sg_rs_shade(int px, int py, int W, int H, int id, float depth, long T, const SgRasterRec* recs, const float* positions,
+SG_CORE_FN void sg_rs_shade(int px, int py, int W, int H, int id, float depth, long T, const SgRasterRec* recs, const float* positions,
                           const float* normals, const float* smap, int N, float ground, const SgRasterParams& P, unsigned char* rgb) {
     // the floor: the eye ray through the sample centre against the plane y = ground; it wins where it is nearer than the mesh
     if (P.cam[1] > ground) {

@@ -17,11 +17,17 @@
 #include "sdfnet_tile.h"
 #include "../../include/shapegan_hip.h"
 
+// positions, directions and pixels are compared with the twin: no contraction of a * b + c into one rounding.  The pragma stays BELOW
+// the sdfnet_tile.h include: above it, it would change the MLP arithmetic of raymarch_step_kernel.
+#pragma clang fp contract(off)
+#include "raymarch_core.h"  // the per-ray and per-pixel arithmetic, shared with the twin
+
 namespace sg {
 
 constexpr int kMarchTile = 64;
 constexpr int kMaxSegments = 256;
 constexpr int kScanBlock = 256;
+static_assert(kScanBlock == 256, "sg_block_exclusive_256 scans four waves");
 
 struct MarchArgs {
     float* pos;               // [nrays][3]
@@ -49,7 +55,6 @@ struct MarchIo {
     __device__ __forceinline__ bool ragged(const SdfFwdArgs&) const { return true; }
     __device__ __forceinline__ int shape(const SdfFwdArgs&, long gp) const { return rseg[gp - p0] % m->nshapes; }
     __device__ void store(const SdfFwdArgs& a, long gp, float v) const {
-#pragma clang fp contract(off)
         // raymarching.py:106-117 (:47-55): sdf = clamp(tanh(v) + offset, -c, c); points += dir * sdf; hit / miss
         const int lane = threadIdx.x;
         const int ray = rid[lane], seg = rseg[lane];
@@ -59,16 +64,9 @@ struct MarchIo {
             s = fminf(fmaxf(s, -m->clampv), m->clampv);
             const long di = m->dir_period > 0 ? ray % m->dir_period : ray;
             float* p = m->pos + (long)ray * 3;
-            const float x = p[0] + m->dir[di * 3] * s, y = p[1] + m->dir[di * 3 + 1] * s, z = p[2] + m->dir[di * 3 + 2] * s;
-            p[0] = x;
-            p[1] = y;
-            p[2] = z;
-            if (s > 0.f && s < m->threshold) {
-                m->status[ray] = 1;
-            } else {
-                const float r = seg < m->nshapes ? m->radius0 : m->radius1;
-                surv = !(m->shadow ? y > r : sqrtf(x * x + y * y + z * z) > r);
-            }
+            sg_rm_move(p, m->dir + di * 3, s);
+            if (sg_rm_hit(s, m->threshold)) m->status[ray] = 1;
+            else surv = !sg_rm_left(p, seg < m->nshapes ? m->radius0 : m->radius1, m->shadow);
         }
         // append the survivors: per distinct segment in the wave one atomic (ballot + mbcnt)
         int* next = m->active + ((m->iter + 1) & 1) * m->nrays;
@@ -152,40 +150,21 @@ __global__ void __launch_bounds__(256) raymarch_finish_kernel(MarchArgs m) {
 
 // ---- camera rays (raymarching.py:65-102) ----
 struct Camera {
-    double pos[3], right[3], up[3], fwd[3], focal, c;   // c = |pos|^2 - radius^2
+    double v[13], c;   // position, right, up, forward, focal length; c = |position|^2 - radius^2
     float posf[3];
 };
 
 __global__ void __launch_bounds__(256) raymarch_rays_kernel(Camera cam, int W, long M, int S, float* __restrict__ dir,
                                                             float* __restrict__ pos, unsigned char* __restrict__ status,
                                                             int* __restrict__ active, int* __restrict__ counts) {
-#pragma clang fp contract(off)
     const long pix = (long)blockIdx.x * 256 + threadIdx.x;
     bool inside = false;
     float p[3] = {cam.posf[0], cam.posf[1], cam.posf[2]};
     if (pix < M) {
-        // np.linspace(-1, 1, W): i * (2 / (W - 1)) - 1, the last one exactly 1; meshgrid: x along a row, y down the rows
-        const long row = pix / W, col = pix - row * W;
-        const double step = W > 1 ? 2.0 / (double)(W - 1) : 0.0;
-        const double sx = col == W - 1 && W > 1 ? 1.0 : (double)col * step + -1.0;
-        const double sy = row == W - 1 && W > 1 ? 1.0 : (double)row * step + -1.0;
         float d[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) d[c] = (float)(sx * cam.right[c] + sy * cam.up[c] + cam.focal * cam.fwd[c]);
-        const float n = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) d[c] = d[c] / n;
+        inside = sg_rm_camera_ray(cam.v, cam.c, W, pix, d, p);
 #pragma unroll
         for (int c = 0; c < 3; ++c) dir[pix * 3 + c] = d[c];
-        // entry into the bounding sphere; rays that miss it are never marched (raymarching.py:91-97)
-        const float b = (p[0] * d[0] + p[1] * d[1] + p[2] * d[2]) * 2.f;
-        const double disc = (double)(b * b) - 4.0 * cam.c;
-        if (disc >= 0.0) {
-            const double t = (-(double)b - sqrt(disc)) / 2.0;
-            inside = true;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) p[c] = (float)((double)p[c] + (double)d[c] * t);
-        }
     }
     const unsigned long long mm = __ballot(inside);
     const int lane = threadIdx.x & 63;
@@ -220,45 +199,11 @@ struct Scene {
     const int64_t* hit_off;  // [S + 1]
 };
 
-__device__ __forceinline__ int float_key(float f) {   // monotonic int image of a float (min of keys = key of min)
-    const int b = __float_as_int(f);
-    return b ^ ((b >> 31) & 0x7fffffff);
-}
-__device__ __forceinline__ float key_float(int k) { return __int_as_float(k ^ ((k >> 31) & 0x7fffffff)); }
-
-// the ground point of a non-hit pixel looking down: its ray meets y = ground within |xz| < 3 (raymarching.py:159-163)
+// the ground point of a non-hit pixel looking down, if image s has a ground plane at all (without a hit the image stays white)
 __device__ __forceinline__ bool ground_point(const Scene& sc, int s, long pix, float q[3]) {
-#pragma clang fp contract(off)
-    if (sc.hit_off[s + 1] == sc.hit_off[s]) return false;   // no hit: no ground plane (the image stays white)
-    const float* d = sc.dir + pix * 3;
-    if (!(d[1] < 0.f) || sc.status[(long)s * sc.M + pix]) return false;
-    const float* p = sc.pos + ((long)s * sc.M + pix) * 3;
-    const float t = (p[1] - sc.ground[s]) / d[1];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) q[c] = p[c] - d[c] * t;
-    return sqrtf(q[0] * q[0] + q[2] * q[2]) < 3.f;
-}
-
-__device__ __forceinline__ int block_exclusive(int x, int* lds_waves, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = x;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int y = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += y;
-    }
-    if (lane == 63) lds_waves[wave] = incl;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kScanBlock / 64; ++w) {
-        const int t = lds_waves[w];
-        before += w < wave ? t : 0;
-        total += t;
-    }
-    __syncthreads();
-    return before + incl - x;
+    if (sc.hit_off[s + 1] == sc.hit_off[s]) return false;
+    const long r = (long)s * sc.M + pix;
+    return sg_rm_ground_point(sc.status[r], sc.pos + r * 3, sc.dir + pix * 3, sc.ground[s], q);
 }
 
 // pass 0: vertical cutoff (raymarching.py:126-128), hits per block and the block's minimum hit y; pass 1: ground rays per block
@@ -277,7 +222,7 @@ __global__ void __launch_bounds__(kScanBlock) raymarch_count_kernel(Scene sc, in
                 if (sc.cutoff && (y > sc.vcut || y < -sc.vcut)) sc.status[r] = 0;
                 else {
                     x = 1;
-                    key = float_key(y);
+                    key = sg_float_key(y);
                 }
             }
         } else {
@@ -286,7 +231,7 @@ __global__ void __launch_bounds__(kScanBlock) raymarch_count_kernel(Scene sc, in
         }
     }
     int tot;
-    block_exclusive(x, lds, tot);
+    sg_block_exclusive_256(x, lds, tot);
     if (pass == 0) {
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) key = min(key, __shfl_xor(key, off, 64));
@@ -351,7 +296,7 @@ __global__ void __launch_bounds__(1024) raymarch_scan_kernel(const int* __restri
     if (block_min) {
         __syncthreads();
         // (an image without hits keeps the initial key, a NaN pattern: the minimum over nothing is +inf)
-        for (int s = threadIdx.x; s < S; s += 1024) ground[s] = smin[s] == 0x7fffffff ? INFINITY : key_float(smin[s]);
+        for (int s = threadIdx.x; s < S; s += 1024) ground[s] = smin[s] == 0x7fffffff ? INFINITY : sg_key_float(smin[s]);
     }
 }
 
@@ -370,22 +315,6 @@ struct Emit {
     int64_t* sseg;              // [2S + 1]
 };
 
-// shadow ray towards the light from q (raymarching.py:37-42): direction in float64, cast; start q + 0.1 d
-__device__ __forceinline__ void shadow_ray(const Emit& e, const float q[3], long j) {
-#pragma clang fp contract(off)
-    double d[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) d[c] = e.light[c] - (double)q[c];
-    const double n = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float df = (float)(d[c] / n);
-        e.sdir[j * 3 + c] = df;
-        e.spos[j * 3 + c] = q[c] + df * 0.1f;
-    }
-    e.sactive[j] = (int)j;
-}
-
 __global__ void __launch_bounds__(kScanBlock) raymarch_emit_kernel(Scene sc, Emit e) {
     __shared__ int lds[kScanBlock / 64];
     const int s = blockIdx.y;
@@ -400,8 +329,8 @@ __global__ void __launch_bounds__(kScanBlock) raymarch_emit_kernel(Scene sc, Emi
         if (!hit) gnd = ground_point(sc, s, pix, q);
     }
     int tot;
-    const int hr = block_exclusive(hit ? 1 : 0, lds, tot);
-    const int gr = block_exclusive(gnd ? 1 : 0, lds, tot);
+    const int hr = sg_block_exclusive_256(hit ? 1 : 0, lds, tot);
+    const int gr = sg_block_exclusive_256(gnd ? 1 : 0, lds, tot);
     if (pix < sc.M) {
         if (hit) {
             const long h = e.hit_boff[bi] + hr;
@@ -409,11 +338,13 @@ __global__ void __launch_bounds__(kScanBlock) raymarch_emit_kernel(Scene sc, Emi
             for (int c = 0; c < 3; ++c) q[c] = e.hit_pos[h * 3 + c] = sc.pos[r * 3 + c];
             e.hit_sid[h] = s;
             e.slot[r] = (int)h;
-            shadow_ray(e, q, h);
+            sg_rm_shadow_ray(e.light, q, e.sdir + h * 3, e.spos + h * 3);
+            e.sactive[h] = (int)h;
         } else if (gnd) {
             const long g = e.gnd_boff[bi] + gr;
             e.slot[r] = -2 - (int)g;
-            shadow_ray(e, q, H + g);
+            sg_rm_shadow_ray(e.light, q, e.sdir + (H + g) * 3, e.spos + (H + g) * 3);
+            e.sactive[H + g] = (int)(H + g);
         } else {
             e.slot[r] = -1;
         }
@@ -433,7 +364,7 @@ __global__ void __launch_bounds__(kScanBlock) raymarch_emit_kernel(Scene sc, Emi
     }
 }
 
-// ---- shading (raymarching.py:130-175): float64 like the reference's numpy, uint8 by truncation ----
+// ---- shading ----
 struct Shade {
     const int* slot;
     const float* hit_pos;
@@ -447,45 +378,9 @@ struct Shade {
 };
 
 __global__ void __launch_bounds__(256) raymarch_shade_kernel(Shade sh) {
-#pragma clang fp contract(off)
     const long r = (long)blockIdx.x * 256 + threadIdx.x;
     if (r >= (long)sh.S * sh.M) return;
-    const long pix = r % sh.M;
-    const int k = sh.slot[r];
-    double px[3] = {1.0, 1.0, 1.0};
-    if (k >= 0) {
-        const float* g = sh.grad + (long)k * 3;
-        const float gn = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
-        const float nf[3] = {g[0] / gn, g[1] / gn, g[2] / gn};
-        const float* d = sh.dir + pix * 3;
-        const double seen = (double)(1.f - (float)sh.shadow[k]);
-        double ld[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) ld[c] = sh.light[c] - (double)sh.hit_pos[(long)k * 3 + c];
-        const double ln = sqrt(ld[0] * ld[0] + ld[1] * ld[1] + ld[2] * ld[2]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) ld[c] = ld[c] / ln;
-        const double dn = ld[0] * nf[0] + ld[1] * nf[1] + ld[2] * nf[2];
-        const double diffuse = fmin(fmax(dn, 0.0), 1.0) * seen;
-        double rf[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) rf[c] = ld[c] - dn * (double)nf[c] * 2.0;
-        const double rn = sqrt(rf[0] * rf[0] + rf[1] * rf[1] + rf[2] * rf[2]);
-        double spec = (rf[0] / rn) * d[0] + (rf[1] / rn) * d[1] + (rf[2] / rn) * d[2];
-        spec = fmin(fmax(spec, 0.0), 1.0);
-        spec = pow(spec, 20.0) * seen;
-        float rim = -(nf[0] * d[0] + nf[1] * d[1] + nf[2] * d[2]);
-        rim = 1.f - fminf(fmaxf(rim, 0.f), 1.f);
-        rim = rim * rim * rim * rim * 0.3f;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) px[c] = fmin(fmax(sh.color[c] * (diffuse * 0.5 + 0.5) + (spec * 0.3 + (double)rim), 0.0), 1.0);
-    } else if (k <= -2) {
-        const double dk = (double)(0.35f * (float)sh.shadow[sh.H + (-2 - k)]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) px[c] -= dk;
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) sh.image[r * 3 + c] = (unsigned char)(px[c] * 255.0);
+    sg_rm_shade(sh.slot[r], sh.dir + (r % sh.M) * 3, sh.hit_pos, sh.grad, sh.shadow, sh.H, sh.light, sh.color, sh.image + r * 3);
 }
 
 static MarchArgs march_args(float* pos, const float* dir, long dir_period, unsigned char* status, int* active, long nrays,
@@ -517,14 +412,8 @@ int sg_raymarch_rays(const double* camera, int width, long nshapes, double radiu
     const long M = (long)width * width;
     SG_CHECK_ARG(nshapes * M < (1L << 31));
     Camera cam;
-    for (int c = 0; c < 3; ++c) {
-        cam.pos[c] = camera[c];
-        cam.right[c] = camera[3 + c];
-        cam.up[c] = camera[6 + c];
-        cam.fwd[c] = camera[9 + c];
-        cam.posf[c] = (float)camera[c];
-    }
-    cam.focal = camera[12];
+    for (int i = 0; i < 13; ++i) cam.v[i] = camera[i];
+    for (int c = 0; c < 3; ++c) cam.posf[c] = (float)camera[c];
     cam.c = (camera[0] * camera[0] + camera[1] * camera[1] + camera[2] * camera[2]) - radius * radius;
     hipLaunchKernelGGL(raymarch_rays_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, stream, cam, width, M, (int)nshapes, dir,
                        pos, status, active, counts);

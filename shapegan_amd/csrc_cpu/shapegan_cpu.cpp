@@ -4,9 +4,12 @@
 // is `train_autoencoder.py classic ... on CPU (plumbing, no GPU)`.  Every function here is `sg_<name>_cpu` with the argument
 // list of `sg_<name>` (the stream and workspace arguments are accepted and ignored; pointers are host pointers).  It is a
 // SEPARATE implementation written against the header's contracts — straightforward loops with OpenMP over the outer index,
-// no tiling heroics: correctness plumbing, not a performance path — and it shares no code with oracle/ (test infrastructure)
-// or with the HIP kernels.  The Python shells pick it only for tensors that live on the CPU (shapegan_amd/lib.py); GPU
-// tensors never come here and there is no fallback in either direction.
+// no tiling heroics: correctness plumbing, not a performance path — and it shares no code with oracle/ (test infrastructure).
+// With the HIP kernels it shares the per-element arithmetic of the areas that promise equal bits (csrc/*_core.h, mc_tables.h): one
+// statement of each formula, the loops and summations around them written here.  Independence of those areas comes from the float64
+// references of the tests (tests/geometry_reference.py, evaluation_reference.py, emd_reference.py), written from the header alone.
+// The Python shells pick the twin only for tensors that live on the CPU (shapegan_amd/lib.py); GPU tensors never come here and
+// there is no fallback in either direction.
 //
 // Opaque-buffer contracts it keeps compatible with the sizes the HIP library reports (host-side helpers, callable without a
 // GPU): sg_sdfnet_packed_floats (this twin stores the plain weights at the front of the buffer), sg_sdfnet_bwd_blocks
@@ -19,12 +22,10 @@
 #include <algorithm>
 #include <vector>
 
-#include "../csrc/mc_tables.h"
+#include "../../include/shapegan_hip.h"   // the constants of the contract (SG_SDFNET_PARTIAL_ROW, SG_EMD_*, ...)
 
 typedef void* hipStream_t_;
-#define SG_OK 0
-#define SG_SDFNET_PARTIAL_ROW (14 * 256 + 32)   // include/shapegan_hip.h (the twin does not include the HIP header)
-#define SG_SDFGEN_PARTIAL_ROW (SG_SDFNET_PARTIAL_ROW + 14 * 256)
+#define SG_OK 0          // csrc/common.h (the header names the codes only in its comments)
 #define SG_ERR_ARG (-1)
 enum { ACT_NONE = 0, ACT_LEAKY = 1, ACT_RELU = 2, ACT_TANH = 3, ACT_SIGMOID = 4 };
 
@@ -1651,95 +1652,41 @@ int sg_scatter_max_gather_cpu(const float* x, const int* arg, float* out, long N
     return SG_OK;
 }
 
+}  // extern "C"
+
+// ---- the areas that promise the bits of the HIP kernels: K12, sphere tracing, K13, K15 ---------------------------------------------
+// Their per-element arithmetic is csrc/*_core.h, the files the HIP kernels include: one statement of every formula.  What is written
+// here is the part the headers leave to each library: the loops, the lists and the summations.
+#pragma GCC push_options
+#pragma GCC optimize("fp-contract=off")
+#include "../csrc/mesh_core.h"
+#include "../csrc/raymarch_core.h"
+#include "../csrc/pointcloud_core.h"
+
+extern "C" {
+
 // ---- K12: marching cubes and surface sampling (csrc/mesh.hip) ------------------------------------------------------------------
 // The same cells in the same order as the kernels: the corners of the (virtually padded) grid in row-major order, each owning the
 // crossing edges at its minimum corner (axes 0, 1, 2) and, where it exists, the cube with that minimum corner.
-struct McGridCpu {
-    const float* g;
-    int R0, R1, R2, P0, P1, P2, pad;
-    float pad_value, level;
-    float value(int a, int b, int c) const {
-        if (pad) {
-            a -= 1;
-            b -= 1;
-            c -= 1;
-            if ((unsigned)a >= (unsigned)R0 || (unsigned)b >= (unsigned)R1 || (unsigned)c >= (unsigned)R2) return pad_value;
-        }
-        return g[((long)a * R1 + b) * R2 + c];
-    }
-    // case bits of the cell at (a, b, c) (corners outside the grid read as pad_value), owned-edge crossing mask, cube or -1
-    void classify(int a, int b, int c, float v[8], int& mask, int& cube) const {
-        int cs = 0;
-        for (int n = 0; n < 8; ++n) {
-            const int x = a + ((n >> 2) & 1), y = b + ((n >> 1) & 1), z = c + (n & 1);
-            v[n] = (x < P0 && y < P1 && z < P2) ? value(x, y, z) : pad_value;
-            cs |= (v[n] < level ? 1 : 0) << n;
-        }
-        const int in0 = cs & 1;
-        mask = 0;
-        if (a + 1 < P0 && in0 != ((cs >> 4) & 1)) mask |= 1;
-        if (b + 1 < P1 && in0 != ((cs >> 2) & 1)) mask |= 2;
-        if (c + 1 < P2 && in0 != ((cs >> 1) & 1)) mask |= 4;
-        cube = (a + 1 < P0 && b + 1 < P1 && c + 1 < P2) ? cs : -1;
-    }
-    float grad(int a, int b, int c, int axis, float spacing) const {
-        const int p = axis == 0 ? a : axis == 1 ? b : c;
-        const int P = axis == 0 ? P0 : axis == 1 ? P1 : P2;
-        const int lo = p > 0 ? p - 1 : p, hi = p < P - 1 ? p + 1 : p;
-        if (hi == lo) return 0.f;
-        float vl, vh;
-        if (axis == 0) {
-            vl = value(lo, b, c);
-            vh = value(hi, b, c);
-        } else if (axis == 1) {
-            vl = value(a, lo, c);
-            vh = value(a, hi, c);
-        } else {
-            vl = value(a, b, lo);
-            vh = value(a, b, hi);
-        }
-        return (vh - vl) / ((float)(hi - lo) * spacing);
-    }
-};
-
-static bool mc_setup_cpu(McGridCpu& m, const float* grids, long S, int R0, int R1, int R2, float level, int pad, float pad_value,
-                         long& cells) {
-    if (!grids || S <= 0 || R0 <= 0 || R1 <= 0 || R2 <= 0 || (pad != 0 && pad != 1)) return false;
-    m.g = grids;
-    m.R0 = R0;
-    m.R1 = R1;
-    m.R2 = R2;
-    m.P0 = R0 + 2 * pad;
-    m.P1 = R1 + 2 * pad;
-    m.P2 = R2 + 2 * pad;
-    m.pad = pad;
-    m.pad_value = pad_value;
-    m.level = level;
-    cells = (long)m.P0 * m.P1 * m.P2;
-    const long lim = 2147483647L / 24;     // the index limit of include/shapegan_hip.h
-    return cells <= lim && S <= lim / cells;
-}
-
 int sg_mc_count_cpu(const float* grids, long S, int R0, int R1, int R2, float level, int pad, float pad_value, int64_t* vert_offsets,
                     int64_t* tri_offsets, void*, size_t, void*) {
-    McGridCpu m;
+    SgMcGrid m;
     long cells = 0;
-    CPU_CHECK(mc_setup_cpu(m, grids, S, R0, R1, R2, level, pad, pad_value, cells));
+    CPU_CHECK(grids && sg_mc_grid(m, S, R0, R1, R2, level, pad, pad_value, cells));
     CPU_CHECK(vert_offsets && tri_offsets);
     std::vector<int64_t> nv(S), nt(S);
 #pragma omp parallel for schedule(dynamic)
     for (long s = 0; s < S; ++s) {
-        McGridCpu ms = m;
-        ms.g = grids + s * (long)R0 * R1 * R2;
+        const float* g = grids + s * (long)R0 * R1 * R2;
         int64_t v = 0, t = 0;
         float val[8];
         for (int a = 0; a < m.P0; ++a)
             for (int b = 0; b < m.P1; ++b)
                 for (int c = 0; c < m.P2; ++c) {
-                    int mask, cube;
-                    ms.classify(a, b, c, val, mask, cube);
-                    v += __builtin_popcount(mask);
-                    t += cube >= 0 ? sg_mc_tri_count[cube] : 0;
+                    sg_mc_corners(m, g, a, b, c, val);
+                    const SgMcCell r = sg_mc_classify(m, val, a, b, c);
+                    v += r.nv;
+                    t += r.nt;
                 }
         nv[s] = v;
         nt[s] = t;
@@ -1755,17 +1702,16 @@ int sg_mc_count_cpu(const float* grids, long S, int R0, int R1, int R2, float le
 int sg_mc_emit_cpu(const float* grids, long S, int R0, int R1, int R2, float level, int pad, float pad_value, float sx, float sy,
                    float sz, float ox, float oy, float oz, const int64_t* vert_offsets, const int64_t* tri_offsets, float* vertices,
                    float* normals, int64_t* faces, long max_verts, long max_tris, void*, size_t, void*) {
-    McGridCpu m;
+    SgMcGrid m;
     long cells = 0;
-    CPU_CHECK(mc_setup_cpu(m, grids, S, R0, R1, R2, level, pad, pad_value, cells));
+    CPU_CHECK(grids && sg_mc_grid(m, S, R0, R1, R2, level, pad, pad_value, cells));
     CPU_CHECK(vert_offsets && tri_offsets && max_verts >= 0 && max_tris >= 0);
     CPU_CHECK((max_verts == 0 || (vertices && normals)) && (max_tris == 0 || faces));
     CPU_CHECK(vert_offsets[S] <= max_verts && tri_offsets[S] <= max_tris);
     const float sp[3] = {sx, sy, sz}, org[3] = {ox, oy, oz};
 #pragma omp parallel for schedule(dynamic)
     for (long s = 0; s < S; ++s) {
-        McGridCpu ms = m;
-        ms.g = grids + s * (long)R0 * R1 * R2;
+        const float* g = grids + s * (long)R0 * R1 * R2;
         std::vector<int> first(cells), owned(cells);      // per cell: first vertex (local to the shape), crossing mask
         long vo = 0, to = 0;
         float v[8];
@@ -1773,30 +1719,17 @@ int sg_mc_emit_cpu(const float* grids, long S, int R0, int R1, int R2, float lev
         for (int a = 0; a < m.P0; ++a)
             for (int b = 0; b < m.P1; ++b)
                 for (int c = 0; c < m.P2; ++c, ++cell) {
-                    int mask, cube;
-                    ms.classify(a, b, c, v, mask, cube);
+                    sg_mc_corners(m, g, a, b, c, v);
+                    const int mask = sg_mc_classify(m, v, a, b, c).mask;
                     first[cell] = (int)vo;
                     owned[cell] = mask;
                     if (!mask) continue;
-                    const int idx[3] = {a, b, c};
                     float g0[3];
-                    for (int k = 0; k < 3; ++k) g0[k] = ms.grad(a, b, c, k, sp[k]);
+                    for (int k = 0; k < 3; ++k) g0[k] = sg_mc_grad(m, g, a, b, c, k, sp[k]);
                     for (int axis = 0; axis < 3; ++axis) {
                         if (!((mask >> axis) & 1)) continue;
-                        const float va = v[0], vb = v[axis == 0 ? 4 : axis == 1 ? 2 : 1];
-                        const float t = (level - va) / (vb - va);
-                        const int a1 = a + (axis == 0), b1 = b + (axis == 1), c1 = c + (axis == 2);
-                        float n[3];
-                        for (int k = 0; k < 3; ++k) {
-                            const float g1 = ms.grad(a1, b1, c1, k, sp[k]);
-                            n[k] = g0[k] + t * (g1 - g0[k]);
-                        }
-                        const float len = sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
                         const long out = vert_offsets[s] + vo;
-                        for (int k = 0; k < 3; ++k) {
-                            vertices[out * 3 + k] = ((float)idx[k] + (k == axis ? t : 0.f)) * sp[k] + org[k];
-                            normals[out * 3 + k] = len > 0.f ? n[k] / len : 0.f;
-                        }
+                        sg_mc_vertex(m, g, sp, org, a, b, c, v, g0, axis, vertices + out * 3, normals + out * 3);
                         ++vo;
                     }
                 }
@@ -1805,20 +1738,18 @@ int sg_mc_emit_cpu(const float* grids, long S, int R0, int R1, int R2, float lev
         for (int a = 0; a < m.P0; ++a)
             for (int b = 0; b < m.P1; ++b)
                 for (int c = 0; c < m.P2; ++c, ++cell) {
-                    int mask, cube;
-                    ms.classify(a, b, c, v, mask, cube);
-                    if (cube < 0) continue;
-                    for (int j = 0; j < sg_mc_tri_count[cube]; ++j) {
+                    sg_mc_corners(m, g, a, b, c, v);
+                    const SgMcCell r = sg_mc_classify(m, v, a, b, c);
+                    for (int j = 0; j < r.nt; ++j) {
                         const long f = tri_offsets[s] + to + j;
                         for (int k = 0; k < 3; ++k) {
-                            const int e = sg_mc_tri_edges[cube][3 * j + k];
-                            const int axis = e >> 2, u = (e >> 1) & 1, w = e & 1;
-                            const int oa = axis == 0 ? 0 : u, ob = axis == 1 ? 0 : (axis == 0 ? u : w), oc = axis == 2 ? 0 : w;
+                            int oa, ob, oc;
+                            const int axis = sg_mc_edge_owner(sg_mc_tri_edges[r.cube][3 * j + k], oa, ob, oc);
                             const long owner = (long)(a + oa) * plane + (long)(b + ob) * m.P2 + (c + oc);
-                            faces[f * 3 + k] = first[owner] + __builtin_popcount(owned[owner] & ((1 << axis) - 1));
+                            faces[f * 3 + k] = first[owner] + sg_mc_rank(owned[owner], axis);
                         }
                     }
-                    to += sg_mc_tri_count[cube];
+                    to += r.nt;
                 }
     }
     return SG_OK;
@@ -1840,13 +1771,7 @@ int sg_mesh_sample_cpu(const float* vertices, const int64_t* faces, const int64_
         std::vector<double> cdf(f1 - f0);
         double run = 0.0;
         for (long f = f0; f < f1; ++f) {
-            const float* p0 = vertices + (vb + faces[f * 3]) * 3;
-            const float* p1 = vertices + (vb + faces[f * 3 + 1]) * 3;
-            const float* p2 = vertices + (vb + faces[f * 3 + 2]) * 3;
-            const double ax = (double)p1[0] - (double)p0[0], ay = (double)p1[1] - (double)p0[1], az = (double)p1[2] - (double)p0[2];
-            const double bx = (double)p2[0] - (double)p0[0], by = (double)p2[1] - (double)p0[1], bz = (double)p2[2] - (double)p0[2];
-            const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
-            run += sqrt(cx * cx + cy * cy + cz * cz);
+            run += sg_mesh_area2(vertices + (vb + faces[f * 3]) * 3, vertices + (vb + faces[f * 3 + 1]) * 3, vertices + (vb + faces[f * 3 + 2]) * 3);
             cdf[f - f0] = run;
         }
         for (long q = 0; q < P; ++q) {
@@ -1855,15 +1780,8 @@ int sg_mesh_sample_cpu(const float* vertices, const int64_t* faces, const int64_
             const double x = (double)u0 * cdf.back();
             const long k = std::min((long)(std::lower_bound(cdf.begin(), cdf.end(), x) - cdf.begin()), f1 - f0 - 1);
             const long f = f0 + k;
-            const float* p0 = vertices + (vb + faces[f * 3]) * 3;
-            const float* p1 = vertices + (vb + faces[f * 3 + 1]) * 3;
-            const float* p2 = vertices + (vb + faces[f * 3 + 2]) * 3;
-            float p = u1, r = u2;
-            if (p + r > 1.f) {
-                p = 1.f - p;
-                r = 1.f - r;
-            }
-            for (int c = 0; c < 3; ++c) out[i * 3 + c] = p0[c] + (p * (p1[c] - p0[c]) + r * (p2[c] - p0[c]));
+            sg_mesh_point(vertices + (vb + faces[f * 3]) * 3, vertices + (vb + faces[f * 3 + 1]) * 3, vertices + (vb + faces[f * 3 + 2]) * 3, u1, u2,
+                          out + i * 3);
         }
     }
     return SG_OK;
@@ -1872,8 +1790,6 @@ int sg_mesh_sample_cpu(const float* vertices, const int64_t* faces, const int64_
 // ---- sphere tracing (header: sg_raymarch_*; rendering/raymarching.py:render_image, get_shadows) ------------------------------
 // The same lists, counts and segments as the HIP library; a step appends the survivors in list order (the HIP kernel in any
 // order: the sets are the same).
-#pragma GCC push_options
-#pragma GCC optimize("fp-contract=off")
 // pre-activation of the last layer for one point, per-shape mode (packed of sg_sdfnet_pack_shape_bias_cpu, kin_used = 3)
 static float rm_sdf_pre(const CpuSdf& v, const float* x, const float* zb1, const float* zb5) {
     float h[256], h2[256];
@@ -1900,23 +1816,9 @@ int sg_raymarch_rays_cpu(const double* camera, int width, long nshapes, double r
     const volatile float cfv[3] = {(float)camera[0], (float)camera[1], (float)camera[2]};
     const float cf[3] = {cfv[0], cfv[1], cfv[2]};
     const double cc =(camera[0] * camera[0] + camera[1] * camera[1] + camera[2] * camera[2]) - radius * radius;
-    const double step = width > 1 ? 2.0 / (double)(width - 1) : 0.0;
     for (long pix = 0; pix < M; ++pix) {
-        const long row = pix / width, col = pix - row * width;
-        const double sx = col == width - 1 && width > 1 ? 1.0 : (double)col * step + -1.0;
-        const double sy = row == width - 1 && width > 1 ? 1.0 : (double)row * step + -1.0;
-        float d[3], p[3] = {cf[0], cf[1], cf[2]};
-        for (int c = 0; c < 3; ++c) d[c] = (float)(sx * camera[3 + c] + sy * camera[6 + c] + camera[12] * camera[9 + c]);
-        const float n = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        for (int c = 0; c < 3; ++c) d[c] = d[c] / n;
-        for (int c = 0; c < 3; ++c) dir[pix * 3 + c] = d[c];
-        const float b = (p[0] * d[0] + p[1] * d[1] + p[2] * d[2]) * 2.f;
-        const double disc = (double)(b * b) - 4.0 * cc;
-        const bool inside = disc >= 0.0;
-        if (inside) {
-            const double t = (-(double)b - sqrt(disc)) / 2.0;
-            for (int c = 0; c < 3; ++c) p[c] = (float)((double)p[c] + (double)d[c] * t);
-        }
+        float p[3] = {cf[0], cf[1], cf[2]};
+        const bool inside = sg_rm_camera_ray(camera, cc, width, pix, dir + pix * 3, p);
         for (long s = 0; s < nshapes; ++s) {
             const long r = s * M + pix;
             for (int c = 0; c < 3; ++c) pos[r * 3 + c] = p[c];
@@ -1970,18 +1872,12 @@ int sg_raymarch_steps_cpu(const float* packed, const float* zb1, const float* zb
         for (long i = 0; i < n; ++i) {
             const long r = ray[i];
             const long di = dir_period > 0 ? r % dir_period : r;
-            float* p = pos + r * 3;
-            const float s = sdf[i];
-            const float x = p[0] + dir[di * 3] * s, y = p[1] + dir[di * 3 + 1] * s, z = p[2] + dir[di * 3 + 2] * s;
-            p[0] = x;
-            p[1] = y;
-            p[2] = z;
-            if (s > 0.f && s < threshold) {
+            sg_rm_move(pos + r * 3, dir + di * 3, sdf[i]);
+            if (sg_rm_hit(sdf[i], threshold)) {
                 status[r] = 1;
                 continue;
             }
-            const float rad = seg[i] < nshapes ? radius0 : radius1;
-            if (shadow ? y > rad : sqrtf(x * x + y * y + z * z) > rad) continue;
+            if (sg_rm_left(pos + r * 3, seg[i] < nshapes ? radius0 : radius1, shadow)) continue;
             next[seg_off[seg[i]] + cw[seg[i]]++] = (int)r;
         }
     }
@@ -1995,16 +1891,6 @@ int sg_raymarch_finish_cpu(unsigned char* status, const int* active, long nrays,
     for (long s = 0; s < nseg; ++s)
         for (int k = 0; k < counts[(iter % 3) * nseg + s]; ++k) status[cur[seg_off[s] + k]] = 1;
     return SG_OK;
-}
-
-static bool rm_ground_point(const unsigned char* status, const float* pos, const float* dir, long M, long s, long pix, float ground,
-                            float q[3]) {
-    const float* d = dir + pix * 3;
-    if (!(d[1] < 0.f) || status[s * M + pix]) return false;
-    const float* p = pos + (s * M + pix) * 3;
-    const float t = (p[1] - ground) / d[1];
-    for (int c = 0; c < 3; ++c) q[c] = p[c] - d[c] * t;
-    return sqrtf(q[0] * q[0] + q[2] * q[2]) < 3.f;
 }
 
 int sg_raymarch_classify_cpu(unsigned char* status, const float* pos, const float* dir, long M, long nshapes, int use_cutoff,
@@ -2030,22 +1916,10 @@ int sg_raymarch_classify_cpu(unsigned char* status, const float* pos, const floa
         long n = 0;
         float q[3];
         if (h > 0)
-            for (long pix = 0; pix < M; ++pix) n += rm_ground_point(status, pos, dir, M, s, pix, g, q) ? 1 : 0;
+            for (long pix = 0; pix < M; ++pix) n += sg_rm_ground_point(status[s * M + pix], pos + (s * M + pix) * 3, dir + pix * 3, g, q) ? 1 : 0;
         gnd_off[s + 1] = gnd_off[s] + n;
     }
     return SG_OK;
-}
-
-static void rm_shadow_ray(const double* light, const float q[3], long j, float* spos, float* sdir, int* sactive) {
-    double d[3];
-    for (int c = 0; c < 3; ++c) d[c] = light[c] - (double)q[c];
-    const double n = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    for (int c = 0; c < 3; ++c) {
-        const float df = (float)(d[c] / n);
-        sdir[j * 3 + c] = df;
-        spos[j * 3 + c] = q[c] + df * 0.1f;
-    }
-    sactive[j] = (int)j;
 }
 
 int sg_raymarch_emit_cpu(const unsigned char* status, const float* pos, const float* dir, long M, long nshapes, const float* ground,
@@ -2064,11 +1938,13 @@ int sg_raymarch_emit_cpu(const unsigned char* status, const float* pos, const fl
                 for (int c = 0; c < 3; ++c) q[c] = hit_pos[h * 3 + c] = pos[r * 3 + c];
                 hit_sid[h] = (int)s;
                 slot[r] = (int)h;
-                rm_shadow_ray(light, q, h, shadow_pos, shadow_dir, shadow_active);
+                sg_rm_shadow_ray(light, q, shadow_dir + h * 3, shadow_pos + h * 3);
+                shadow_active[h] = (int)h;
                 ++h;
-            } else if (hit_off[s + 1] > hit_off[s] && rm_ground_point(status, pos, dir, M, s, pix, ground[s], q)) {
+            } else if (hit_off[s + 1] > hit_off[s] && sg_rm_ground_point(status[r], pos + r * 3, dir + pix * 3, ground[s], q)) {
                 slot[r] = -2 - (int)g;
-                rm_shadow_ray(light, q, H + g, shadow_pos, shadow_dir, shadow_active);
+                sg_rm_shadow_ray(light, q, shadow_dir + (H + g) * 3, shadow_pos + (H + g) * 3);
+                shadow_active[H + g] = (int)(H + g);
                 ++g;
             } else {
                 slot[r] = -1;
@@ -2089,49 +1965,13 @@ int sg_raymarch_shade_cpu(const int* slot, const float* hit_pos, const float* gr
     CPU_CHECK(nhits == 0 || (hit_pos && grad && shadow));
 #pragma omp parallel for schedule(static)
     for (long r = 0; r < nshapes * M; ++r) {
-        const long pix = r % M;
-        const int k = slot[r];
-        double px[3] = {1.0, 1.0, 1.0};
-        if (k >= 0) {
-            const float* g = grad + (long)k * 3;
-            const float gn = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
-            const float nf[3] = {g[0] / gn, g[1] / gn, g[2] / gn};
-            const float* d = dir + pix * 3;
-            const double seen = (double)(1.f - (float)shadow[k]);
-            double ld[3];
-            for (int c = 0; c < 3; ++c) ld[c] = light[c] - (double)hit_pos[(long)k * 3 + c];
-            const double ln = sqrt(ld[0] * ld[0] + ld[1] * ld[1] + ld[2] * ld[2]);
-            for (int c = 0; c < 3; ++c) ld[c] = ld[c] / ln;
-            const double dn = ld[0] * nf[0] + ld[1] * nf[1] + ld[2] * nf[2];
-            const double diffuse = std::min(std::max(dn, 0.0), 1.0) * seen;
-            double rf[3];
-            for (int c = 0; c < 3; ++c) rf[c] = ld[c] - dn * (double)nf[c] * 2.0;
-            const double rn = sqrt(rf[0] * rf[0] + rf[1] * rf[1] + rf[2] * rf[2]);
-            double spec = (rf[0] / rn) * d[0] + (rf[1] / rn) * d[1] + (rf[2] / rn) * d[2];
-            spec = std::min(std::max(spec, 0.0), 1.0);
-            spec = pow(spec, 20.0) * seen;
-            float rim = -(nf[0] * d[0] + nf[1] * d[1] + nf[2] * d[2]);
-            rim = 1.f - std::min(std::max(rim, 0.f), 1.f);
-            rim = rim * rim * rim * rim * 0.3f;
-            for (int c = 0; c < 3; ++c)
-                px[c] = std::min(std::max(color[c] * (diffuse * 0.5 + 0.5) + (spec * 0.3 + (double)rim), 0.0), 1.0);
-        } else if (k <= -2) {
-            const double dk = (double)(0.35f * (float)shadow[nhits + (-2 - k)]);
-            for (int c = 0; c < 3; ++c) px[c] -= dk;
-        }
-        for (int c = 0; c < 3; ++c) image[r * 3 + c] = (unsigned char)(px[c] * 255.0);
+        sg_rm_shade(slot[r], dir + (r % M) * 3, hit_pos, grad, shadow, nhits, light, color, image + r * 3);
     }
     return SG_OK;
 }
-#pragma GCC pop_options
 
 // ---- K13: point-cloud evaluation (include/shapegan_hip.h) -------------------------------------------------------------------
-#pragma GCC push_options
-#pragma GCC optimize("fp-contract=off")
-static inline float cd_pair(const float* a, const float* b) {
-    const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
-    return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-}
+static inline float cd_pair(const float* a, const float* b) { return sg_pc_d2(a[0], a[1], a[2], b[0], b[1], b[2]); }
 
 // the header's summation order of the minima m[0..n): tiles of 2048, 256 strided partial sums, a halving tree, tiles in order
 static double cd_mean(const float* m, long n) {
@@ -2207,37 +2047,18 @@ int sg_chamfer_nearest_cpu(const float* A, const float* B, long S, long P, long 
     return SG_OK;
 }
 
-static inline int occupancy_axis(float x, float rm1) {
-    const float t = (x + 0.5f) * rm1;
-    float f = floorf(t + 0.5f);
-    f = f > 0.f ? f : 0.f;       // NaN -> 0
-    return (int)(f < rm1 ? f : rm1);
-}
-
 int sg_occupancy_histogram_cpu(const float* clouds, long S, long P, int R, int64_t* hist, hipStream_t_) {
     CPU_CHECK(clouds && hist && S >= 1 && P >= 1 && R >= 2 && R <= 1024 && S * P <= (1L << 38));
     const float rm1 = (float)(R - 1);
     for (long i = 0; i < S * P; ++i) {
-        const int ix = occupancy_axis(clouds[i * 3], rm1), iy = occupancy_axis(clouds[i * 3 + 1], rm1),
-                  iz = occupancy_axis(clouds[i * 3 + 2], rm1);
+        const int ix = sg_pc_occupancy_axis(clouds[i * 3], rm1), iy = sg_pc_occupancy_axis(clouds[i * 3 + 1], rm1),
+                  iz = sg_pc_occupancy_axis(clouds[i * 3 + 2], rm1);
         hist[((long)ix * R + iy) * R + iz] += 1;
     }
     return SG_OK;
 }
 
 // ---- K15: earth mover's distance (include/shapegan_hip.h): the same rounds as csrc/emd.hip, from a table of the integer costs ----
-#define SG_EMD_MAX_POINTS 2048
-#define SG_EMD_MAX_COST (1 << 22)
-#define SG_EMD_ROUND_CAP (1 << 20)
-
-// the largest f32 that is not above eps / 4; 0 when eps is not a positive finite number or eps / 4 is below the normal range
-static float emd_unit(double eps) {
-    if (!(eps > 0.0) || !(eps < INFINITY) || eps / 4 < 1.17549435e-38) return 0.f;
-    float u = (float)(eps / 4);
-    if ((double)u > eps / 4) u = nextafterf(u, 0.f);
-    return u;
-}
-
 struct EmdScratch {
     std::vector<int> cost, price, owner, asg, list;
     std::vector<uint64_t> bid;
@@ -2251,9 +2072,8 @@ static void emd_pair(const float* a, const float* b, int P, float u, int* match,
     for (int i = 0; i < P; ++i)
         for (int j = 0; j < P; ++j) {
             const float d = sqrtf(cd_pair(a + i * 3, b + j * 3));
-            const float q = d / u;
-            const int k = q < (float)SG_EMD_MAX_COST ? (int)floorf(q) : SG_EMD_MAX_COST;      // NaN: the comparison is false
-            too_small |= d < INFINITY && q >= (float)SG_EMD_MAX_COST;
+            const int k = sg_emd_cost(d, u);
+            too_small |= sg_emd_too_small(d, u);
             w.cost[(size_t)i * P + j] = k;
             kmax = k > kmax ? k : kmax;
         }
@@ -2319,23 +2139,20 @@ static void emd_pair(const float* a, const float* b, int P, float u, int* match,
 }
 
 static bool emd_args_ok(long S, long P, double eps, const char* who) {
-    if (P < 1 || P > SG_EMD_MAX_POINTS || S < 1 || S > 65535) {
+    const int refused = sg_emd_refused(S, P, eps);
+    if (refused == 1)
         snprintf(g_err, sizeof(g_err), "%s: 1 <= P <= %d points per cloud and at most 65535 clouds per call, got P = %ld", who,
                  SG_EMD_MAX_POINTS, P);
-        return false;
-    }
-    if (emd_unit(eps) == 0.f) {
+    else if (refused)
         snprintf(g_err, sizeof(g_err), "%s: eps must be a finite number of at least 4.8e-38, got %g", who, eps);
-        return false;
-    }
-    return true;
+    return !refused;
 }
 
 int sg_emd_match_cpu(const float* A, const float* B, long S, long P, double eps, int* match, double* emd, int* rounds, int* status,
                      hipStream_t_) {
     CPU_CHECK(A && B && emd && status);
     if (!emd_args_ok(S, P, eps, __func__)) return SG_ERR_ARG;
-    const float u = emd_unit(eps);
+    const float u = sg_emd_unit(eps);
 #pragma omp parallel
     {
         EmdScratch w;
@@ -2352,7 +2169,7 @@ int sg_emd_matrix_cpu(const float* A, const float* B, long Sa, long Sb, long P, 
     CPU_CHECK(A && B && emd && status && workspace && Sb >= 1 && Sb <= 65535 && (!symmetric || Sa == Sb));
     if (!emd_args_ok(Sa, P, eps, __func__)) return SG_ERR_ARG;
     CPU_CHECK(workspace_bytes >= (size_t)(Sa * Sb) * sizeof(int));
-    const float u = emd_unit(eps);
+    const float u = sg_emd_unit(eps);
     int* rounds = (int*)workspace;
 #pragma omp parallel
     {
@@ -2376,8 +2193,7 @@ int sg_emd_matrix_cpu(const float* A, const float* B, long Sa, long Sb, long P, 
 
 // ---- K14: tiled rasteriser (include/shapegan_hip.h) --------------------------------------------------------------------------------
 // The per-triangle and per-sample arithmetic is csrc/raster_core.h, the file the HIP kernels include: one statement of every fp32
-// formula.  What is written here is the part the header leaves to each library: the loops, the bins (filled in triangle order) and
-// the search for the winner.
+// formula, like the areas above.  What is written here: the loops, the bins (filled in triangle order) and the search for the winner.
 #pragma GCC push_options
 #pragma GCC optimize("fp-contract=off")
 #include "../csrc/raster_core.h"
