@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 import shapegan_amd.lib as L
+import conv_patterns as GRIDS
 import test_gpu_modules as M
 import test_gpu_ops as OPS
 import test_gpu_losses as LOSS
@@ -71,6 +72,50 @@ def test_conv3d(on_cpu, N, Ci, Co, R):
 @pytest.mark.parametrize("N,Ci,Co,R", [(2, 16, 8, 4), (3, 8, 1, 8), (1, 5, 3, 3)])
 def test_conv_transpose3d(on_cpu, N, Ci, Co, R):
     OPS.test_conv_transpose3d(N, Ci, Co, R)
+
+
+# the bodies of tests/test_gpu_conv_grids.py that use dispatching entries only (the *_impl hooks have no twin): grids of three extents
+@pytest.mark.parametrize("N,Ci,Co,grid", GRIDS.TILE_CASES)
+def test_conv3d_grids(on_cpu, N, Ci, Co, grid):
+    GRIDS.body_conv3d(N, Ci, Co, grid)
+
+
+@pytest.mark.parametrize("pattern", GRIDS.PATTERNS)
+def test_conv_fwd_patterns(on_cpu, pattern):
+    GRIDS.body_fwd_dispatch(*GRIDS.FWD_SPLIT_CASE, pattern)
+
+
+@pytest.mark.parametrize("pattern", ["random", "border"])
+@pytest.mark.parametrize("N,Ci,Co,ogrid", GRIDS.DGRAD_ROWS64)
+def test_conv_dgrad_grids(on_cpu, N, Ci, Co, ogrid, pattern):
+    GRIDS.body_dgrad_dispatch(N, Ci, Co, ogrid, pattern)
+
+
+def test_conv_dgrad_keep_twice(on_cpu, monkeypatch):
+    GRIDS.body_dgrad_keep_twice(*GRIDS.DGRAD_ROWS64[1], monkeypatch)
+
+
+@pytest.mark.parametrize("N,Ci,Co,grid", GRIDS.C1_CASES)
+def test_conv_one_channel_grids(on_cpu, N, Ci, Co, grid):
+    GRIDS.body_c1(N, Ci, Co, grid)
+    if grid in [c[3] for c in GRIDS.C1_CASES[:2]]:
+        for act in (1, 2):
+            GRIDS.body_c1_wgrad_act(N, Ci, Co, grid, act)
+
+
+@pytest.mark.parametrize("N,C,Co,grid", GRIDS.CONVT_TO1_CASES)
+def test_conv_transpose3d_to_one_channel_grids(on_cpu, N, C, Co, grid):
+    GRIDS.body_convT_to1(N, C, Co, grid)
+
+
+@pytest.mark.parametrize("N,C,grid", GRIDS.CONVT_TO1_PRE_CASES)
+def test_conv_transpose3d_to1_pre_grids(on_cpu, N, C, grid):
+    GRIDS.body_convT_to1_pre(N, C, grid)
+
+
+@pytest.mark.parametrize("N,Ci,Co,grid", GRIDS.CONVT_CASES)
+def test_conv_transpose3d_grids(on_cpu, N, Ci, Co, grid):
+    GRIDS.body_convT(N, Ci, Co, grid)
 
 
 def test_conv_wgrad_through_activation(on_cpu):

@@ -27,6 +27,7 @@ import torch
 import torch.nn.functional as F
 
 from poison import poisoned, run_poisoned
+import conv_patterns as GRIDS
 import evaluation_reference as ER
 import test_evaluation as EV
 import test_gpu_losses as LOSS
@@ -92,6 +93,8 @@ BODIES = [
     (OPS.test_conv_transpose3d, (1, 5, 3, 3)), (OPS.test_conv_transpose3d, (70, 64, 1, 2)), (OPS.test_conv_transpose3d, (2, 3, 1, 12)),
     (OPS.test_conv_transpose3d_to_one_channel_random_shapes, ()),
     (OPS.test_conv_transpose3d_to_one_channel_streaming_kernel_random_shapes, ()),          # (all eight to1_pre forms)
+    # the same families on grids of three different extents (tests/test_gpu_conv_grids.py)
+    *GRIDS.DISPATCH_BODIES, *GRIDS.FORCED_BODIES,
     (OPS.test_linear_fwd_bwd, (5, 7, 3)), (OPS.test_linear_fwd_bwd, (200, 300, 130)), (OPS.test_linear_fwd_bwd, (4, 128, 256)),
     (OPS.test_linear_fwd_bwd, (16388, 384, 320)), (OPS.test_linear_fwd_bwd, (40004, 128, 100)),
     (OPS.test_gemm128_persistent_all_layouts, (70004, 256, 100)),
@@ -199,7 +202,8 @@ def test_conv_forward_forms(N, Ci, Co, R):
     x, w, b = torch.randn(N, Ci, R, R, R), torch.randn(Co, Ci, 4, 4, 4) / (Ci * 64) ** 0.5, torch.randn(Co)
     ref = _lrelu(F.conv3d(x.double(), w.double(), b.double(), stride=2, padding=1))
     xg, wg, bg = x.cuda(), w.cuda(), b.cuda()
-    forms = [(0, 0), (1, 0)] + ([(1, 48), (1, 128)] if R // 2 >= 8 else [])       # (gather, halo, halo with 64- / 128-row tiles)
+    # (gather, halo, halo with 64- / 128-row tiles, 4 waves x 2 column tiles, no LDS cap)
+    forms = [(0, 0), (1, 0)] + ([(1, 48), (1, 128), (1, 16), (1, 64)] if R // 2 >= 8 else [])
     for impl, debug in forms:
         what = "conv fwd impl %d debug %d" % (impl, debug)
         run_form(lambda: ops.conv_fwd_impl_raw(xg, wg, bg, 1, 0.2, impl=impl, debug=debug),
@@ -235,6 +239,19 @@ def test_conv_dgrad_halo_forms(N, Ci, Co, O):
         impl = 1 if ppw == 1 else 1 + 4 * ppw
         what = "dgrad halo, %d parities per workgroup" % ppw
         run_form(lambda: ops.conv_dgrad_halo_raw(dyg, wg, bg, Ci, 1, 0.2, impl=impl), lambda o: OPS.close(o[0], ref, what=what), what=what)
+
+
+@pytest.mark.parametrize("N,Ci,Co,ogrid", [(8, 72, 32, (4, 16, 32)), (255, 72, 32, (4, 4, 4))])
+def test_conv_dgrad_halo_rows64_forms(N, Ci, Co, ogrid):
+    """The 64-row kernels (conv_dgrad_halo_kernel<0> / <1>: what production takes at batch 64) with 4 (the dispatch rule), 1, 2, 4 and 8
+    parities per workgroup; 72 input channels = a full row tile + 8 rows, 255 samples = a last workgroup with one sample."""
+    from shapegan_amd import ops
+    from shapegan_amd.lib import ACT_LEAKY
+    dy, w, b, ref = GRIDS.dgrad_inputs(N, Ci, Co, ogrid, "random", ACT_LEAKY)
+    dyg, wg, bg = dy.cuda(), w.cuda(), b.cuda()
+    for impl in (1, 3, 9, 17, 33):
+        what = "dgrad halo, 64 rows, impl %d" % impl
+        run_form(lambda: ops.conv_dgrad_halo_raw(dyg, wg, bg, Ci, ACT_LEAKY, 0.2, impl=impl), lambda o: OPS.close(o[0], ref, what=what), what=what)
 
 
 @pytest.mark.parametrize("N,Ci,Co,O", [(1, 3, 32, 8), (1, 3, 40, 4), (9, 16, 130, 4)])

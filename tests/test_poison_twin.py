@@ -6,6 +6,7 @@ then isolates the HIP kernels and their workspace contracts."""
 import pytest
 import torch
 
+import conv_patterns as GRIDS
 import poison
 from poison import poisoned, run_poisoned
 from test_cpu_twin import on_cpu  # noqa: F401  (fixture)
@@ -117,6 +118,7 @@ BODIES = [
     (OPS.test_conv_wgrad_through_activation, (2, 5, 4, 1)), (OPS.test_conv_wgrad_through_activation, (1, 3, 2, 2)),
     (OPS.test_conv_from_sdf_zero_channels, ()),
     (OPS.test_conv_transpose3d_to_one_channel_streaming_kernel_random_shapes, ()),
+    *GRIDS.DISPATCH_BODIES,          # (the conv family on grids of three different extents: tests/test_gpu_conv_grids.py)
     (OPS.test_linear_fwd_bwd, (64, 128, 256)), (OPS.test_linear_fwd_bwd, (4, 128, 256)), (OPS.test_linear_fwd_bwd, (5, 7, 3)),
     (OPS.test_gemm_double_backward, ()),
     (OPS.test_batchnorm_train_fwd_bwd, (4, 8, 64)), (OPS.test_batchnorm_train_fwd_bwd, (4, 256, 1)),
