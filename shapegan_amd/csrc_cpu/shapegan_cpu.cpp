@@ -617,7 +617,8 @@ int sg_sdfnet_fwd_cpu(const float* points, long points_period, const float* late
                       const float* packed, int kin_used, const float* zb1, const float* zb5, long points_per_shape,
                       const int* shape_index, float* out, float* acts, long ldn, long N, void*) {
     CPU_CHECK(points && packed && out && N > 0 && kin_used >= 3 && (kin_used == 3 || latent) && ((zb1 != nullptr) == (zb5 != nullptr)));
-    CPU_CHECK(!zb1 || shape_index || points_per_shape > 0);
+    // (the HIP library's rule — its tiles must not straddle shapes —, kept here so that the CPU tier sees a caller that breaks it)
+    CPU_CHECK(!zb1 || shape_index || (points_per_shape > 0 && (points_per_shape % 128 == 0 || points_per_shape >= N)));
     const CpuSdf v = sdf_view(packed, kin_used);
     const int KU = kin_used, L = latent_size;
 #pragma omp parallel for schedule(static)

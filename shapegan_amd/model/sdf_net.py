@@ -119,16 +119,21 @@ class SDFNet(SavableModule):
 
     def grid_values(self, latent_codes, points):
         """SDF of every shape at every point of one shared grid: latent_codes [S,L], points [P,3] -> [S,P] on the points' device.
-        One sg_sdfnet_fwd launch with points_period = P: the grid is not tiled S times."""
+        One sg_sdfnet_fwd launch with points_period = P: the grid is not tiled S times.  Any P and S: where a 64-point tile could
+        straddle two shapes (several shapes of P points, P no multiple of 128: every sphere-masked grid) each point names its
+        shape, as in forward_segments."""
         z = ops.f32c(latent_codes.detach().reshape(-1, self.latent_code_size))
         points = ops.f32c(points)
         S, P = z.shape[0], points.shape[0]
         with torch.no_grad():
             packed, zb1, zb5 = self._pack_shapes.get_with_fold(self._params(), z)
             out = torch.empty((S, P), dtype=torch.float32, device=points.device)
+            sid = None
+            if S > 1 and P % 128 != 0:
+                sid = torch.arange(S, dtype=torch.int32, device=points.device).repeat_interleave(P)
             lib = ops._lib()
             ops.check(lib.sg_sdfnet_fwd(ops.ptr(points), P, None, None, z.shape[1], ops.ptr(packed), 3, ops.ptr(zb1), ops.ptr(zb5), P,
-                                        None, ops.ptr(out), None, S * P, S * P, ops.stream()), "sdfnet_fwd")
+                                        ops.ptr(sid), ops.ptr(out), None, S * P, S * P, ops.stream()), "sdfnet_fwd")
         return out
 
     def voxel_grids(self, latent_codes, voxel_resolution, sphere_only=True, pad=True):

@@ -13,6 +13,7 @@ import torch.nn as nn
 
 import shapegan_amd.lib as L
 import conv_patterns as GRIDS
+import sdfnet_forms as FORMS
 import test_gpu_modules as M
 import test_gpu_ops as OPS
 import test_gpu_losses as LOSS
@@ -172,6 +173,62 @@ def test_sdfnet_shapes(on_cpu, S, pps):
 @pytest.mark.parametrize("S,N", [(5, 700), (3, 64), (7, 33100)])   # 33100: 512 tiles of 64 + 11 of 32 in the partial-sum layout
 def test_sdfnet_segments(on_cpu, S, N):
     OPS.test_sdfnet_segments_mode(S, N)
+
+
+# the bodies of tests/test_gpu_sdfnet_forms.py (tests/sdfnet_forms.py): the fused MLP in every calling form against float64
+@pytest.mark.parametrize("need_p,need_z,need_w", FORMS.SUBSETS)
+@pytest.mark.parametrize("mode", FORMS.MODES)
+def test_sdfnet_which_grads(on_cpu, mode, need_p, need_z, need_w):
+    FORMS.body_which_grads(mode, need_p, need_z, need_w)
+
+
+@pytest.mark.parametrize("with_reg", [True, False])
+def test_sdfnet_segments_by_position(on_cpu, with_reg):
+    FORMS.body_segments_dense(with_reg)
+
+
+@pytest.mark.parametrize("where", sorted(FORMS.ONE_HOT_POSITIONS))
+def test_sdfnet_segments_one_hot(on_cpu, where):
+    FORMS.body_segments_one_hot(where)
+
+
+@pytest.mark.parametrize("kind", sorted(FORMS.DEGENERATE))
+def test_sdfnet_segments_degenerate_tables(on_cpu, kind):
+    FORMS.body_segments_degenerate(kind)
+
+
+@pytest.mark.parametrize("S,reg,z_only", FORMS.FOLD_CASES)
+def test_sdfnet_beyond_the_one_launch_fold(on_cpu, S, reg, z_only):
+    FORMS.body_beyond_fold(S, reg, z_only)
+
+
+def test_sdfnet_fold_forms(on_cpu):
+    FORMS.body_fold_forms()
+
+
+@pytest.mark.parametrize("train", [False, True])
+def test_sdfnet_raw_abi_latent_idx_and_points_period(on_cpu, train):
+    FORMS.body_raw_abi(train)
+
+
+@pytest.mark.parametrize("latent", FORMS.EDGE_LATENTS)
+@pytest.mark.parametrize("mode", ["points", "ragged"])
+def test_sdfnet_latent_sizes_at_the_padding_edges(on_cpu, mode, latent):
+    FORMS.body_latent_size(mode, latent)
+
+
+@pytest.mark.parametrize("R", sorted(FORMS.SPHERE_POINTS))
+def test_sdfnet_voxel_grids_of_several_shapes(on_cpu, R):
+    FORMS.body_sphere_grids(R)
+
+
+def test_sdfnet_grid_values_of_several_shapes(on_cpu):
+    FORMS.body_grid_values()
+
+
+def test_sdfnet_points_per_shape_refusal(on_cpu):
+    """The twin refuses what the HIP library refuses: a caller that only the HIP library would stop shows in this tier."""
+    FORMS.body_points_per_shape_refusal()
 
 
 @pytest.mark.parametrize("S,pc,N", [(64, 200, 20000), (5, 40, 700), (300, 7, 1000), (4097, 3, 9000)])
