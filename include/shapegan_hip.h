@@ -731,6 +731,70 @@ size_t sg_emd_matrix_workspace_bytes(long Sa, long Sb, long P);
 int sg_emd_matrix(const float* A, const float* B, long Sa, long Sb, long P, double eps, int symmetric, double* emd, int* status,
                   void* workspace, size_t workspace_bytes, hipStream_t stream);
 
+/* ---- K16: meshes to signed distances: exact point-triangle distances, the sign from orthographic depth scans --------------------------
+ * reference: prepare_shapenet_dataset.py:69-131 and prepare_data.py, which sit on mesh_to_sdf's "depth" method (USE_DEPTH_BUFFER =
+ *            True): a point is OUTSIDE when at least one of K virtual scans sees it — what makes ShapeNet's open, inconsistently
+ *            oriented meshes usable.  Two deliberate differences: the magnitude is the exact distance to the triangles (mesh_to_sdf:
+ *            the distance to a scanned point cloud through a kd-tree), and the scans are orthographic, so depth is linear in distance
+ *            and one bias holds everywhere (mesh_to_sdf: perspective at fov 1 rad).
+ * Input: S triangle soups packed as K14 takes them (positions [T][3][3] fp32, tri_offsets [S+1] int64; any shape may be empty) and
+ * Q query points per shape, points [S][Q][3] fp32.  1 <= S <= 65535, 0 <= T <= SG_MESHSDF_MAX_TRIANGLES, 1 <= Q <=
+ * SG_MESHSDF_MAX_POINTS, S Q <= SG_MESHSDF_MAX_TOTAL_POINTS; beyond: SG_ERR_ARG, in the library and the twin alike.  All arithmetic is
+ * fp32 with the fused steps written out (contraction off) and exists once (csrc/meshsdf_core.h); a minimum of f32 values does not
+ * depend on the order it is taken in: dist2, tri, closest, outside and sdf are the same BIT FOR BIT on the GPU, in the twin and
+ * under any tiling.
+ *
+ * sg_meshsdf_distance: dist2 [S][Q] fp32 = the minimum over the triangles of shape s of the squared distance from the point to the
+ *   closest point of the triangle; tri [S][Q] int32 (may be NULL) = the LOWEST triangle index, local to the shape, that attains it;
+ *   closest [S][Q][3] fp32 (may be NULL) = that triangle's closest point.  A shape without triangles: dist2 = +inf, tri = -1,
+ *   closest = 0.  Per triangle (a, b, c), made once per call: ab = b - a, bc = c - b, ca = a - c; i_e = 1 / |e|^2 per edge, 0 when
+ *   |e|^2 < 1e-30 (no division has a divisor that can be 0); n = ab x ac; gv = (ac x n) i_n, gw = (n x ab) i_n, i_n = 1 / |n|^2 or 0
+ *   alike.  dot(a, b) = fmaf(a2, b2, fmaf(a1, b1, a0 b0)); cross components fmaf(a, b, -(c d)).  Per pair, four candidates, each the
+ *   squared length |r|^2 = dot(r, r) of the residual of a point of the triangle:
+ *     edge from corner o along e, q = p - o:  t = dot(q, e) i_e, clamped to [0, 1] by comparisons (NaN -> 0);  r = fmaf(-t, e, q)
+ *       (ab from a, bc from b, ca from c: a point ON a corner has r = 0 and dist2 exactly 0);
+ *     face, q = p - a:  v = dot(q, gv), w = dot(q, gw);  counted only when v >= 0, w >= 0, v + w <= 1;  r = fmaf(w, ca, fmaf(-v, ab, q)).
+ *   The pair's value is the smallest, the first of (ab, bc, ca, face) on a tie; its point is fmaf(t, e, o), or for the face
+ *   fmaf(-w, ca, fmaf(v, ab, a)).  Every candidate is the distance to a point of the triangle, so a zero-area or collinear triangle
+ *   (gv = gw = 0, or weights without meaning) gives a finite value that is one, for every finite input.  A candidate replaces the
+ *   running minimum only when it is smaller (strict, NaN never): non-finite points or corners give unspecified values, no fault,
+ *   and tri in [-1, T_s).
+ *   The grid is (blocks of queries) x (split) x S: the triangles of a shape are cut into `split` runs of whole LDS chunks of
+ *   SG_MESHSDF_CHUNK records, and the partial minima meet in a 64-bit unsigned atomicMin on (bits(d2) << 32 | tri) — d2 >= +0, so
+ *   its bits order like the value and the lowest index wins a tie.  workspace: the triangle records [T][32] fp32, then the packed
+ *   minima [S][Q] uint64, which the entry point itself sets to all ones before the launch (nothing is read that the call did not
+ *   write).  sg_meshsdf_distance_impl (testing / tuning): split > 0 forces the factor (capped by the number of chunks T allows),
+ *   <= 0 = the host's choice; chosen (may be NULL) receives the factor used.  The results do not depend on it.
+ *
+ * sg_meshsdf_sign: depth [K][S][N][N] fp32 = K14's depth (NDC z, smaller = nearer the scan, 1.0 = nothing drawn) of the shapes under
+ *   the K views vps [K][16] (host doubles, row-major, rounded ONCE to fp32 = M; 1 <= K <= SG_MESHSDF_MAX_SCANS, N <= 16384).  A row
+ *   3 other than (0, 0, 0, 1) — a perspective view — is refused with SG_ERR_ARG.  Per point (x, y, z) and scan k:
+ *     c_j = fmaf(M[j][2], z, fmaf(M[j][1], y, fmaf(M[j][0], x, M[j][3])))   j = 0, 1, 2       (the rows of sg_raster_setup)
+ *     fx = fmaf(c_0, 0.5f N, 0.5f N),  fy = fmaf(c_1, -0.5f N, 0.5f N)
+ *     in_window = fx >= 0 && fx < N && fy >= 0 && fy < N                                   (false for NaN)
+ *     t = depth[k][s][(int) fy][(int) fx]                                                 (read only when in_window)
+ *     visible_k = !in_window || t == 1.0f || c_2 < t - bias
+ *   outside [S][Q] uint8 (may be NULL) = OR_k visible_k;  sdf [S][Q] fp32 = outside ? sqrtf(dist2) : -sqrtf(dist2), given iff dist2
+ *   [S][Q] is given.  bias >= 0, finite; the callers' default is 2 / N, one texel in NDC units.  No map is read outside [0, N)^2
+ *   for any input, non-finite included.
+ * The scans of shapegan_amd/prepare.py: K directions on a Fibonacci sphere, computed on the host in float64:
+ *   y = 1 - (2 i + 1) / K,  r = sqrt(1 - y^2),  phi = i pi (3 - sqrt 5),  d = (r cos phi, y, r sin phi);
+ *   up = (0, 1, 0), or (1, 0, 0) when |d_y| > 0.9;  u = normalize(up x d),  v = d x u;  for the bounding radius rho the view has the
+ *   rows u / rho, v / rho, -d / rho, (0, 0, 0, 1);  depth map k = sg_raster_* of the soup under it, N x N, nothing culled. */
+#define SG_MESHSDF_CHUNK 256
+#define SG_MESHSDF_MAX_SCANS 64
+#define SG_MESHSDF_MAX_TRIANGLES 16777216      /* 2^24 */
+#define SG_MESHSDF_MAX_POINTS 16777216         /* 2^24 per shape */
+#define SG_MESHSDF_MAX_TOTAL_POINTS 268435456  /* 2^28 per call */
+size_t sg_meshsdf_distance_workspace_bytes(long S, long T, long Q);
+int sg_meshsdf_distance(const float* positions, const int64_t* tri_offsets, long S, long T, const float* points, long Q, float* dist2,
+                        int* tri, float* closest, void* workspace, size_t workspace_bytes, hipStream_t stream);
+int sg_meshsdf_distance_impl(const float* positions, const int64_t* tri_offsets, long S, long T, const float* points, long Q,
+                             float* dist2, int* tri, float* closest, void* workspace, size_t workspace_bytes, int split, int* chosen,
+                             hipStream_t stream);
+int sg_meshsdf_sign(const float* points, long S, long Q, const float* depth, const double* vps, int K, int N, float bias,
+                    const float* dist2, float* sdf, unsigned char* outside, hipStream_t stream);
+
 /* ---- sphere tracing of SDFNet shapes (rendering/raymarching.py:render_image, get_shadows) ----------------------------------
  * S images of the same camera, M = width^2 pixels each; ray r = s * M + pixel.  Rays live in segments with an active list each
  * (active [2][nrays], counts [3][nseg] int32, seg_off [nseg + 1] int64): step `iter` reads list iter & 1 / counts iter % 3 and

@@ -2363,3 +2363,67 @@ int sg_raster_resolve_cpu(const unsigned char* samples, long S, int width, int h
 
 }  // extern "C"
 #pragma GCC pop_options
+
+// ---- K16: meshes to signed distances (include/shapegan_hip.h) ----------------------------------------------------------------------
+// The per-pair arithmetic is csrc/meshsdf_core.h, the file csrc/meshsdf.hip includes.  Here: the records, the walk over a shape's
+// triangles in increasing index with a strict comparison, and the loop over the scans.
+#pragma GCC push_options
+#pragma GCC optimize("fp-contract=off")
+#include "../csrc/meshsdf_core.h"
+
+extern "C" {
+
+int sg_meshsdf_distance_cpu(const float* positions, const int64_t* tri_offsets, long S, long T, const float* points, long Q, float* dist2,
+                            int* tri, float* closest, void* workspace, size_t workspace_bytes, hipStream_t_) {
+    CPU_CHECK(sg_msdf_sizes_ok(S, T, Q));
+    CPU_CHECK(tri_offsets && points && dist2 && workspace && (T == 0 || positions));
+    CPU_CHECK(workspace_bytes >= (size_t)T * sizeof(SgMsdfRec));      // the twin keeps its records where the library does
+    SgMsdfRec* recs = (SgMsdfRec*)workspace;
+#pragma omp parallel for schedule(static)
+    for (long t = 0; t < T; ++t) sg_msdf_record(positions + t * 9, &recs[t]);
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < S * Q; ++i) {
+        const long s = i / Q;
+        const long t0 = std::max<long>(tri_offsets[s], 0), t1 = std::min<long>(tri_offsets[s + 1], T);
+        const float px = points[i * 3], py = points[i * 3 + 1], pz = points[i * 3 + 2];
+        float best = INFINITY, c[3] = {0.f, 0.f, 0.f};
+        long arg = -1;
+        for (long t = t0; t < t1; ++t) {
+            const float d2 = sg_msdf_d2(px, py, pz, recs[t], nullptr);
+            if (d2 < best) {
+                best = d2;
+                arg = t - t0;
+            }
+        }
+        if (arg >= 0 && closest) sg_msdf_d2(px, py, pz, recs[t0 + arg], c);
+        dist2[i] = best;
+        if (tri) tri[i] = (int)arg;
+        if (closest) closest[i * 3] = c[0], closest[i * 3 + 1] = c[1], closest[i * 3 + 2] = c[2];
+    }
+    return SG_OK;
+}
+
+int sg_meshsdf_sign_cpu(const float* points, long S, long Q, const float* depth, const double* vps, int K, int N, float bias,
+                        const float* dist2, float* sdf, unsigned char* outside, hipStream_t_) {
+    CPU_CHECK(sg_msdf_sizes_ok(S, 0, Q) && sg_msdf_scans_ok(vps, K, N, bias));
+    CPU_CHECK(points && depth && (sdf != nullptr) == (dist2 != nullptr) && (sdf || outside));
+    std::vector<float> M((size_t)K * 12);
+    for (int k = 0; k < K; ++k)
+        for (int i = 0; i < 12; ++i) M[(size_t)k * 12 + i] = (float)vps[k * 16 + i];
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < S * Q; ++i) {
+        const long s = i / Q;
+        bool seen = false;
+        for (int k = 0; k < K && !seen; ++k)
+            seen = sg_msdf_visible(&M[(size_t)k * 12], points[i * 3], points[i * 3 + 1], points[i * 3 + 2], depth + ((long)k * S + s) * N * N, N, bias);
+        if (outside) outside[i] = seen ? 1 : 0;
+        if (sdf) {
+            const float d = sqrtf(dist2[i]);
+            sdf[i] = seen ? d : -d;
+        }
+    }
+    return SG_OK;
+}
+
+}  // extern "C"
+#pragma GCC pop_options

@@ -171,6 +171,10 @@ SIGNATURES = {
     "sg_emd_match_impl": (c_int, [_P, _P, _L, _L, _D, _P, _P, _P, _P, _I, _I, _P]),
     "sg_emd_matrix_workspace_bytes": (_Z, [_L, _L, _L]),
     "sg_emd_matrix": (c_int, [_P, _P, _L, _L, _L, _D, _I, _P, _P, _P, _Z, _P]),
+    "sg_meshsdf_distance_workspace_bytes": (_Z, [_L, _L, _L]),
+    "sg_meshsdf_distance": (c_int, [_P, _P, _L, _L, _P, _L, _P, _P, _P, _P, _Z, _P]),
+    "sg_meshsdf_distance_impl": (c_int, [_P, _P, _L, _L, _P, _L, _P, _P, _P, _P, _Z, _I, _P, _P]),
+    "sg_meshsdf_sign": (c_int, [_P, _L, _L, _P, _P, _I, _I, _F, _P, _P, _P, _P]),
     "sg_raster_setup": (c_int, [_P, _P, _L, _L, _P, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P]),
     "sg_raster_scan": (c_int, [_P, _L, _P, _P, _P, _P, _P]),
     "sg_raster_fill": (c_int, [_P, _P, _P, _L, _L, _I, _I, _P, _P, _P, _L, _P]),
