@@ -292,6 +292,34 @@ int sg_sdfnet_bwd_finish(const float* dz, const float* bias_partials, long ldn, 
                          const int64_t* seg_off, long nseg, float* t1, float* t5, void* workspace, size_t workspace_bytes,
                          unsigned* tickets, hipStream_t stream);
 
+/* ---- K7c: latent codes of unseen shapes — the loss and its latent-only gradient with the weights frozen (serves
+ * shapegan_amd/reconstruct.py fit_latent_codes and SDFNet.latent_loss_and_grad; the reference has no encoder and never wrote the
+ * fit: create_plot.py's sdf_net_reconstruction only renders training codes).  Additions to ABI 8, backward compatible.
+ * Shape s owns the points [seg_off[s], seg_off[s+1]) of points [*][3] / target [*] (n_s of them, n_s >= 1) and uses
+ * m_s = n_s (win_count <= 0) or min(win_count, n_s) of them: used point i < m_s is seg_off[s] + (win_start + i) mod n_s.
+ * Tiles of SG_SDFNET_LATENT_TILE used points never straddle shapes: shape s has ceil(m_s / TILE) of them, laid end to end in
+ * shape order; tiles [T][2] (int32: shape, first used point i of the tile) and tile_off [S+1] (int64: shape s owns the tiles
+ * [tile_off[s], tile_off[s+1])) are built by the caller once per fit.
+ * sg_sdfnet_latent_grad: one launch; per tile the forward of sg_sdfnet_fwd (per-shape mode, zb1 / zb5 [S][256] of
+ *   sg_sdfnet_shape_bias, packed with kin_used = 3; bit for bit), out = tanh(v), d = out - clamp(target, +-cutoff),
+ *   dz8 = sign(d) (1 - out^2) / m_s with sign(0) = 0, and the backward chain through the transposed packs with ReLU' from sign words
+ *   that never leave the chip.  partials [T][SG_SDFNET_LATENT_PARTIAL_ROW]: floats [0, 256) the tile's row sums of dZ1, [256, 512)
+ *   of dZ5, float 512 its sum of |d|; every row is written in full.  A shape's rows do not depend on the other shapes of the call.
+ *   SG_ERR_ARG: nshapes < 1, win_start < 0, ntiles < 1 (an empty shape is refused where seg_off can be read: by the twin, and by
+ *   the caller that builds the tile table).
+ * sg_sdfnet_latent_reduce: t1 / t5 [256][nshapes] (the layout sg_sdfnet_shape_bias_bwd takes: dW1 = dW5 = NULL, gz, reg_scale =
+ *   2 sigma / L give the gradient of the objective with sigma mean_k z_k^2) and loss [nshapes] = sum |d| / m_s; a shape's tiles
+ *   are added in tile order in double: deterministic. */
+#ifndef SG_SDFNET_LATENT_TILE
+#define SG_SDFNET_LATENT_TILE 32
+#endif
+#define SG_SDFNET_LATENT_PARTIAL_ROW 513 /* 2 * 256 + 1 */
+int sg_sdfnet_latent_grad(const float* points, const float* target, const int64_t* seg_off, long nshapes, const float* zb1,
+                          const float* zb5, const float* packed, float cutoff, long win_start, long win_count, const int* tiles,
+                          long ntiles, float* partials, hipStream_t stream);
+int sg_sdfnet_latent_reduce(const float* partials, const int64_t* tile_off, const int64_t* seg_off, long nshapes, long win_count,
+                            float* t1, float* t5, float* loss, hipStream_t stream);
+
 /* ---- K7b: the LayerNorm form of the fused MLP — SDFGenerator (model/point_sdf_net.py:49-119) with hidden_channels 256 and
  * num_layers 8: x = relu(LayerNorm(lin_i(x) [+ z_lin(z)])) for i = 0..6 (:104-116), cat([x, pos]) in front of lins.4 (:100), a
  * plain Linear(256, 1) at the end (ABI 8).  The eight Linear layers have the shapes of an SDFNet without latent columns, so the

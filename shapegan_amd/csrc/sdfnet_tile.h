@@ -234,7 +234,9 @@ struct SdfPointIo {
     }
 };
 
-template <int P, bool SHAPE_BIAS, bool TRAIN, bool NORM = false, class Io = SdfPointIo<NORM>>   // TRAIN: `acts` is given (H images + sign masks are written)
+// KEEP: the sign word of every hidden layer (the one TRAIN stores to `acts`, same bit order) is handed to io.keep(layer, words) instead
+// of memory — for a kernel that runs the backward chain of the tile itself (latent_fit.hip).  Off in every other instantiation.
+template <int P, bool SHAPE_BIAS, bool TRAIN, bool NORM = false, class Io = SdfPointIo<NORM>, bool KEEP = false>   // TRAIN: `acts` is given (H images + sign masks are written)
 __device__ __forceinline__ void sdfnet_fwd_tile(const SdfFwdArgs& a, const long p0, const Io& io = Io()) {
     constexpr int NT = P / 32;
     constexpr int LDX = P + 1;
@@ -433,6 +435,15 @@ __device__ __forceinline__ void sdfnet_fwd_tile(const SdfFwdArgs& a, const long 
                 for (int t = 0; t < NT; ++t)
                     __builtin_amdgcn_raw_buffer_store_b16((unsigned short)mk[t], mres, (int)mstore[t], 0, 0);
             }
+        }
+        if constexpr (KEEP) {
+            static_assert(!NORM && !TRAIN, "the kept sign words are those of the plain ReLU form");
+#pragma unroll
+            for (int q = 15; q >= 0; --q)
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+                    asm volatile("v_cmp_lt_f32 vcc, 0, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mk[t]) : "v"(acc[t][q]) : "vcc");
+            io.keep(layer, mk);
         }
         __syncthreads();
     };

@@ -854,6 +854,88 @@ int sg_sdfnet_bwd_finish_cpu(const float* dz, const float* bias_partials, long l
     return SG_OK;
 }
 
+// ---- K7c: loss and latent-only gradient with frozen weights (header: sg_sdfnet_latent_grad / sg_sdfnet_latent_reduce) -------------
+// Per tile of the caller's table: the forward of sg_sdfnet_fwd_cpu point by point (the same `dense` calls in the same order, so a
+// target made by that forward gives d == 0 exactly), the upstream gradient of the header, the chain of sg_sdfnet_bwd_cpu, and the
+// tile's row sums of dZ1 / dZ5 and sum of |d|.
+int sg_sdfnet_latent_grad_cpu(const float* points, const float* target, const int64_t* seg_off, long nshapes, const float* zb1,
+                              const float* zb5, const float* packed, float cutoff, long win_start, long win_count,
+                              const int* tiles, long ntiles, float* partials, void*) {
+    CPU_CHECK(points && target && seg_off && zb1 && zb5 && packed && tiles && partials);
+    CPU_CHECK(nshapes >= 1 && win_start >= 0 && ntiles >= 1 && cutoff >= 0.f);
+    for (long s = 0; s < nshapes; ++s) CPU_CHECK(seg_off[s + 1] - seg_off[s] >= 1);
+    const CpuSdf v = sdf_view(packed, 3);
+    const float* Wt[7] = {nullptr, v.W2, v.W3, v.W4, v.W5x, v.W6, v.W7};
+    const float* bs[7] = {nullptr, v.b + 256, v.b + 512, v.b + 768, nullptr, v.b + 1280, v.b + 1536};
+#pragma omp parallel for schedule(dynamic)
+    for (long t = 0; t < ntiles; ++t) {
+        float* prow = partials + t * SG_SDFNET_LATENT_PARTIAL_ROW;
+        for (int e = 0; e < SG_SDFNET_LATENT_PARTIAL_ROW; ++e) prow[e] = 0.f;
+        const long s = tiles[2 * t], i0 = tiles[2 * t + 1];
+        if (s < 0 || s >= nshapes || i0 < 0) continue;
+        const long beg = seg_off[s], n = seg_off[s + 1] - beg;
+        const long m = win_count <= 0 || win_count > n ? n : win_count;
+        long cnt = m - i0;
+        if (cnt > SG_SDFNET_LATENT_TILE) cnt = SG_SDFNET_LATENT_TILE;
+        double s1[256] = {0}, s5[256] = {0};
+        float labs = 0.f;
+        for (long i = 0; i < cnt; ++i) {
+            const long pi = beg + (win_start + i0 + i) % n;
+            float h[7][256], g[256], gn[256];
+            const float* x = points + pi * 3;
+            dense(v.W1k, 3, x, zb1 + s * 256, h[0], true, false);
+            for (int l = 1; l < 7; ++l) {
+                if (l == 4) {
+                    dense(v.W5x, 256, h[3], zb5 + s * 256, h[4], false, false);
+                    dense(v.W5i, 3, x, nullptr, h[4], true, true);
+                } else {
+                    dense(Wt[l], 256, h[l - 1], bs[l], h[l], true, false);
+                }
+            }
+            float pre = v.b8[0];
+            for (int k = 0; k < 256; ++k) pre += v.w8[k] * h[6][k];
+            const float o = tanhf(pre);
+            const float tg = fminf(fmaxf(target[pi], -cutoff), cutoff);
+            const float d = o - tg;
+            labs += fabsf(d);
+            const float d8 = (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * ((1.f - o * o) / (float)m);
+            for (int r = 0; r < 256; ++r) g[r] = h[6][r] > 0.f ? v.w8[r] * d8 : 0.f;
+            for (int layer = 5; layer >= 0; --layer) {
+                dense_t(Wt[layer + 1], 256, g, gn, false);
+                for (int r = 0; r < 256; ++r) g[r] = h[layer][r] > 0.f ? gn[r] : 0.f;
+                if (layer == 4)
+                    for (int r = 0; r < 256; ++r) s5[r] += g[r];
+            }
+            for (int r = 0; r < 256; ++r) s1[r] += g[r];
+        }
+        for (int r = 0; r < 256; ++r) {
+            prow[r] = (float)s1[r];
+            prow[256 + r] = (float)s5[r];
+        }
+        prow[512] = labs;
+    }
+    return SG_OK;
+}
+int sg_sdfnet_latent_reduce_cpu(const float* partials, const int64_t* tile_off, const int64_t* seg_off, long nshapes, long win_count,
+                                float* t1, float* t5, float* loss, void*) {
+    CPU_CHECK(partials && tile_off && seg_off && t1 && t5 && loss && nshapes >= 1);
+#pragma omp parallel for schedule(static)
+    for (long s = 0; s < nshapes; ++s) {
+        const long ta = tile_off[s], tb = tile_off[s + 1];
+        for (int r = 0; r < 512; ++r) {
+            double a = 0;
+            for (long t = ta; t < tb; ++t) a += partials[t * SG_SDFNET_LATENT_PARTIAL_ROW + r];
+            (r < 256 ? t1 : t5)[(long)(r & 255) * nshapes + s] = (float)a;
+        }
+        double l = 0;
+        for (long t = ta; t < tb; ++t) l += partials[t * SG_SDFNET_LATENT_PARTIAL_ROW + 512];
+        const long n = seg_off[s + 1] - seg_off[s];
+        const long m = win_count <= 0 || win_count > n ? n : win_count;
+        loss[s] = (float)(l / (double)(m > 0 ? m : 1));
+    }
+    return SG_OK;
+}
+
 // ---- K7b: the LayerNorm form (SDFGenerator, model/point_sdf_net.py:49-119; header: sg_sdfgen_*) ------------------------------------
 // The LayerNorm vectors sit where sg_sdfgen_packed_norm_offset (host code of the HIP library, shared) says: float offsets of the
 // HIP image's layout for kin_used = 3, far behind this twin's own 462 337 floats.

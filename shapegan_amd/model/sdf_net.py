@@ -85,6 +85,23 @@ class SDFNet(SavableModule):
         return ops.SDFNetShapes.apply(self._pack_shapes, points, latent_table, 0, shape_index, segment_offsets, latent_reg,
                                       torch.is_grad_enabled(), *self._params())
 
+    def latent_loss_and_grad(self, points, sdf, latent_table, segment_offsets, cutoff=0.1, sigma=0.0, window=None, fused=True):
+        """The objective a latent code is fitted with, and its gradient, the weights frozen: points [N,3] grouped by shape, sdf [N],
+        latent_table [S,L], segment_offsets [S+1] (int64) ->
+            loss [S]   = mean_p |SDFNet(x_p, z_s) - clamp(sdf_p, +-cutoff)|   (the data term only)
+            grad [S,L] = d/dz_s (loss_s + sigma * mean_k z_{s,k}^2).
+        window = (start, count): shape s uses min(count, n_s) of its n_s points (count <= 0: all), the i-th being
+        (start + i) mod n_s.  fused: one launch runs forward, loss and the latent-only backward of a tile (csrc/latent_fit.hip);
+        False composes the same from forward_segments and autograd.  No parameter is touched, no .grad written."""
+        off = ops.check_segments(points, sdf, latent_table, segment_offsets)
+        start, count = (0, 0) if window is None else (int(window[0]), int(window[1]))
+        if start < 0:
+            raise ValueError("the window starts at %d" % start)
+        if fused:
+            fit = ops.LatentFit(self._pack_shapes, self._params(), points, sdf, segment_offsets, off, cutoff)
+            return fit.step(latent_table, start, count, sigma)
+        return ops.latent_step_composed(self._pack_shapes, self._params(), points, sdf, latent_table, off, cutoff, sigma, start, count)
+
     # ---- inference helpers (reference signatures) ----
     def evaluate_in_batches(self, points, latent_code, batch_size=100000, return_cpu_tensor=True):
         """One latent for all points (model/sdf_net.py:63-75).  The fused kernel streams any N in one launch, so
@@ -100,7 +117,8 @@ class SDFNet(SavableModule):
 
     def _helper(self, voxel_resolution, sphere_only):
         key = (voxel_resolution, sphere_only)
-        if key not in sdf_voxelization_helper:
+        # (one grid per resolution, as in the reference; remade when a network on another device asks for it)
+        if key not in sdf_voxelization_helper or sdf_voxelization_helper[key].sample_points.device != self.device:
             sdf_voxelization_helper[key] = SDFVoxelizationHelperData(self.device, voxel_resolution, sphere_only)
         return sdf_voxelization_helper[key]
 

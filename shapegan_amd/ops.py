@@ -1301,6 +1301,157 @@ class SDFNetShapes(Function):
         return (None, dx, gz, None, None, None, None, None) + tuple(grads)
 
 
+# ---- latent codes of unseen shapes: loss and latent-only gradient with the weights frozen (csrc/latent_fit.hip) -------------------
+_LATENT_TILE = 32             # SG_SDFNET_LATENT_TILE
+_LATENT_ROW = 2 * _H + 1      # SG_SDFNET_LATENT_PARTIAL_ROW
+_LATENT_MAX_SHAPES = 6144     # what sg_sdfnet_shape_bias_bwd takes in one call; more shapes go in chunks (shapes are independent)
+
+
+def check_segments(points, sdf, latent_table, segment_offsets):
+    """The argument checks of the latent fit, before anything is launched: returns the run bounds as a host int64 array."""
+    import numpy as np
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points must be [N, 3], got %s" % (tuple(points.shape),))
+    if sdf.dim() != 1 or sdf.shape[0] != points.shape[0]:
+        raise ValueError("sdf must be [N] = [%d], got %s" % (points.shape[0], tuple(sdf.shape)))
+    if latent_table.dim() != 2 or latent_table.shape[1] < 1:
+        raise ValueError("latent_table must be [S, L], got %s" % (tuple(latent_table.shape),))
+    if segment_offsets.dim() != 1 or segment_offsets.dtype != torch.int64 or segment_offsets.numel() < 2:
+        raise ValueError("segment_offsets must be int64 [S + 1] with S >= 1")
+    if segment_offsets.numel() - 1 != latent_table.shape[0]:
+        raise ValueError("latent_table has %d rows for %d shapes" % (latent_table.shape[0], segment_offsets.numel() - 1))
+    off = segment_offsets.detach().cpu().numpy().astype(np.int64)
+    if off[0] < 0 or off[-1] > points.shape[0]:
+        raise ValueError("segment_offsets reach outside the %d points" % points.shape[0])
+    if (np.diff(off) < 1).any():
+        raise ValueError("shape %d has no points" % int(np.argmax(np.diff(off) < 1)))
+    return off
+
+
+class LatentFit(object):
+    """One fit's constants for the fused latent step: the weight image (packed once), the run bounds and, per window length, the tile
+    tables of every chunk of shapes.  step(z, start, count, sigma) -> (loss [S], grad [S, L]): three launches per chunk of shapes
+    (sg_sdfnet_shape_bias, sg_sdfnet_latent_grad, sg_sdfnet_latent_reduce) and sg_sdfnet_shape_bias_bwd for d/dz."""
+
+    def __init__(self, cache, params, points, sdf, segment_offsets, off_host, cutoff):
+        self.params = [f32c(p.detach()) for p in params]
+        self.points, self.sdf = f32c(points.detach()), f32c(sdf.detach())
+        self.seg_off = segment_offsets.contiguous()
+        self.off = off_host
+        self.cutoff = float(cutoff)
+        self.S = len(off_host) - 1
+        self.L = self.params[0].shape[1] - 3
+        self.dev = self.points.device
+        self.packed = cache.get(self.params, self.L, 3)
+        self.plans = {}
+
+    def _plan(self, count):
+        import numpy as np
+        plan = self.plans.get(count)
+        if plan is None:
+            plan = []
+            for a in range(0, self.S, _LATENT_MAX_SHAPES):
+                b = min(self.S, a + _LATENT_MAX_SHAPES)
+                n = np.diff(self.off[a:b + 1])
+                m = n if count <= 0 else np.minimum(n, count)
+                nt = (m + _LATENT_TILE - 1) // _LATENT_TILE
+                tile_off = np.zeros(b - a + 1, dtype=np.int64)
+                tile_off[1:] = np.cumsum(nt)
+                shape = np.repeat(np.arange(b - a, dtype=np.int64), nt)
+                first = (np.arange(tile_off[-1], dtype=np.int64) - tile_off[shape]) * _LATENT_TILE
+                tiles = np.stack([shape, first], axis=1).astype(np.int32)
+                plan.append((a, b, torch.from_numpy(tiles).to(self.dev), torch.from_numpy(tile_off).to(self.dev), int(tile_off[-1])))
+            self.plans[count] = plan
+        return plan
+
+    def step(self, z, start, count, sigma):
+        if start < 0:
+            raise ValueError("the window starts at %d" % start)
+        z = f32c(z.detach())
+        if tuple(z.shape) != (self.S, self.L):
+            raise ValueError("latent_table must be [%d, %d], got %s" % (self.S, self.L, tuple(z.shape)))
+        lib = _lib()
+        w1, b1, w5, b5 = self.params[0], self.params[1], self.params[8], self.params[9]
+        loss = torch.empty(self.S, dtype=torch.float32, device=self.dev)
+        grad = torch.empty((self.S, self.L), dtype=torch.float32, device=self.dev)
+        for a, b, tiles, tile_off, ntiles in self._plan(int(count)):
+            S = b - a
+            zc, so = z[a:b], self.seg_off[a:b + 1]
+            zb1 = torch.empty((S, _H), dtype=torch.float32, device=self.dev)
+            zb5 = torch.empty((S, _H), dtype=torch.float32, device=self.dev)
+            check(lib.sg_sdfnet_shape_bias(ptr(zc), S, self.L, ptr(w1), ptr(b1), ptr(w5), ptr(b5), ptr(zb1), ptr(zb5), stream()),
+                  "sdfnet_shape_bias")
+            part = torch.empty((ntiles, _LATENT_ROW), dtype=torch.float32, device=self.dev)
+            check(lib.sg_sdfnet_latent_grad(ptr(self.points), ptr(self.sdf), ptr(so), S, ptr(zb1), ptr(zb5), ptr(self.packed),
+                                            self.cutoff, int(start), int(count), ptr(tiles), ntiles, ptr(part), stream()),
+                  "sdfnet_latent_grad")
+            t1 = torch.empty((_H, S), dtype=torch.float32, device=self.dev)
+            t5 = torch.empty((_H, S), dtype=torch.float32, device=self.dev)
+            check(lib.sg_sdfnet_latent_reduce(ptr(part), ptr(tile_off), ptr(so), S, int(count), ptr(t1), ptr(t5), ptr(loss[a:b]),
+                                              stream()), "sdfnet_latent_reduce")
+            check(lib.sg_sdfnet_shape_bias_bwd(ptr(t1), ptr(t5), S, ptr(zc), self.L, ptr(w1), ptr(w5), None, None, ptr(grad[a:b]),
+                                               None, 2.0 * float(sigma) / self.L, stream()), "sdfnet_shape_bias_bwd")
+        return loss, grad
+
+
+class LatentFitComposed(object):
+    """The same step from the training kernels: forward_segments on the window's points and autograd with respect to the latent table
+    only (sg_sdfnet_fwd with the activation images, sg_sdfnet_bwd, sg_sdfnet_bwd_finish, the fold's backward).  Like LatentFit it keeps
+    one fit's constants — per window length the shape index of every used point, the run bounds and the counts, on the device —, so a
+    step does no host work beyond its launches.  step(z, start, count, sigma) -> (loss [S], grad [S, L])."""
+
+    def __init__(self, cache, params, points, sdf, off_host, cutoff):
+        self.cache = cache
+        self.params = [p.detach() for p in params]
+        self.points, self.sdf = f32c(points.detach()), f32c(sdf.detach())
+        self.off = off_host
+        self.cutoff = float(cutoff)
+        self.S = len(off_host) - 1
+        self.dev = self.points.device
+        self.plans = {}
+
+    def _plan(self, count):
+        import numpy as np
+        plan = self.plans.get(count)
+        if plan is None:
+            S, dev = self.S, self.dev
+            n = np.diff(self.off)
+            m = n if count <= 0 else np.minimum(n, count)
+            shape = np.repeat(np.arange(S, dtype=np.int64), m)
+            moff = np.zeros(S + 1, dtype=np.int64)
+            moff[1:] = np.cumsum(m)
+            whole = bool((m == n).all() and self.off[0] == 0 and self.off[-1] == self.points.shape[0])
+            plan = dict(sid=torch.from_numpy(shape).to(dev), sid32=torch.from_numpy(shape.astype(np.int32)).to(dev),
+                        seg=torch.from_numpy(moff).to(dev), counts=torch.from_numpy(m.astype(np.float32)).to(dev), whole=whole,
+                        i=torch.from_numpy(np.arange(moff[-1], dtype=np.int64) - moff[shape]).to(dev),
+                        n=torch.from_numpy(n[shape]).to(dev), base=torch.from_numpy(self.off[:-1][shape]).to(dev))
+            self.plans[count] = plan
+        return plan
+
+    def step(self, z, start, count, sigma):
+        if start < 0:
+            raise ValueError("the window starts at %d" % start)
+        p = self._plan(int(count))
+        if p["whole"] and start == 0:
+            pts, tgt = self.points, self.sdf
+        else:
+            idx = p["base"] + (p["i"] + int(start)) % p["n"]
+            pts, tgt = self.points[idx], self.sdf[idx]
+        zz = f32c(z.detach()).clone().requires_grad_(True)
+        with torch.enable_grad():
+            out = SDFNetShapes.apply(self.cache, pts, zz, 0, p["sid32"], p["seg"], None, True, *self.params)
+            d = (out - tgt.clamp(-self.cutoff, self.cutoff)).abs()
+            loss = torch.zeros(self.S, dtype=torch.float32, device=self.dev).index_add_(0, p["sid"], d) / p["counts"]
+            total = loss.sum() + float(sigma) * (zz * zz).mean(dim=1).sum()
+            grad, = torch.autograd.grad(total, zz)
+        return loss.detach(), grad
+
+
+def latent_step_composed(cache, params, points, sdf, z, off_host, cutoff, sigma, start, count):
+    """One composed step without a kept plan (SDFNet.latent_loss_and_grad(fused=False))."""
+    return LatentFitComposed(cache, params, points, sdf, off_host, cutoff).step(z, start, count, sigma)
+
+
 class _GenPackCache(object):
     """MFMA-fragment image of an SDFGenerator's 30 tensors (lins.{0..7}.{weight,bias}, norms.{0..6}.{weight,bias}), rebuilt when a
     parameter changed; one entry per device (see _PackCache)."""

@@ -1,0 +1,164 @@
+"""Encoding unseen shapes with a trained DeepSDF auto-decoder: fit latent codes to SDF samples with the network frozen, then mesh them.
+
+An auto-decoder (model/sdf_net.py, train_sdf_autodecoder.py) has no encoder: the only shapes with a latent code are the rows of the
+training table.  The code of a new shape is the minimiser of
+
+    mean_p |SDFNet(x_p, z) - clamp(sdf_p, +-cutoff)| + sigma * mean_k z_k^2
+
+over z (Park et al., DeepSDF, section 4.2 / eq. 10).  The reference never wrote this step (create_plot.py's sdf_net_reconstruction only renders
+training codes).  fit_latent_codes runs it for a batch of shapes at once — every shape is independent — on the fused kernel of
+csrc/latent_fit.hip (SDFNet.latent_loss_and_grad), with Adam through sg_adam_step; reconstruct_meshes turns codes into a MeshBatch.
+
+    python -m shapegan_amd.reconstruct --net models/sdf_net.to --models DIR --out codes.to [--meshes OUTDIR] [--chamfer]
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+from . import lib as L
+from . import ops
+from .mesh import marching_cubes
+
+
+def _segments(points, sdf, segment_offsets, points_per_shape):
+    """points [N,3] / sdf [N] with runs, from either calling form ([S,P,3] / [S,P] batches, or flat tensors with offsets or a fixed
+    run length)."""
+    if points.dim() == 3:
+        S, P = points.shape[0], points.shape[1]
+        points, sdf = points.reshape(S * P, 3), sdf.reshape(S * P)
+        points_per_shape = P
+    if segment_offsets is None:
+        if not points_per_shape or points.shape[0] % int(points_per_shape):
+            raise ValueError("fit_latent_codes: give segment_offsets, or points_per_shape dividing the %d points" % points.shape[0])
+        segment_offsets = torch.arange(points.shape[0] // int(points_per_shape) + 1, dtype=torch.int64) * int(points_per_shape)
+    return points, sdf, segment_offsets.to(device=points.device, dtype=torch.int64)
+
+
+def fit_latent_codes(sdf_net, points, sdf, segment_offsets=None, points_per_shape=None, iterations=800, lr=5e-3, sigma=0.01, cutoff=0.1,
+                     init=None, points_per_step=None, shuffle=True, seed=0, fused=True):
+    """Latent codes [S,L] of S shapes from their SDF samples, and the data term [S] at those codes (one evaluation over all points).
+
+    points [N,3] / sdf [N] grouped by shape with segment_offsets [S+1] (int64) or a fixed points_per_shape, or batches [S,P,3] /
+    [S,P].  Adam with torch's defaults; init None starts from zeros.  points_per_step: iteration k uses the window
+    (k * points_per_step, points_per_step) of every shape's samples, wrapping around (None: all points every iteration); shuffle
+    permutes every shape's samples once, seeded, on the device, so that the windows are random mini-batches.  The network's
+    parameters are not touched and no .grad of theirs is written.  fused=False runs the same loop on forward_segments + autograd."""
+    points, sdf, seg = _segments(points, sdf, segment_offsets, points_per_shape)
+    points, sdf = L.f32c(points.detach()), L.f32c(sdf.detach())
+    S, Lz, dev = seg.numel() - 1, sdf_net.latent_code_size, points.device
+    z = torch.zeros((S, Lz), dtype=torch.float32, device=dev) if init is None else L.f32c(init.detach().to(dev)).clone()
+    off = ops.check_segments(points, sdf, z, seg)
+    if shuffle and points_per_step:
+        # one permutation per shape: sort random keys inside every run (the shape index is the major key)
+        g = torch.Generator(device=dev).manual_seed(int(seed))
+        sid = torch.repeat_interleave(torch.arange(S, device=dev), (seg[1:] - seg[:-1]))
+        lo, hi = int(off[0]), int(off[-1])
+        order = torch.argsort(sid.double() + torch.rand(hi - lo, generator=g, device=dev, dtype=torch.float64) * 0.5) + lo
+        points, sdf = points.clone(), sdf.clone()
+        points[lo:hi], sdf[lo:hi] = points[order], sdf[order]
+    params = sdf_net._params()
+    count = int(points_per_step) if points_per_step else 0
+    if fused:
+        fit = ops.LatentFit(sdf_net._pack_shapes, params, points, sdf, seg, off, cutoff)
+
+        def step(start, cnt, sg):
+            return fit.step(z, start, cnt, sg)
+    else:
+        composed = ops.LatentFitComposed(sdf_net._pack_shapes, params, points, sdf, off, cutoff)
+
+        def step(start, cnt, sg):
+            return composed.step(z, start, cnt, sg)
+    m, v = torch.zeros_like(z), torch.zeros_like(z)
+    lib = ops._lib()
+    for k in range(int(iterations)):
+        _, grad = step(k * count, count, sigma)
+        ops.check(lib.sg_adam_step(ops.ptr(z), ops.ptr(grad), ops.ptr(m), ops.ptr(v), z.numel(), float(lr), 0.9, 0.999, 1e-8, k + 1, 1.0,
+                                   ops.stream()), "adam_step")
+    loss, _ = step(0, 0, 0.0)
+    return z, loss
+
+
+def reconstruct_meshes(sdf_net, latent_codes, voxel_resolution=64, level=0):
+    """MeshBatch of the level sets of the codes [S,L]: shape s is SDFNet.get_mesh(latent_codes[s], voxel_resolution, level=level), all
+    grids and the marching cubes in batched launches."""
+    codes = latent_codes.detach().reshape(-1, sdf_net.latent_code_size)
+    grids = sdf_net.voxel_grids(codes, voxel_resolution, sphere_only=True)
+    return marching_cubes(grids, level=level, spacing=2 / voxel_resolution, origin=-1, pad=True, pad_value=1.0)
+
+
+def write_obj(path, mesh):
+    with open(path, "w") as fh:
+        for x, y, zc in mesh.vertices:
+            fh.write("v %.7g %.7g %.7g\n" % (x, y, zc))
+        for a, b, c in mesh.faces:
+            fh.write("f %d %d %d\n" % (a + 1, b + 1, c + 1))
+
+
+def main(argv=None):
+    from . import evaluation, prepare
+    from .model.sdf_net import SDFNet
+    ap = argparse.ArgumentParser(description="Fit SDFNet latent codes to the meshes of a directory.")
+    ap.add_argument("--net", required=True, help="state_dict of a trained SDFNet (models/sdf_net.to)")
+    ap.add_argument("--models", required=True, help="directory searched for .obj files")
+    ap.add_argument("--out", required=True, help="where the codes [S,L] are torch.save'd")
+    ap.add_argument("--meshes", default=None, help="directory for one reconstructed .obj per model")
+    ap.add_argument("--chamfer", action="store_true", help="print the Chamfer distance between input and reconstruction")
+    ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--points", type=int, default=30000, help="SDF samples per model")
+    ap.add_argument("--points-per-step", type=int, default=0)
+    ap.add_argument("--iterations", type=int, default=800)
+    ap.add_argument("--lr", type=float, default=5e-3)
+    ap.add_argument("--sigma", type=float, default=0.01)
+    ap.add_argument("--resolution", type=int, default=64)
+    ap.add_argument("--scan-count", type=int, default=50)
+    ap.add_argument("--scan-resolution", type=int, default=1024)
+    ap.add_argument("--chamfer-points", type=int, default=2048)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args(argv)
+
+    dev = torch.device(args.device)
+    state = torch.load(args.net, map_location="cpu")
+    net = SDFNet(latent_code_size=state["layers1.0.weight"].shape[1] - 3, device=args.device)
+    net.load_state_dict(state)
+    L.bump_param_epoch()
+    files = prepare.get_model_files(args.models)
+    if not files:
+        raise SystemExit("no .obj files under %s" % args.models)
+    meshes = []
+    for path in files:
+        v, f = prepare.load_obj(path)
+        meshes.append((prepare.scale_to_unit_sphere(v), f))
+    g = torch.Generator().manual_seed(args.seed)
+    scans = prepare.SurfaceScans(meshes, 1.0, args.scan_count, args.scan_resolution, device=dev)
+    points, sdf, ok = scans.sample_sdf_near_surface(args.points, generator=g)
+    codes, loss = fit_latent_codes(net, points, sdf, iterations=args.iterations, lr=args.lr, sigma=args.sigma,
+                                   points_per_step=args.points_per_step or None, seed=args.seed)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    torch.save(codes.cpu(), args.out)
+    batch = None
+    if args.meshes or args.chamfer:
+        batch = reconstruct_meshes(net, codes, args.resolution)
+    if args.meshes:
+        os.makedirs(args.meshes, exist_ok=True)
+        for i, mesh in enumerate(batch.meshes()):
+            write_obj(os.path.join(args.meshes, "%04d.obj" % i), mesh)
+    chamfer = [None] * len(files)
+    if args.chamfer:
+        n = args.chamfer_points
+        recon, empty = batch.sample_surface(n, generator=g, return_empty=True)
+        from .mesh import Mesh
+        truth = torch.stack([torch.from_numpy(Mesh(v, f).sample(n, generator=g)) for v, f in meshes]).to(dev)
+        d = evaluation.chamfer_distance(truth, recon).cpu()
+        chamfer = [None if int(empty[i]) else float(d[i]) for i in range(len(files))]
+    for i, path in enumerate(files):
+        line = "%s: loss %.6f%s" % (path, float(loss[i]), "" if bool(ok[i]) else " (bad mesh: too little inside)")
+        if args.chamfer:
+            line += ", chamfer %s" % ("n/a (empty reconstruction)" if chamfer[i] is None else "%.6f" % chamfer[i])
+        print(line)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
