@@ -823,6 +823,59 @@ int sg_meshsdf_distance_impl(const float* positions, const int64_t* tri_offsets,
 int sg_meshsdf_sign(const float* points, long S, long Q, const float* depth, const double* vps, int K, int N, float bias,
                     const float* dist2, float* sdf, unsigned char* outside, hipStream_t stream);
 
+/* ---- K17: exact t-SNE of a latent table: joint probabilities, the gradient of the KL divergence, the descent step ------------------
+ * reference: demo_latent_space.py:58-60 (TSNE(n_components=2).fit_transform of all latent codes, the map the traversal walks on) and
+ *            create_plot.py:88-96 (create_tsne_plot: the same embedding for the autoencoder, the auto-decoder and the GAN).  Those go
+ *            through scikit-learn's Barnes-Hut approximation on the host; this is the exact form, whose gradient is one pass over the
+ *            N x N affinities.
+ * All tensors fp32, contiguous; 64-bit indexing throughout.  4 <= N <= SG_TSNE_MAX_POINTS = 65536, where P is 16 GiB; 1 <= D <=
+ * SG_TSNE_MAX_DIMS, 1 <= perplexity < N - 1; beyond: SG_ERR_ARG before any launch, in the library and the twin alike.  Every sum has
+ * a fixed order and there are no floating-point atomics: a repeated call gives the same bits.  The arithmetic of an element exists
+ * once (csrc/tsne_core.h).
+ *
+ * sg_tsne_affinities: X [N][D] -> P [N][N], beta [N], plogp (one double).  Every step works in place in P:
+ *   1. P[i][j] = sum_k (x_ik - x_jk)^2, differences squared and added in increasing k with fmaf (never |a|^2 + |b|^2 - 2ab);
+ *      (a - b)^2 = (b - a)^2, so the distances are symmetric bit for bit.
+ *   2. per row i, m = min_{j != i} P[i][j] and the search for beta: p_j = expf(-beta (P[i][j] - m)) for j != i (f32), sum_p = sum p_j
+ *      and sum_dp = sum (P[i][j] - m) p_j in float64, H = log(sum_p) + beta sum_dp / sum_p; the rule is scikit-learn's
+ *      _binary_search_perplexity: beta = 1 first; H > log(perplexity): lower bound = beta, beta doubles while the upper bound is open
+ *      and becomes the midpoint afterwards; otherwise the mirror image with halving; over when |H - log(perplexity)| <= tol or after
+ *      max_steps evaluations (max_steps >= 1, tol >= 0).  beta[i] is the LAST EVALUATED beta, and the row becomes
+ *      P[i][j] = (float)(p_j / sum_p) at it, P[i][i] = 0.
+ *   3. P[i][j] = P[j][i] = (P[i][j] + P[j][i]) / (float)(2N): one thread owns the pair, the sum commutes: P is exactly symmetric with
+ *      an exactly zero diagonal.
+ *   4. plogp = sum_{P > 0} P log P in float64: rows in float64 in a fixed order, then the rows in a fixed order.
+ *   workspace: N doubles (sg_tsne_affinities_workspace_bytes).
+ *
+ * sg_tsne_gradient: Y [N][2], P [N][N], exaggeration -> grad [N][2] and, when kl is given, kl (one double; plogp, the double of
+ *   sg_tsne_affinities, must be given with it).  With w_ij = 1 / (1 + |y_i - y_j|^2), j != i:
+ *     s_i = sum_j w,  a_i = sum_j P_ij w (y_i - y_j),  r_i = sum_j w^2 (y_i - y_j),  k_i = sum_j P_ij log1p(|y_i - y_j|^2)
+ *   in ONE pass over P (nothing of size N^2 is written, Z is not inside the pair sums); Z = sum_i s_i,
+ *     grad_i = 4 (exaggeration a_i - r_i / Z),   kl = plogp + sum_i k_i + log Z       (always the KL of the un-exaggerated P).
+ *   A row's sums are float partial sums over SG_TSNE_FLUSH pairs flushed into float64; Z and sum k_i are float64 in a fixed order.
+ *   The full matrix is walked (no i < j shortcut): a row's sums belong to one workgroup.  workspace: 6 N + 2 doubles.
+ *
+ * sg_tsne_update: scikit-learn's _gradient_descent step on the 2N elements of Y, velocity, gains (in place):
+ *     gains = velocity grad < 0 ? gains + 0.2 : gains 0.8;  gains = max(gains, min_gain);
+ *     velocity = momentum velocity - lr (gains grad);  Y += velocity        (f32, no contraction).
+ *
+ * sg_tsne_step: sg_tsne_gradient followed by sg_tsne_update in the same launches, bit for bit what the two calls give; grad (and kl, when
+ *   given) are outputs as there.  Nothing synchronises: a loop may queue every iteration. */
+#define SG_TSNE_MAX_POINTS 65536
+#define SG_TSNE_MAX_DIMS 65536
+#define SG_TSNE_FLUSH 16
+size_t sg_tsne_affinities_workspace_bytes(long N);
+int sg_tsne_affinities(const float* X, long N, long D, double perplexity, double tol, int max_steps, float* P, float* beta,
+                       double* plogp, void* workspace, size_t workspace_bytes, hipStream_t stream);
+size_t sg_tsne_gradient_workspace_bytes(long N);
+int sg_tsne_gradient(const float* Y, const float* P, long N, float exaggeration, const double* plogp, float* grad, double* kl,
+                     void* workspace, size_t workspace_bytes, hipStream_t stream);
+int sg_tsne_update(float* Y, float* velocity, float* gains, const float* grad, long N, float momentum, float lr, float min_gain,
+                   hipStream_t stream);
+int sg_tsne_step(float* Y, const float* P, long N, float exaggeration, const double* plogp, float* velocity, float* gains,
+                 float momentum, float lr, float min_gain, float* grad, double* kl, void* workspace, size_t workspace_bytes,
+                 hipStream_t stream);
+
 /* ---- sphere tracing of SDFNet shapes (rendering/raymarching.py:render_image, get_shadows) ----------------------------------
  * S images of the same camera, M = width^2 pixels each; ray r = s * M + pixel.  Rays live in segments with an active list each
  * (active [2][nrays], counts [3][nseg] int32, seg_off [nseg + 1] int64): step `iter` reads list iter & 1 / counts iter % 3 and

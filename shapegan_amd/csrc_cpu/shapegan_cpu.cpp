@@ -2509,3 +2509,138 @@ int sg_meshsdf_sign_cpu(const float* points, long S, long Q, const float* depth,
 
 }  // extern "C"
 #pragma GCC pop_options
+
+// ---- K17: exact t-SNE ------------------------------------------------------------------------------------------------------------
+// The per-element arithmetic is csrc/tsne_core.h, the file csrc/tsne.hip includes.  Here: plain loops over rows (OpenMP), a row's sums
+// as float partial sums over SG_TSNE_FLUSH columns flushed into float64, rows added in increasing index.
+#pragma GCC push_options
+#pragma GCC optimize("fp-contract=off")
+#include "../csrc/tsne_core.h"
+
+extern "C" {
+
+int sg_tsne_affinities_cpu(const float* X, long N, long D, double perplexity, double tol, int max_steps, float* P, float* beta,
+                           double* plogp, void* workspace, size_t workspace_bytes, hipStream_t_) {
+    CPU_CHECK(sg_tsne_sizes_ok(N, D, perplexity));
+    CPU_CHECK(X && P && beta && plogp && workspace && tol >= 0.0 && max_steps >= 1);
+    CPU_CHECK(workspace_bytes >= (size_t)N * sizeof(double));
+    double* rows = (double*)workspace;
+    const double log_perp = log(perplexity);
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < N; ++i)
+        for (long j = 0; j < N; ++j) {
+            float acc = 0.f;
+            for (long k = 0; k < D; ++k) acc = sg_tsne_d2_step(acc, X[i * D + k], X[j * D + k]);
+            P[i * N + j] = acc;
+        }
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < N; ++i) {
+        float* row = P + i * N;
+        float m = INFINITY;
+        for (long j = 0; j < N; ++j)
+            if (j != i) m = fminf(m, row[j]);
+        SgTsneSearch st;
+        sg_tsne_search_init(&st);
+        double sum_p = 1.0;
+        for (int step = 0;; ++step) {
+            double sp = 0.0, sdp = 0.0;
+            for (long j = 0; j < N; ++j)
+                if (j != i) {
+                    const float d = row[j] - m;
+                    const float p = sg_tsne_cond(st.beta, d);
+                    sp += (double)p;
+                    sdp += (double)d * (double)p;
+                }
+            sum_p = sp;
+            if (step + 1 >= max_steps) break;
+            if (sg_tsne_search_next(&st, sg_tsne_entropy(st.beta, sp, sdp) - log_perp, tol)) break;
+        }
+        for (long j = 0; j < N; ++j) row[j] = j == i ? 0.f : (float)((double)sg_tsne_cond(st.beta, row[j] - m) / sum_p);
+        beta[i] = st.beta;
+    }
+    const float two_n = (float)(2 * N);
+#pragma omp parallel for schedule(dynamic, 16)
+    for (long i = 0; i < N; ++i)
+        for (long j = i; j < N; ++j) {      // the pair (i, j), i <= j, is written by this iteration alone
+            const float v = sg_tsne_joint(P[i * N + j], P[j * N + i], two_n);
+            P[i * N + j] = v;
+            P[j * N + i] = v;
+        }
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < N; ++i) {
+        double s = 0.0;
+        for (long j = 0; j < N; ++j) {
+            const float p = P[i * N + j];
+            if (p > 0.f) s += (double)p * log((double)p);
+        }
+        rows[i] = s;
+    }
+    double total = 0.0;
+    for (long i = 0; i < N; ++i) total += rows[i];
+    *plogp = total;
+    return SG_OK;
+}
+
+static void tsne_rows_cpu(const float* Y, const float* P, long N, bool want_k, double* stats) {
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < N; ++i) {
+        double acc[6] = {0, 0, 0, 0, 0, 0};
+        const float yix = Y[2 * i], yiy = Y[2 * i + 1];
+        for (long j0 = 0; j0 < N; j0 += SG_TSNE_FLUSH) {
+            SgTsneAcc a;
+            sg_tsne_acc_zero(&a);
+            const long j1 = std::min<long>(N, j0 + SG_TSNE_FLUSH);
+            if (want_k)
+                for (long j = j0; j < j1; ++j) sg_tsne_pair<true>(&a, yix, yiy, Y[2 * j], Y[2 * j + 1], P[i * N + j], j != i);
+            else
+                for (long j = j0; j < j1; ++j) sg_tsne_pair<false>(&a, yix, yiy, Y[2 * j], Y[2 * j + 1], P[i * N + j], j != i);
+            acc[0] += (double)a.s, acc[1] += (double)a.ax, acc[2] += (double)a.ay;
+            acc[3] += (double)a.rx, acc[4] += (double)a.ry, acc[5] += (double)a.k;
+        }
+        for (int e = 0; e < 6; ++e) stats[i * 6 + e] = acc[e];
+    }
+}
+
+static int tsne_gradient_cpu(float* Y, const float* P, long N, float exaggeration, const double* plogp, float* velocity, float* gains,
+                             float momentum, float lr, float min_gain, bool update, float* grad, double* kl, void* workspace) {
+    double* stats = (double*)workspace;
+    tsne_rows_cpu(Y, P, N, kl != nullptr, stats);
+    double Z = 0.0, K = 0.0;
+    for (long i = 0; i < N; ++i) Z += stats[i * 6], K += stats[i * 6 + 5];
+    stats[6 * N] = Z;
+    if (kl) *kl = *plogp + K + log(Z);
+    for (long i = 0; i < N; ++i)
+        for (int c = 0; c < 2; ++c) {
+            const float g = sg_tsne_grad(stats[i * 6 + 1 + c], stats[i * 6 + 3 + c], Z, exaggeration);
+            grad[2 * i + c] = g;
+            if (update) sg_tsne_update_one(Y + 2 * i + c, velocity + 2 * i + c, gains + 2 * i + c, g, momentum, lr, min_gain);
+        }
+    return SG_OK;
+}
+
+int sg_tsne_gradient_cpu(const float* Y, const float* P, long N, float exaggeration, const double* plogp, float* grad, double* kl,
+                         void* workspace, size_t workspace_bytes, hipStream_t_) {
+    CPU_CHECK(N >= 4 && N <= SG_TSNE_MAX_POINTS && Y && P && grad && workspace);
+    CPU_CHECK(!kl || plogp);
+    CPU_CHECK(workspace_bytes >= ((size_t)6 * N + 2) * sizeof(double));
+    return tsne_gradient_cpu((float*)Y, P, N, exaggeration, plogp, nullptr, nullptr, 0.f, 0.f, 0.f, false, grad, kl, workspace);
+}
+
+int sg_tsne_update_cpu(float* Y, float* velocity, float* gains, const float* grad, long N, float momentum, float lr, float min_gain,
+                       hipStream_t_) {
+    CPU_CHECK(N >= 1 && N <= SG_TSNE_MAX_POINTS && Y && velocity && gains && grad);
+    for (long e = 0; e < 2 * N; ++e) sg_tsne_update_one(Y + e, velocity + e, gains + e, grad[e], momentum, lr, min_gain);
+    return SG_OK;
+}
+
+int sg_tsne_step_cpu(float* Y, const float* P, long N, float exaggeration, const double* plogp, float* velocity, float* gains,
+                     float momentum, float lr, float min_gain, float* grad, double* kl, void* workspace, size_t workspace_bytes,
+                     hipStream_t_) {
+    CPU_CHECK(N >= 4 && N <= SG_TSNE_MAX_POINTS && Y && P && velocity && gains && grad && workspace);
+    CPU_CHECK(!kl || plogp);
+    CPU_CHECK(workspace_bytes >= ((size_t)6 * N + 2) * sizeof(double));
+    return tsne_gradient_cpu(Y, P, N, exaggeration, plogp, velocity, gains, momentum, lr, min_gain, true, grad, kl, workspace);
+}
+
+}  // extern "C"
+#pragma GCC pop_options

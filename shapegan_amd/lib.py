@@ -177,6 +177,12 @@ SIGNATURES = {
     "sg_meshsdf_distance": (c_int, [_P, _P, _L, _L, _P, _L, _P, _P, _P, _P, _Z, _P]),
     "sg_meshsdf_distance_impl": (c_int, [_P, _P, _L, _L, _P, _L, _P, _P, _P, _P, _Z, _I, _P, _P]),
     "sg_meshsdf_sign": (c_int, [_P, _L, _L, _P, _P, _I, _I, _F, _P, _P, _P, _P]),
+    "sg_tsne_affinities_workspace_bytes": (_Z, [_L]),
+    "sg_tsne_affinities": (c_int, [_P, _L, _L, _D, _D, _I, _P, _P, _P, _P, _Z, _P]),
+    "sg_tsne_gradient_workspace_bytes": (_Z, [_L]),
+    "sg_tsne_gradient": (c_int, [_P, _P, _L, _F, _P, _P, _P, _P, _Z, _P]),
+    "sg_tsne_update": (c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _P]),
+    "sg_tsne_step": (c_int, [_P, _P, _L, _F, _P, _P, _P, _F, _F, _F, _P, _P, _P, _Z, _P]),
     "sg_raster_setup": (c_int, [_P, _P, _L, _L, _P, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P]),
     "sg_raster_scan": (c_int, [_P, _L, _P, _P, _P, _P, _P]),
     "sg_raster_fill": (c_int, [_P, _P, _P, _L, _L, _I, _I, _P, _P, _P, _L, _P]),

@@ -2512,3 +2512,92 @@ def scatter_max(x, batch, dim_size=None):
     if dim_size is None:
         dim_size = int(batch.max().item()) + 1
     return ScatterMax.apply(x, batch.contiguous(), int(dim_size))[0]
+
+
+# --------------------------------------------------------------------------------------------------------------
+# K17: exact t-SNE (csrc/tsne.hip; shapegan_amd/traversal.py)
+# --------------------------------------------------------------------------------------------------------------
+TSNE_MAX_POINTS = 65536      # SG_TSNE_MAX_POINTS
+
+
+def _tsne_state(name, t, N):
+    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (N, 2):
+        raise ValueError("%s must be a contiguous float32 [%d, 2] tensor, got %s %s" % (name, N, t.dtype, tuple(t.shape)))
+    return t
+
+
+def tsne_affinities(x, perplexity=30.0, tol=1e-5, max_steps=100):
+    """x [N, D] -> (P [N, N] fp32, beta [N] fp32, plogp [1] float64 on the device of x): the joint probabilities of t-SNE at
+    `perplexity`, the precisions the row searches ended at and sum P log P (sg_tsne_affinities)."""
+    if x.dim() != 2:
+        raise ValueError("tsne_affinities: x must be [N, D], got %s" % (tuple(x.shape),))
+    x = f32c(x.detach())
+    N, D, dev = x.shape[0], x.shape[1], x.device
+    lib = _lib()
+    P = torch.empty((N, N), dtype=torch.float32, device=dev)
+    beta = torch.empty(N, dtype=torch.float32, device=dev)
+    plogp = torch.empty(1, dtype=torch.float64, device=dev)
+    ws = workspace("tsne_affinities", lib.sg_tsne_affinities_workspace_bytes(N), dev)
+    try:
+        check(lib.sg_tsne_affinities(ptr(x), N, D, float(perplexity), float(tol), int(max_steps), ptr(P), ptr(beta), ptr(plogp), ptr(ws),
+                                     ws.numel(), stream()), "tsne_affinities")
+    finally:
+        L.reset_call_state()
+    return P, beta, plogp
+
+
+def _tsne_common(y, P):
+    N = P.shape[0]
+    if P.dim() != 2 or P.shape[1] != N or P.dtype != torch.float32 or not P.is_contiguous():
+        raise ValueError("P must be a contiguous float32 [N, N] tensor, got %s %s" % (P.dtype, tuple(P.shape)))
+    _tsne_state("y", y, N)
+    return N, y.device
+
+
+def tsne_gradient(y, P, exaggeration=1.0, plogp=None):
+    """grad [N, 2] of the KL divergence at y for exaggeration * P; with plogp (from tsne_affinities) also kl [1] float64, the KL
+    divergence of the un-exaggerated P (sg_tsne_gradient).  Returns grad, or (grad, kl)."""
+    N, dev = _tsne_common(y, P)
+    lib = _lib()
+    grad = torch.empty((N, 2), dtype=torch.float32, device=dev)
+    kl = torch.empty(1, dtype=torch.float64, device=dev) if plogp is not None else None
+    ws = workspace("tsne_gradient", lib.sg_tsne_gradient_workspace_bytes(N), dev)
+    try:
+        check(lib.sg_tsne_gradient(ptr(y), ptr(P), N, float(exaggeration), ptr(plogp), ptr(grad), ptr(kl), ptr(ws), ws.numel(), stream()),
+              "tsne_gradient")
+    finally:
+        L.reset_call_state()
+    return grad if kl is None else (grad, kl)
+
+
+def tsne_update(y, velocity, gains, grad, momentum, lr, min_gain=0.01):
+    """scikit-learn's _gradient_descent step on y, velocity, gains [N, 2], in place (sg_tsne_update)."""
+    N = y.shape[0]
+    for name, t in (("y", y), ("velocity", velocity), ("gains", gains), ("grad", grad)):
+        _tsne_state(name, t, N)
+    try:
+        check(_lib().sg_tsne_update(ptr(y), ptr(velocity), ptr(gains), ptr(grad), N, float(momentum), float(lr), float(min_gain), stream()),
+              "tsne_update")
+    finally:
+        L.reset_call_state()
+
+
+def tsne_step(y, P, velocity, gains, exaggeration, momentum, lr, min_gain=0.01, plogp=None, grad=None, kl=None):
+    """One iteration, in place on y, velocity, gains: the gradient at y, then the descent step (sg_tsne_step), nothing synchronised.
+    Returns grad, or (grad, kl) when plogp is given.  grad / kl: tensors to reuse."""
+    N, dev = _tsne_common(y, P)
+    _tsne_state("velocity", velocity, N)
+    _tsne_state("gains", gains, N)
+    lib = _lib()
+    if grad is None:
+        grad = torch.empty((N, 2), dtype=torch.float32, device=dev)
+    if plogp is not None and kl is None:
+        kl = torch.empty(1, dtype=torch.float64, device=dev)
+    ws = workspace("tsne_gradient", lib.sg_tsne_gradient_workspace_bytes(N), dev)
+    try:
+        check(lib.sg_tsne_step(ptr(y), ptr(P), N, float(exaggeration), ptr(plogp), ptr(velocity), ptr(gains), float(momentum), float(lr),
+                               float(min_gain), ptr(_tsne_state("grad", grad, N)), ptr(kl if plogp is not None else None), ptr(ws),
+                               ws.numel(), stream()), "tsne_step")
+    finally:
+        L.reset_call_state()
+    return grad if plogp is None else (grad, kl)
