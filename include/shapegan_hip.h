@@ -926,6 +926,63 @@ int sg_raymarch_emit(const unsigned char* status, const float* pos, const float*
 int sg_raymarch_shade(const int* slot, const float* hit_pos, const float* grad, const unsigned char* shadow, const float* dir, long M,
                       long nshapes, long nhits, const double* light, const double* color, unsigned char* image, hipStream_t stream);
 
+/* ---- K18: narrow-band voxel grids: the SDFNet evaluated only in bricks near the surface ---------------------------------------------
+ * reference: SDFNet.get_voxels / get_mesh, model/sdf_net.py:77-112, which evaluate the network at all R^3 lattice points although
+ * marching cubes (K12) reads values only next to the surface.  These entry points are the bookkeeping of an evaluation that runs
+ * sg_sdfnet_fwd on whole bricks near the level set and leaves one constant per brick elsewhere (shapegan_amd/brickgrid.py drives them).
+ *
+ * Lattice: S shapes of R^3 points, flat index x R^2 + y R + z, point (x, y, z) = (axis_x[x], axis_y[y], axis_z[z]) (three fp32
+ * tables [R]).  mask (optional): [R^3] bytes shared by all shapes; a point whose byte is 0 is left out: its value is 1 whatever
+ * the network says.  Bricks: B^3 points, B in {4, 8, 16}, R a multiple of B (anything else: SG_ERR_ARG before any launch);
+ * nb = (R / B)^3 per shape, brick (bx, by, bz) of shape s has the id s nb + (bx (R / B) + by) (R / B) + bz (int32: S nb < 2^31),
+ * its point (lx, ly, lz) the local index lx B^2 + ly B + lz, its corner n the local point ((n >> 2) & 1, (n >> 1) & 1, n & 1) (B - 1).
+ * A value v is INSIDE when v < level (K12's test).
+ *
+ * Every brick is inactive (state 0), active (1) or newly active (2: listed by the last compaction).  At the end every point of
+ * an active brick holds its value (the network's, or 1 where masked: the EVALUATED points) and every point of an inactive brick
+ * the brick's FILL, the value of its corner 0 (masked points hold 1 there too).
+ *
+ * Seed.  sg_brick_points with corners = 1 lists the 8 corners of the bricks (bricks = NULL: of all S nb bricks, in order),
+ * [M][8][3] and the shape of every point; one sg_sdfnet_fwd gives corner_values [S nb][8].  sg_brick_seed writes fill, state = 0,
+ * the whole grid [S][R^3] (fill, or 1 where masked) and flag = 1 for every brick that
+ *   (a) has corners on both sides of the level, or
+ *   (b) has a corner with |v - level| <= band, or
+ *   (c) touches the border of the lattice while pad = 1 and has a corner inside (K12's virtual shell of 1 makes a crossing), or
+ *   (d) has one of its 26 neighbours with a fill on the other side (which flags both).
+ * Continuation, one round: sg_brick_compact turns the flags into the ascending list of newly active bricks (state 2; the
+ * previous ones become 1; the flags are cleared) and its count, by a scan in `workspace`, not by atomics: the list is the same on
+ * every run.  sg_brick_points with corners = 0 lists their points [M][B^3][3] (masked points included, so that a brick is a fixed
+ * block), sg_sdfnet_fwd evaluates them, sg_brick_scatter stores the values (1 where masked) at the bricks' places, and
+ * sg_brick_grow flags every inactive brick N for which some point of a listed brick within Chebyshev distance 2 lattice steps of
+ * a point of N lies on the other side of the level than N's fill (2, not 1: a K12 normal reads the central difference one step
+ * beyond a crossing edge's corners).  The caller repeats until a count is 0 (the driver takes more than 3 R / B rounds for an internal error).
+ *
+ * Guarantee.  At the end every lattice point within Chebyshev distance 2 of an evaluated point that lies on the other side of the
+ * level than anything next to it (another evaluated point, or the fill of an inactive brick within that distance) is itself
+ * evaluated, and no two adjacent inactive bricks have fills on different sides.  sg_sdfnet_fwd gives a point the same bits wherever
+ * it stands in a launch, so the evaluated values are those of the dense grid.  It follows that a crossing edge of the dense grid
+ * between two evaluated points has its whole neighbourhood evaluated (the corners of its cells and the points K12's normals read),
+ * that the surface component through it is followed to its end, and that the narrow-band grid has no crossing the dense grid lacks:
+ * K12 of the narrow-band grid is EXACTLY K12 of the dense grid, vertices, normals and faces, except for the surface components of
+ * the dense mesh that have no crossing edge between two evaluated points.  Those are pieces whose own lattice points (the inside of
+ * a floater, the outside of a bubble) all lie in inactive bricks, on the other side than the brick's fill, and which no brick corner
+ * came within `band` of: smaller than a brick.  Such a piece is absent as a whole; the surface is never open at a brick border.
+ * band >= 0; the driver's default is the largest distance from a brick point to its nearest corner, sqrt(3) (B - 1) / 2 lattice
+ * steps, times a Lipschitz bound of the field.
+ *
+ * Lists are written up to their count only; the grid is written in full by sg_brick_seed. */
+size_t sg_brick_compact_workspace_bytes(long S, int R, int B);
+int sg_brick_points(const int* bricks, long M, int corners, long S, int R, int B, const float* axis_x, const float* axis_y,
+                    const float* axis_z, float* points, int* shape_index, hipStream_t stream);
+int sg_brick_seed(const float* corner_values, const unsigned char* mask, long S, int R, int B, float level, float band, int pad,
+                  int* state, float* fill, int* flag, float* grid, hipStream_t stream);
+int sg_brick_compact(int* state, int* flag, long S, int R, int B, int* list, int* count, void* workspace, size_t workspace_bytes,
+                     hipStream_t stream);
+int sg_brick_scatter(const float* values, const int* bricks, long M, const unsigned char* mask, long S, int R, int B, float* grid,
+                     hipStream_t stream);
+int sg_brick_grow(const int* bricks, long M, const float* grid, const int* state, const float* fill, long S, int R, int B, float level,
+                  int* flag, hipStream_t stream);
+
 /* ---- data-parallel gradient exchange: libshapegan_comm.so ----------------------------------------------
  * reference: nn.DataParallel's gradient reduce-add, train_hybrid_progressive_gan.py:62-68.  One process per GPU; one
  * ncclAllReduce(sum, fp32) of a slice of the flat gradient buffer per call, on the communicator's own stream, ordered after

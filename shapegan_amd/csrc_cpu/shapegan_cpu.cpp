@@ -2644,3 +2644,139 @@ int sg_tsne_step_cpu(float* Y, const float* P, long N, float exaggeration, const
 
 }  // extern "C"
 #pragma GCC pop_options
+
+// ---- K18: narrow-band voxel grids (csrc/brickgrid.hip) --------------------------------------------------------------------------------
+// The integer and side-of-level arithmetic is csrc/brickgrid_core.h, the file the HIP kernels include.  Here: plain walks over the
+// bricks in ascending order (which is the order the HIP scan produces).
+#include "../csrc/brickgrid_core.h"
+
+extern "C" {
+
+int sg_brick_points_cpu(const int* bricks, long M, int corners, long S, int R, int B, const float* axis_x, const float* axis_y,
+                        const float* axis_z, float* points, int* shape_index, hipStream_t_) {
+    SgBrickGeom g;
+    CPU_CHECK(sg_brick_geom(g, S, R, B));
+    CPU_CHECK(axis_x && axis_y && axis_z && points && shape_index && M > 0 && M <= g.S * g.nb && (corners == 0 || corners == 1));
+    CPU_CHECK(bricks || M == g.S * g.nb);
+    const long ppb = corners ? 8 : (long)B * B * B;
+#pragma omp parallel for schedule(static)
+    for (long j = 0; j < M; ++j) {
+        const long brick = bricks ? (long)bricks[j] : j;
+        if (brick < 0 || brick >= g.S * g.nb) continue;
+        long s;
+        int bx, by, bz;
+        sg_brick_decode(g, brick, s, bx, by, bz);
+        for (int l = 0; l < ppb; ++l) {
+            int lx, ly, lz;
+            if (corners) {
+                sg_brick_corner_local(g, l, lx, ly, lz);
+            } else {
+                lx = l / (B * B);
+                ly = (l / B) % B;
+                lz = l % B;
+            }
+            const long i = j * ppb + l;
+            points[i * 3] = axis_x[bx * B + lx];
+            points[i * 3 + 1] = axis_y[by * B + ly];
+            points[i * 3 + 2] = axis_z[bz * B + lz];
+            shape_index[i] = (int)s;
+        }
+    }
+    return SG_OK;
+}
+
+int sg_brick_seed_cpu(const float* corner_values, const unsigned char* mask, long S, int R, int B, float level, float band, int pad,
+                      int* state, float* fill, int* flag, float* grid, hipStream_t_) {
+    SgBrickGeom g;
+    CPU_CHECK(sg_brick_geom(g, S, R, B));
+    CPU_CHECK(corner_values && state && fill && flag && grid && band >= 0.f && (pad == 0 || pad == 1) && S <= 65535);
+    const long cells = (long)R * R * R;
+#pragma omp parallel for schedule(static)
+    for (long brick = 0; brick < g.S * g.nb; ++brick) {
+        long s;
+        int bx, by, bz;
+        sg_brick_decode(g, brick, s, bx, by, bz);
+        float f;
+        flag[brick] = sg_brick_seed_test(g, corner_values, mask, s, bx, by, bz, level, band, pad, &f) ? 1 : 0;
+        fill[brick] = f;
+        state[brick] = 0;
+    }
+#pragma omp parallel for schedule(static)
+    for (long brick = 0; brick < g.S * g.nb; ++brick) {
+        long s;
+        int bx, by, bz;
+        sg_brick_decode(g, brick, s, bx, by, bz);
+        for (int l = 0; l < B * B * B; ++l) {
+            const long p = sg_brick_lattice(g, bx, by, bz, l / (B * B), (l / B) % B, l % B);
+            grid[s * cells + p] = (mask && !mask[p]) ? 1.f : fill[brick];
+        }
+    }
+    return SG_OK;
+}
+
+int sg_brick_compact_cpu(int* state, int* flag, long S, int R, int B, int* list, int* count, void* workspace, size_t, hipStream_t_) {
+    SgBrickGeom g;
+    CPU_CHECK(sg_brick_geom(g, S, R, B));
+    CPU_CHECK(state && flag && list && count && workspace);
+    int n = 0;
+    for (long i = 0; i < g.S * g.nb; ++i) {
+        if (flag[i]) {
+            list[n++] = (int)i;
+            state[i] = 2;
+            flag[i] = 0;
+        } else if (state[i] == 2) {
+            state[i] = 1;
+        }
+    }
+    *count = n;
+    return SG_OK;
+}
+
+int sg_brick_scatter_cpu(const float* values, const int* bricks, long M, const unsigned char* mask, long S, int R, int B, float* grid,
+                         hipStream_t_) {
+    SgBrickGeom g;
+    CPU_CHECK(sg_brick_geom(g, S, R, B));
+    CPU_CHECK(values && bricks && grid && M > 0 && M <= g.S * g.nb);
+    const long cells = (long)R * R * R, ppb = (long)B * B * B;
+#pragma omp parallel for schedule(static)
+    for (long j = 0; j < M; ++j) {
+        const long brick = bricks[j];
+        if (brick < 0 || brick >= g.S * g.nb) continue;
+        long s;
+        int bx, by, bz;
+        sg_brick_decode(g, brick, s, bx, by, bz);
+        for (int l = 0; l < ppb; ++l) {
+            const long p = sg_brick_lattice(g, bx, by, bz, l / (B * B), (l / B) % B, l % B);
+            grid[s * cells + p] = (mask && !mask[p]) ? 1.f : values[j * ppb + l];
+        }
+    }
+    return SG_OK;
+}
+
+int sg_brick_grow_cpu(const int* bricks, long M, const float* grid, const int* state, const float* fill, long S, int R, int B, float level,
+                      int* flag, hipStream_t_) {
+    SgBrickGeom g;
+    CPU_CHECK(sg_brick_geom(g, S, R, B));
+    CPU_CHECK(bricks && grid && state && fill && flag && M > 0 && M <= g.S * g.nb);
+    const long cells = (long)R * R * R;
+    for (long j = 0; j < M; ++j) {
+        const long brick = bricks[j];
+        if (brick < 0 || brick >= g.S * g.nb) continue;
+        long s;
+        int bx, by, bz;
+        sg_brick_decode(g, brick, s, bx, by, bz);
+        unsigned in_mask = 0, out_mask = 0;
+        for (int l = 0; l < B * B * B; ++l) {
+            const int lx = l / (B * B), ly = (l / B) % B, lz = l % B;
+            const unsigned m = sg_brick_region_mask(B, lx, ly, lz);
+            if (sg_brick_inside(grid[s * cells + sg_brick_lattice(g, bx, by, bz, lx, ly, lz)], level))
+                in_mask |= m;
+            else
+                out_mask |= m;
+        }
+        for (int d = 0; d < 27; ++d) sg_brick_grow_apply(g, state, fill, flag, brick, d, in_mask, out_mask, level);
+    }
+    return SG_OK;
+}
+
+}  // extern "C"

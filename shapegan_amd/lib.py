@@ -196,6 +196,12 @@ SIGNATURES = {
     "sg_raymarch_classify": (c_int, [_P, _P, _P, _L, _L, _I, _F, _P, _P, _P, _P, _Z, _P]),
     "sg_raymarch_emit": (c_int, [_P, _P, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "sg_raymarch_shade": (c_int, [_P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P]),
+    "sg_brick_compact_workspace_bytes": (_Z, [_L, _I, _I]),
+    "sg_brick_points": (c_int, [_P, _L, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "sg_brick_seed": (c_int, [_P, _P, _L, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P]),
+    "sg_brick_compact": (c_int, [_P, _P, _L, _I, _I, _P, _P, _P, _Z, _P]),
+    "sg_brick_scatter": (c_int, [_P, _P, _L, _P, _L, _I, _I, _P, _P]),
+    "sg_brick_grow": (c_int, [_P, _L, _P, _P, _P, _L, _I, _I, _F, _P, _P]),
 }
 
 # libshapegan_comm.so (RCCL gradient exchange; loaded only by data-parallel runs that ask for it)

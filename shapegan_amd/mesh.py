@@ -16,6 +16,8 @@ Host synchronisation: marching_cubes reads the two totals back from the device O
 the int32 limits) between the counting and the emitting launches, to size its outputs.  Meshing is therefore not meant for graph
 capture.  Sampling does not synchronise.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -73,6 +75,66 @@ class Mesh(object):
         to = torch.tensor([0, f.shape[0]], dtype=torch.int64)
         u = torch.rand((1, int(count), 3), generator=generator)
         return sample_packed(v, f, vo, to, u)[0][0].numpy()
+
+    def apply_transform(self, matrix):
+        """trimesh.Trimesh.apply_transform: vertices through the homogeneous 4x4 `matrix`; the normals through its 3x3 part, made
+        unit length again; the winding reversed when that part mirrors.  In place; returns self."""
+        m = np.asarray(matrix, dtype=np.float64)
+        if m.shape != (4, 4):
+            raise ValueError("apply_transform: expected a 4x4 matrix, got %s" % (m.shape,))
+        v = self.vertices.astype(np.float64) @ m[:3, :3].T + m[:3, 3]
+        self.vertices = np.ascontiguousarray(v, dtype=np.float32)
+        if self.vertex_normals is not None:
+            n = self.vertex_normals.astype(np.float64) @ m[:3, :3].T
+            length = np.linalg.norm(n, axis=1, keepdims=True)
+            self.vertex_normals = np.ascontiguousarray(np.divide(n, length, out=np.zeros_like(n), where=length > 0), dtype=np.float32)
+        if np.linalg.det(m[:3, :3]) < 0:
+            self.faces = np.ascontiguousarray(self.faces[:, ::-1])
+        return self
+
+    def apply_translation(self, translation):
+        """trimesh.Trimesh.apply_translation: vertices += translation [3].  In place; returns self."""
+        t = np.asarray(translation, dtype=np.float64).reshape(3)
+        self.vertices = np.ascontiguousarray(self.vertices.astype(np.float64) + t, dtype=np.float32)
+        return self
+
+    def export(self, path):
+        """Writes the mesh by the extension of `path`: .obj (text; v, vn and f a//a lines, 9 significant digits, so float32 reads
+        back exactly), .stl (binary: per triangle its face normal and its three corners, unwelded) or .ply (binary little endian:
+        x y z [nx ny nz] per vertex, one uchar-counted int32 index list per face)."""
+        ext = os.path.splitext(str(path))[1].lower()
+        v, f, n = self.vertices, self.faces, self.vertex_normals
+        if ext == ".obj":
+            with open(path, "w") as fh:
+                fh.writelines("v %.9g %.9g %.9g\n" % tuple(r) for r in v.tolist())
+                if n is not None:
+                    fh.writelines("vn %.9g %.9g %.9g\n" % tuple(r) for r in n.tolist())
+                pattern = "f %d//%d %d//%d %d//%d\n" if n is not None else "f %d %d %d\n"
+                rep = 2 if n is not None else 1
+                fh.writelines(pattern % tuple(np.repeat(r, rep)) for r in (f + 1).tolist())
+        elif ext == ".stl":
+            rec = np.zeros(f.shape[0], dtype=[("normal", "<f4", 3), ("corners", "<f4", (3, 3)), ("attr", "<u2")])
+            rec["normal"] = self.face_normals.astype(np.float32) if f.shape[0] else 0
+            rec["corners"] = v[f]
+            with open(path, "wb") as fh:
+                fh.write(b"shapegan_amd binary STL".ljust(80, b" "))
+                fh.write(np.uint32(f.shape[0]).tobytes())
+                fh.write(rec.tobytes())
+        elif ext == ".ply":
+            props = "".join("property float %s\n" % c for c in (("x", "y", "z") + (("nx", "ny", "nz") if n is not None else ())))
+            head = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n%selement face %d\n"
+                    "property list uchar int vertex_indices\nend_header\n" % (v.shape[0], props, f.shape[0]))
+            vert = v if n is None else np.concatenate([v, n], axis=1)
+            rec = np.zeros(f.shape[0], dtype=[("count", "u1"), ("index", "<i4", 3)])
+            rec["count"] = 3
+            rec["index"] = f
+            with open(path, "wb") as fh:
+                fh.write(head.encode("ascii"))
+                fh.write(np.ascontiguousarray(vert, dtype="<f4").tobytes())
+                fh.write(rec.tobytes())
+        else:
+            raise ValueError("export: unknown mesh format %r (.obj, .stl and .ply are written)" % ext)
+        return path
 
     def to_trimesh(self):
         import trimesh

@@ -9,6 +9,7 @@ reference's `if '...' in sys.argv` script blocks (file I/O, pyrender) are not po
 import numpy as np
 import torch
 
+from .brickgrid import options as narrow_band_options
 from .mesh import marching_cubes, max_shapes_per_call
 from .model import LATENT_CODE_SIZE
 from .util import device, standard_normal_distribution
@@ -43,9 +44,13 @@ def shapes_per_chunk(voxel_resolution, padded_grid):
     return max(1, min(max_shapes_per_call((g, g, g), pad=True), _MAX_GRID_POINTS // voxel_resolution ** 3))
 
 
-def sample_point_clouds(sdf_net, sample_count, point_cloud_size, voxel_resolution=128, rescale='half_unit_sphere', latent_codes=None):
+def sample_point_clouds(sdf_net, sample_count, point_cloud_size, voxel_resolution=128, rescale='half_unit_sphere', latent_codes=None,
+                        narrow_band=False, generator=None):
     """get_uniform_surface_points(z, point_cloud_size, voxel_resolution, sphere_only=False, level=LEVEL) + rescale for
-    `sample_count` latent codes (standard normal when None), in chunks of shapes_per_chunk(voxel_resolution, True)."""
+    `sample_count` latent codes (standard normal when None), in chunks of shapes_per_chunk(voxel_resolution, True).
+    narrow_band: the grids come from the brick path of SDFNet.voxel_grids, built for LEVEL (True, or a dict of its
+    arguments brick / band / lipschitz; voxel_resolution a multiple of the brick).
+    generator: the torch.Generator of the surface samples (default: the device's own)."""
     result = np.zeros((sample_count, point_cloud_size, 3))
     if latent_codes is None:
         latent_codes = standard_normal_distribution.sample((sample_count, LATENT_CODE_SIZE)).to(device)
@@ -53,9 +58,9 @@ def sample_point_clouds(sdf_net, sample_count, point_cloud_size, voxel_resolutio
     chunk = shapes_per_chunk(voxel_resolution, True)
     for begin in range(0, sample_count, chunk):
         z = latent_codes[begin:min(begin + chunk, sample_count)]
-        grids = sdf_net.voxel_grids(z, voxel_resolution, sphere_only=False)
+        grids = sdf_net.voxel_grids(z, voxel_resolution, sphere_only=False, level=LEVEL, **narrow_band_options(narrow_band))
         batch = marching_cubes(grids, level=LEVEL, spacing=size / voxel_resolution, origin=-size / 2, pad=True, pad_value=1.0)
-        points, empty = batch.sample_surface(point_cloud_size, return_empty=True)
+        points, empty = batch.sample_surface(point_cloud_size, generator=generator, return_empty=True)
         _collect(result, begin, points, empty, rescale)
     return result
 

@@ -9,6 +9,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..mesh import marching_cubes
+from ..brickgrid import options as narrow_band_options
 from ..util import get_points_in_unit_sphere, get_voxel_coordinates
 from . import LATENT_CODE_SIZE, LATENT_CODES_FILENAME, SavableModule  # noqa: F401  (re-exported: train_sdf_autodecoder.py:13)
 
@@ -154,31 +155,80 @@ class SDFNet(SavableModule):
                                         ops.ptr(sid), ops.ptr(out), None, S * P, S * P, ops.stream()), "sdfnet_fwd")
         return out
 
-    def voxel_grids(self, latent_codes, voxel_resolution, sphere_only=True, pad=True):
+    def voxel_grids(self, latent_codes, voxel_resolution, sphere_only=True, pad=True, narrow_band=False, level=0, brick=4, band=None,
+                    lipschitz=1.0, return_stats=False):
         """get_voxels for a batch of latent codes [S,L], built on the device without a host round trip: [S,R,R,R], or
-        [S,R+2,R+2,R+2] when not sphere_only and pad (the same values as get_voxels, shape by shape)."""
+        [S,R+2,R+2,R+2] when not sphere_only and pad (the same values as get_voxels, shape by shape).
+
+        narrow_band: the network runs only in bricks of brick^3 points (4, 8 or 16; R a multiple of it) near the `level` set; every
+        other brick holds one constant (shapegan_amd/brickgrid.py; the rule and its guarantee: include/shapegan_hip.h, K18).  Same
+        shape, dtype, device and padding; marching cubes of it at `level` is bit for bit that of the dense grid, apart from
+        pieces smaller than a brick that no brick corner came within `band` (default: lipschitz * sqrt(3) (brick - 1) / 2 lattice
+        steps) of.  brick defaults to 4, the one size that was never slower than the dense path in DESIGN 3.15's table (8 is the
+        faster one at 256^3).  The grid is only good for the level it was built for.  Unlike the dense path this one reads a count back from the
+        device once per round of its continuation: it synchronises, as marching_cubes does, and is not meant for graph capture.
+        return_stats: (grids, stats) with stats = {"evaluated_points": per shape, "rounds", "active_bricks": per shape, ...}."""
         helper = self._helper(voxel_resolution, sphere_only)
         R = voxel_resolution
-        d = self.grid_values(latent_codes, helper.sample_points)
-        S = d.shape[0]
-        if sphere_only:
-            if getattr(helper, "unit_sphere_mask_t", None) is None or helper.unit_sphere_mask_t.device != d.device:
-                helper.unit_sphere_mask_t = torch.from_numpy(helper.unit_sphere_mask.reshape(-1)).to(d.device)
-            grids = torch.ones((S, R * R * R), dtype=torch.float32, device=d.device)
-            grids[:, helper.unit_sphere_mask_t] = d
-            return grids.view(S, R, R, R)
-        grids = d.view(S, R, R, R)
-        if pad:
+        if narrow_band:
+            grids, stats = self._narrow_band_grids(latent_codes, helper, R, sphere_only, pad, level, brick, band, lipschitz)
+        else:
+            d = self.grid_values(latent_codes, helper.sample_points)
+            S = d.shape[0]
+            stats = {"resolution": R, "rounds": 0, "active_bricks": None, "evaluated_points": [helper.point_count] * S,
+                     "dense_points": R ** 3}
+            if sphere_only:
+                grids = torch.ones((S, R * R * R), dtype=torch.float32, device=d.device)
+                grids[:, self._mask_tensor(helper, d.device)] = d
+                grids = grids.view(S, R, R, R)
+            else:
+                grids = d.view(S, R, R, R)
+        if not sphere_only and pad:
             grids = torch.nn.functional.pad(grids, (1, 1, 1, 1, 1, 1), mode='constant', value=1.0)
-        return grids
+        return (grids, stats) if return_stats else grids
 
-    def get_mesh(self, latent_code, voxel_resolution=64, sphere_only=True, raise_on_empty=False, level=0):
+    @staticmethod
+    def _mask_tensor(helper, device):
+        if getattr(helper, "unit_sphere_mask_t", None) is None or helper.unit_sphere_mask_t.device != device:
+            helper.unit_sphere_mask_t = torch.from_numpy(helper.unit_sphere_mask.reshape(-1)).to(device)
+        return helper.unit_sphere_mask_t
+
+    def point_evaluator(self, latent_codes):
+        """evaluate(points [N,3], shape_index [N] int32) -> sdf [N] for the codes [S,L]: one sg_sdfnet_fwd launch per call, each point
+        with the folded biases of the shape it names.  A point gets the same bits wherever it stands in a launch (the k order of
+        every layer and the last layer's 16-row groups are fixed per point: csrc/sdfnet_tile.h), and the same as grid_values."""
+        z = ops.f32c(latent_codes.detach().reshape(-1, self.latent_code_size))
+        lib = ops._lib()
+        with torch.no_grad():
+            packed, zb1, zb5 = self._pack_shapes.get_with_fold(self._params(), z)
+
+        def evaluate(points, shape_index):
+            n = points.shape[0]
+            out = torch.empty(n, dtype=torch.float32, device=points.device)
+            ops.check(lib.sg_sdfnet_fwd(ops.ptr(points), 0, None, None, z.shape[1], ops.ptr(packed), 3, ops.ptr(zb1), ops.ptr(zb5), n,
+                                        ops.ptr(shape_index), ops.ptr(out), None, n, n, ops.stream()), "sdfnet_fwd")
+            return out
+        return evaluate, z.shape[0]
+
+    def _narrow_band_grids(self, latent_codes, helper, R, sphere_only, pad, level, brick, band, lipschitz):
+        from ..brickgrid import check_arguments, narrow_band_grids
+        check_arguments(latent_codes.reshape(-1, self.latent_code_size).shape[0], R, brick, None, band)
+        dev = helper.sample_points.device
+        evaluate, S = self.point_evaluator(latent_codes)
+        mask = self._mask_tensor(helper, dev) if sphere_only else None
+        with torch.no_grad():
+            result = narrow_band_grids(evaluate, S, R, dev, brick=brick, level=level, band=band, lipschitz=lipschitz, pad=pad, mask=mask)
+        return result.grid, result.stats
+
+    def get_mesh(self, latent_code, voxel_resolution=64, sphere_only=True, raise_on_empty=False, level=0, narrow_band=False):
         """Marching cubes of the SDF grid (model/sdf_net.py:97-112) on the device: a mesh.Mesh, None when the grid does not cross
         `level` (ValueError with raise_on_empty).  Coordinates are the reference's: the grid of get_voxels padded once more with
         1, spacing 2 / R, shifted by -1 — grid index i lands at (i + 1 + t) 2/R - 1 (sphere_only) or (i + 2 + t) 2/R - 1 (the
-        grid get_voxels pads itself)."""
+        grid get_voxels pads itself).  narrow_band: the grid is built for `level` by the brick path of voxel_grids (True, or a dict
+        of its arguments brick / band / lipschitz)."""
         size = 2
-        grids = self.voxel_grids(latent_code.reshape(1, -1), voxel_resolution, sphere_only=sphere_only)
+        grids = self.voxel_grids(latent_code.reshape(1, -1), voxel_resolution, sphere_only=sphere_only, level=level,
+                                 **narrow_band_options(narrow_band))
         batch = marching_cubes(grids, level=level, spacing=size / voxel_resolution, origin=-size / 2, pad=True, pad_value=1.0)
         if batch.faces.shape[0] == 0:
             if raise_on_empty:
@@ -186,9 +236,11 @@ class SDFNet(SavableModule):
             return None
         return batch.mesh(0)
 
-    def get_uniform_surface_points(self, latent_code, point_count=1000, voxel_resolution=64, sphere_only=True, level=0):
+    def get_uniform_surface_points(self, latent_code, point_count=1000, voxel_resolution=64, sphere_only=True, level=0,
+                                   narrow_band=False):
         """get_mesh(...).sample(point_count) (model/sdf_net.py:114-116): AttributeError when the mesh is empty, as there."""
-        mesh = self.get_mesh(latent_code, voxel_resolution=voxel_resolution, sphere_only=sphere_only, level=level)
+        mesh = self.get_mesh(latent_code, voxel_resolution=voxel_resolution, sphere_only=sphere_only, level=level,
+                             narrow_band=narrow_band)
         return mesh.sample(point_count)
 
     def get_normals(self, latent_code, points):
