@@ -320,6 +320,33 @@ int sg_sdfnet_latent_grad(const float* points, const float* target, const int64_
 int sg_sdfnet_latent_reduce(const float* partials, const int64_t* tile_off, const int64_t* seg_off, long nshapes, long win_count,
                             float* t1, float* t5, float* loss, hipStream_t stream);
 
+/* ---- K7d: points onto a level set of a frozen SDFNet — value, point gradient and Newton steps of a tile in one launch (serves
+ * SDFNet.sdf_and_gradient / project_to_level_set and shapegan_amd/surface.py: exact normals, refined meshes, oriented surface
+ * clouds).  The reference takes normals and surface points from autograd with respect to the points and one first-order step that
+ * assumes |grad f| = 1 (model/sdf_net.py:118-156).  Addition to ABI 8, backward compatible.
+ * points [N][3] are grouped by shape: shape s owns [seg_off[s], seg_off[s+1]).  zb1 / zb5 [S][256] come from sg_sdfnet_shape_bias,
+ * `packed` is packed with kin_used = 3.  tiles [T][2] (int32: shape, first point of the tile within the shape) are built by the
+ * caller as for K7c: SG_SDFNET_PROJECT_TILE points each, never straddling shapes; a row that names nothing (shape outside
+ * [0, nshapes), negative first point, first point beyond the run) is skipped.
+ * Per tile, `iterations + 1` rounds of: the forward of sg_sdfnet_fwd (per-shape mode, bit for bit) at the tile's current points,
+ * out = tanh(v), dz8 = 1 - out^2, the backward chain through the transposed packs with ReLU' from sign words that never leave the
+ * chip, and g = W5[:, 256:259]^T dZ5 + W1[:, 0:3]^T dZ1 per point.  On all rounds but the last the point moves (float32, in this
+ * order; csrc/project_core.h is the one statement both libraries compile):
+ *   d = out - level;  n2 = fma(gx, gx, fma(gy, gy, gz gz));  t = d / n2 (rule 0, Newton) or d / sqrt(n2) (rule 1, the reference's
+ *   step);  s = t g;  len = |t| sqrt(n2);  max_step > 0 and len > max_step: s *= max_step / len;  !(n2 > 0) or a component of s not
+ *   finite: s = 0;  x -= s.
+ * out_points [N][3]: x after `iterations` steps (NULL allowed only with iterations == 0; may alias `points`: a tile reads all its
+ * points before it writes any); value [N]: f at out_points; grad [N][3]: grad f at out_points, unnormalised.  Every element of every
+ * row a tile names is written, ragged last tiles included; nothing is read from the outputs.  With iterations == 0 `value` is
+ * sg_sdfnet_fwd's bit for bit.  A point's outputs do not depend on what else is in the call or where it stands: there is no
+ * reduction across points and the k order of its sums is fixed.
+ * SG_ERR_ARG before any launch: a NULL pointer, nshapes < 1, ntiles < 1 or >= 2^31, iterations outside [0, 64], rule outside {0, 1},
+ * max_step < 0, out_points == NULL with iterations > 0. */
+#define SG_SDFNET_PROJECT_TILE 32
+int sg_sdfnet_project(const float* points, const int64_t* seg_off, long nshapes, const float* zb1, const float* zb5,
+                      const float* packed, float level, int iterations, int rule, float max_step, const int* tiles, long ntiles,
+                      float* out_points, float* value, float* grad, hipStream_t stream);
+
 /* ---- K7b: the LayerNorm form of the fused MLP — SDFGenerator (model/point_sdf_net.py:49-119) with hidden_channels 256 and
  * num_layers 8: x = relu(LayerNorm(lin_i(x) [+ z_lin(z)])) for i = 0..6 (:104-116), cat([x, pos]) in front of lins.4 (:100), a
  * plain Linear(256, 1) at the end (ABI 8).  The eight Linear layers have the shapes of an SDFNet without latent columns, so the

@@ -2780,3 +2780,74 @@ int sg_brick_grow_cpu(const int* bricks, long M, const float* grid, const int* s
 }
 
 }  // extern "C"
+
+// ---- K7d: points onto a level set of a frozen SDFNet (header: sg_sdfnet_project; csrc/sdfnet_project.hip) ----------------------------
+// Per point of every tile the caller's table names: `iterations + 1` rounds of the forward of sg_sdfnet_fwd_cpu (the same `dense`
+// calls in the same order, so iterations == 0 gives its bits), the chain of sg_sdfnet_latent_grad_cpu from dz8 = 1 - out^2, the two
+// products with the point columns of W5 / W1, and between rounds the step of csrc/project_core.h, the file the HIP kernel includes.
+#pragma GCC push_options
+#pragma GCC optimize("fp-contract=off")
+#include "../csrc/project_core.h"
+
+extern "C" {
+
+int sg_sdfnet_project_cpu(const float* points, const int64_t* seg_off, long nshapes, const float* zb1, const float* zb5,
+                          const float* packed, float level, int iterations, int rule, float max_step, const int* tiles, long ntiles,
+                          float* out_points, float* value, float* grad, void*) {
+    CPU_CHECK(points && seg_off && zb1 && zb5 && packed && tiles && value && grad);
+    CPU_CHECK(nshapes >= 1 && ntiles >= 1 && ntiles < (1L << 31));
+    CPU_CHECK(iterations >= 0 && iterations <= 64 && (rule == SG_PROJECT_RULE_NEWTON || rule == SG_PROJECT_RULE_UNIT));
+    CPU_CHECK(max_step >= 0.f && (out_points || iterations == 0));
+    const CpuSdf v = sdf_view(packed, 3);
+    const float* Wt[7] = {nullptr, v.W2, v.W3, v.W4, v.W5x, v.W6, v.W7};
+    const float* bs[7] = {nullptr, v.b + 256, v.b + 512, v.b + 768, nullptr, v.b + 1280, v.b + 1536};
+#pragma omp parallel for schedule(dynamic)
+    for (long t = 0; t < ntiles; ++t) {
+        const long s = tiles[2 * t], i0 = tiles[2 * t + 1];
+        if (s < 0 || s >= nshapes || i0 < 0) continue;
+        const long beg = seg_off[s], n = seg_off[s + 1] - beg;
+        long cnt = n - i0;
+        if (cnt > SG_SDFNET_PROJECT_TILE) cnt = SG_SDFNET_PROJECT_TILE;
+        if (cnt <= 0) continue;
+        float xs[SG_SDFNET_PROJECT_TILE][3];      // (all of the tile's points are read before any is written: out_points may alias)
+        for (long i = 0; i < cnt; ++i)
+            for (int c = 0; c < 3; ++c) xs[i][c] = points[(beg + i0 + i) * 3 + c];
+        for (long i = 0; i < cnt; ++i) {
+            const long pi = beg + i0 + i;
+            float* x = xs[i];
+            float o = 0.f, gp[3] = {0.f, 0.f, 0.f};
+            for (int round = 0; round <= iterations; ++round) {
+                float h[7][256], g[256], gn[256];
+                dense(v.W1k, 3, x, zb1 + s * 256, h[0], true, false);
+                for (int l = 1; l < 7; ++l) {
+                    if (l == 4) {
+                        dense(v.W5x, 256, h[3], zb5 + s * 256, h[4], false, false);
+                        dense(v.W5i, 3, x, nullptr, h[4], true, true);
+                    } else {
+                        dense(Wt[l], 256, h[l - 1], bs[l], h[l], true, false);
+                    }
+                }
+                float pre = v.b8[0];
+                for (int k = 0; k < 256; ++k) pre += v.w8[k] * h[6][k];
+                o = tanhf(pre);
+                const float d8 = 1.f - o * o;
+                for (int r = 0; r < 256; ++r) g[r] = h[6][r] > 0.f ? v.w8[r] * d8 : 0.f;
+                for (int layer = 5; layer >= 0; --layer) {
+                    dense_t(Wt[layer + 1], 256, g, gn, false);
+                    for (int r = 0; r < 256; ++r) g[r] = h[layer][r] > 0.f ? gn[r] : 0.f;
+                    if (layer == 4) dense_t(v.W5i, 3, g, gp, false);      // g is dZ5 here
+                }
+                dense_t(v.W1k, 3, g, gp, true);
+                if (round < iterations) sg_project_step(x, o, gp, level, rule, max_step);
+            }
+            if (out_points)
+                for (int c = 0; c < 3; ++c) out_points[pi * 3 + c] = x[c];
+            value[pi] = o;
+            for (int c = 0; c < 3; ++c) grad[pi * 3 + c] = gp[c];
+        }
+    }
+    return SG_OK;
+}
+
+}  // extern "C"
+#pragma GCC pop_options

@@ -85,6 +85,7 @@ SIGNATURES = {
     "sg_sdfnet_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _I, _L, _L, _P]),
     "sg_sdfnet_latent_grad": (c_int, [_P, _P, _P, _L, _P, _P, _P, _F, _L, _L, _P, _L, _P, _P]),
     "sg_sdfnet_latent_reduce": (c_int, [_P, _P, _P, _L, _L, _P, _P, _P, _P]),
+    "sg_sdfnet_project": (c_int, [_P, _P, _L, _P, _P, _P, _F, _I, _I, _F, _P, _L, _P, _P, _P, _P]),
     "sg_axpby": (c_int, [_P, _P, _P, _L, _F, _F, _P]),
     "sg_reduce_workspace_bytes": (_Z, []),
     "sg_reduce_sum": (c_int, [_P, _P, _L, _F, _P, _Z, _P]),

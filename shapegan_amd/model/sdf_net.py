@@ -103,6 +103,33 @@ class SDFNet(SavableModule):
             return fit.step(latent_table, start, count, sigma)
         return ops.latent_step_composed(self._pack_shapes, self._params(), points, sdf, latent_table, off, cutoff, sigma, start, count)
 
+    def surface_projector(self, latent_codes):
+        """ops.SurfaceProjector for these codes [S,L] (or one code [L]): weight image and latent fold made once, for callers that
+        project many batches of points onto the same shapes."""
+        return ops.SurfaceProjector(self._pack_shapes, self._params(), latent_codes)
+
+    def _project(self, points, latent_codes, segment_offsets, **kw):
+        proj = self.surface_projector(latent_codes)
+        off = ops.check_point_segments(points, proj.S, segment_offsets)
+        seg_off = torch.from_numpy(off).to(points.device) if segment_offsets is None else segment_offsets.contiguous()
+        return proj.run(points, off, seg_off, **kw)
+
+    def sdf_and_gradient(self, points, latent_codes, segment_offsets=None):
+        """points [N,3] grouped by shape, latent_codes [S,L] (or [L]: one shape owns all points) -> (sdf [N], grad [N,3]): the
+        network's value and its unnormalised gradient with respect to the point, from one fused launch (csrc/sdfnet_project.hip)
+        that keeps nothing of the forward but sign bits on the chip.  segment_offsets [S+1] (int64): shape s owns the points
+        [off[s], off[s+1]); None: N = S * pps, equal runs.  No autograd graph is built, no .grad is written, `points` is left as
+        it is (model/sdf_net.py:118-128 takes the same gradient through autograd and normalises it)."""
+        _, sdf, grad = self._project(points, latent_codes, segment_offsets, iterations=0)
+        return sdf, grad
+
+    def project_to_level_set(self, points, latent_codes, segment_offsets=None, level=0.0, iterations=5, rule="newton", max_step=0.1):
+        """Moves every point toward f(., z_s) = level by `iterations` steps along the gradient, all in one launch:
+        rule "newton": x -= (f - level) g / |g|^2; "unit": x -= (f - level) g / |g|, the reference's step, which takes |g| = 1 for
+        granted (model/sdf_net.py:146).  A step longer than max_step is cut to it (0: no limit); where g = 0 the point stays.
+        -> (points [N,3] (new), sdf [N] and grad [N,3] at the returned points).  Arguments as in sdf_and_gradient."""
+        return self._project(points, latent_codes, segment_offsets, level=level, iterations=iterations, rule=rule, max_step=max_step)
+
     # ---- inference helpers (reference signatures) ----
     def evaluate_in_batches(self, points, latent_code, batch_size=100000, return_cpu_tensor=True):
         """One latent for all points (model/sdf_net.py:63-75).  The fused kernel streams any N in one launch, so
@@ -220,12 +247,13 @@ class SDFNet(SavableModule):
             result = narrow_band_grids(evaluate, S, R, dev, brick=brick, level=level, band=band, lipschitz=lipschitz, pad=pad, mask=mask)
         return result.grid, result.stats
 
-    def get_mesh(self, latent_code, voxel_resolution=64, sphere_only=True, raise_on_empty=False, level=0, narrow_band=False):
+    def get_mesh(self, latent_code, voxel_resolution=64, sphere_only=True, raise_on_empty=False, level=0, narrow_band=False, refine=0):
         """Marching cubes of the SDF grid (model/sdf_net.py:97-112) on the device: a mesh.Mesh, None when the grid does not cross
         `level` (ValueError with raise_on_empty).  Coordinates are the reference's: the grid of get_voxels padded once more with
         1, spacing 2 / R, shifted by -1 — grid index i lands at (i + 1 + t) 2/R - 1 (sphere_only) or (i + 2 + t) 2/R - 1 (the
         grid get_voxels pads itself).  narrow_band: the grid is built for `level` by the brick path of voxel_grids (True, or a dict
-        of its arguments brick / band / lipschitz)."""
+        of its arguments brick / band / lipschitz).  refine = K > 0: every vertex is then moved onto the network's own level set by K
+        Newton steps and given its exact normal (surface.refine_meshes, at most a cell diagonal away); 0 is the marching-cubes mesh."""
         size = 2
         grids = self.voxel_grids(latent_code.reshape(1, -1), voxel_resolution, sphere_only=sphere_only, level=level,
                                  **narrow_band_options(narrow_band))
@@ -234,6 +262,10 @@ class SDFNet(SavableModule):
             if raise_on_empty:
                 raise ValueError("Surface level must be within volume data range.")
             return None
+        if refine:
+            from ..surface import cell_diagonal, refine_meshes
+            batch, _ = refine_meshes(self, latent_code.reshape(1, -1), batch, level=level, iterations=int(refine),
+                                     max_move=cell_diagonal(voxel_resolution))
         return batch.mesh(0)
 
     def get_uniform_surface_points(self, latent_code, point_count=1000, voxel_resolution=64, sphere_only=True, level=0,

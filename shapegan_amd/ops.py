@@ -1394,6 +1394,101 @@ class LatentFit(object):
         return loss, grad
 
 
+# ---- points onto a level set: value, point gradient and Newton steps with the weights frozen (csrc/sdfnet_project.hip) -------------
+_PROJECT_TILE = 32                 # SG_SDFNET_PROJECT_TILE
+_PROJECT_MAX_SHAPES = 6144         # shapes per launch, the chunks of LatentFit (shapes are independent: chunked or not, equal bits)
+_PROJECT_MAX_ITERATIONS = 64
+PROJECT_RULES = {"newton": 0, "unit": 1}      # SG_PROJECT_RULE_*: d / |g|^2, or the reference's d / |g| (model/sdf_net.py:146)
+
+
+def check_point_segments(points, nshapes, segment_offsets):
+    """The argument checks of SurfaceProjector, before anything is launched: returns the run bounds as a host int64 array.
+    segment_offsets None: the shapes own equal runs of the points, in order."""
+    import numpy as np
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points must be [N, 3], got %s" % (tuple(points.shape),))
+    N = points.shape[0]
+    if segment_offsets is None:
+        if N < nshapes or N % nshapes != 0:
+            raise ValueError("%d points do not divide among %d shapes: pass segment_offsets" % (N, nshapes))
+        return np.arange(nshapes + 1, dtype=np.int64) * (N // nshapes)
+    if segment_offsets.dim() != 1 or segment_offsets.dtype != torch.int64 or segment_offsets.numel() < 2:
+        raise ValueError("segment_offsets must be int64 [S + 1] with S >= 1")
+    if segment_offsets.numel() - 1 != nshapes:
+        raise ValueError("latent_codes has %d rows for %d shapes" % (nshapes, segment_offsets.numel() - 1))
+    off = segment_offsets.detach().cpu().numpy().astype(np.int64)
+    if off[0] < 0 or off[-1] > N:
+        raise ValueError("segment_offsets reach outside the %d points" % N)
+    if (np.diff(off) < 0).any():
+        raise ValueError("segment_offsets must not decrease")
+    return off
+
+
+class SurfaceProjector(object):
+    """SDF value, point gradient and projection onto a level set for frozen weights and codes: the weight image and the per-shape
+    latent fold are made once, the tile table per call.  run(points, off_host, seg_off, ...) -> (points, value [N], grad [N, 3]):
+    one sg_sdfnet_project launch per chunk of shapes; shape s owns the points [off[s], off[s+1]), an empty run is allowed, and rows
+    outside every run are returned as they came with value and grad 0."""
+
+    def __init__(self, cache, params, latent_codes):
+        self.params = [f32c(p.detach()) for p in params]
+        self.L = self.params[0].shape[1] - 3
+        z = f32c(latent_codes.detach().reshape(-1, self.L))
+        self.S = z.shape[0]
+        self.dev = z.device
+        with torch.no_grad():
+            self.packed, self.zb1, self.zb5 = cache.get_with_fold(self.params, z)
+
+    @staticmethod
+    def _tiles(off, a, b):
+        import numpy as np
+        n = np.diff(off[a:b + 1])
+        nt = (n + _PROJECT_TILE - 1) // _PROJECT_TILE
+        start = np.zeros(b - a + 1, dtype=np.int64)
+        start[1:] = np.cumsum(nt)
+        shape = np.repeat(np.arange(b - a, dtype=np.int64), nt)
+        first = (np.arange(start[-1], dtype=np.int64) - start[shape]) * _PROJECT_TILE
+        return np.stack([shape, first], axis=1).astype(np.int32)
+
+    def run(self, points, off, seg_off, level=0.0, iterations=0, rule="newton", max_step=0.0, out_points=None):
+        """out_points: None (a new tensor when iterations > 0, else `points` itself is returned) or the tensor to write, which may
+        be `points`."""
+        if rule not in PROJECT_RULES:
+            raise ValueError("rule must be one of %s, got %r" % (sorted(PROJECT_RULES), rule))
+        iterations = int(iterations)
+        if iterations < 0 or iterations > _PROJECT_MAX_ITERATIONS:
+            raise ValueError("iterations must be in [0, %d], got %d" % (_PROJECT_MAX_ITERATIONS, iterations))
+        if not float(max_step) >= 0.0:
+            raise ValueError("max_step must be >= 0 (0: no limit), got %r" % (max_step,))
+        if len(off) - 1 != self.S:
+            raise ValueError("latent_codes has %d rows for %d shapes" % (self.S, len(off) - 1))
+        if points.device != self.dev:
+            raise ValueError("points are on %s, the latent codes on %s" % (points.device, self.dev))
+        pts = f32c(points.detach())
+        N = pts.shape[0]
+        covered = int(off[0]) == 0 and int(off[-1]) == N
+        make = torch.empty if covered else torch.zeros
+        value = make(N, dtype=torch.float32, device=self.dev)
+        grad = make((N, 3), dtype=torch.float32, device=self.dev)
+        if iterations == 0:
+            out = None
+        elif out_points is not None:
+            out = out_points
+        else:
+            out = torch.empty_like(pts) if covered else pts.clone()
+        lib = _lib()
+        for a in range(0, self.S, _PROJECT_MAX_SHAPES):
+            b = min(self.S, a + _PROJECT_MAX_SHAPES)
+            tiles = self._tiles(off, a, b)
+            if tiles.shape[0] == 0:
+                continue
+            tiles_d = torch.from_numpy(tiles).to(self.dev)
+            check(lib.sg_sdfnet_project(ptr(pts), ptr(seg_off[a:b + 1]), b - a, ptr(self.zb1[a:b]), ptr(self.zb5[a:b]), ptr(self.packed),
+                                        float(level), iterations, PROJECT_RULES[rule], float(max_step), ptr(tiles_d), tiles.shape[0],
+                                        ptr(out), ptr(value), ptr(grad), stream()), "sdfnet_project")
+        return (points if out is None else out), value, grad
+
+
 class LatentFitComposed(object):
     """The same step from the training kernels: forward_segments on the window's points and autograd with respect to the latent table
     only (sg_sdfnet_fwd with the activation images, sg_sdfnet_bwd, sg_sdfnet_bwd_finish, the fold's backward).  Like LatentFit it keeps

@@ -69,8 +69,14 @@ def _march(lib, packed, zb1, zb5, pos, dir, dir_period, status, active, counts, 
     return it
 
 
-def _render(sdf_net, latent_codes, resolution, threshold, sdf_offset, iterations, ssaa, radius, color, vertical_cutoff):
+NORMALS = ("autograd", "fused")
+
+
+def _render(sdf_net, latent_codes, resolution, threshold, sdf_offset, iterations, ssaa, radius, color, vertical_cutoff,
+            normals="autograd"):
     """Device uint8 images [S, W, W, 3] (W = resolution * ssaa) before crop and resize, and a dict of counters."""
+    if normals not in NORMALS:
+        raise ValueError("normals must be one of %s, got %r" % (NORMALS, normals))
     z = f32c(latent_codes.detach().reshape(-1, sdf_net.latent_code_size))
     S = z.shape[0]
     if S > 128:
@@ -133,8 +139,13 @@ def _render(sdf_net, latent_codes, resolution, threshold, sdf_offset, iterations
     stats["launches"] += 1
 
     # normals: d sdf / d p of every hit in one forward_segments + backward (raymarching.py:130, model/sdf_net.py:118-128)
+    # ("fused": the same gradient from sg_sdfnet_project, which keeps no activation image: 28 B per hit instead of 14.8 KB)
     grad = torch.zeros((max(H, 1), 3), dtype=torch.float32, device=dev)
-    if H > 0:
+    if H > 0 and normals == "fused":
+        proj = ops.SurfaceProjector(sdf_net._pack_shapes, sdf_net._params(), z)
+        _, _, grad = proj.run(hit_pos[:H], offs_h[0].numpy(), offs[0], iterations=0)
+        stats["launches"] += 1
+    elif H > 0:
         pts = hit_pos[:H].detach().clone().requires_grad_(True)
         with torch.enable_grad():
             sdf = sdf_net.forward_segments(pts, z, hit_sid[:H], offs[0])
@@ -166,21 +177,24 @@ def _to_pil(pixels, resolution, ssaa, crop):
 
 
 def render_images(sdf_net, latent_codes, resolution=800, threshold=0.0005, sdf_offset=0, iterations=1000, ssaa=2, radius=1.0,
-                  crop=False, color=(0.8, 0.1, 0.1), vertical_cutoff=None, return_tensor=False):
+                  crop=False, color=(0.8, 0.1, 0.1), vertical_cutoff=None, return_tensor=False, normals="autograd"):
     """render_image for every row of latent_codes [S,L] (S <= 128) in one march: a list of PIL images, or with return_tensor the
-    device uint8 images [S, R ssaa, R ssaa, 3] before crop and resize."""
-    image, _ = _render(sdf_net, latent_codes, resolution, threshold, sdf_offset, iterations, ssaa, radius, color, vertical_cutoff)
+    device uint8 images [S, R ssaa, R ssaa, 3] before crop and resize.  normals: "autograd" — the hits' normals through
+    forward_segments and its backward, as the reference takes them — or "fused": SDFNet.sdf_and_gradient's kernel, the same gradient
+    without the activation images of the training path."""
+    image, _ = _render(sdf_net, latent_codes, resolution, threshold, sdf_offset, iterations, ssaa, radius, color, vertical_cutoff,
+                       normals=normals)
     if return_tensor:
         return image
     return [_to_pil(image[s], resolution, ssaa, crop) for s in range(image.shape[0])]
 
 
 def render_image(sdf_net, latent_code, resolution=800, threshold=0.0005, sdf_offset=0, iterations=1000, ssaa=2, radius=1.0,
-                 crop=False, color=(0.8, 0.1, 0.1), vertical_cutoff=None):
+                 crop=False, color=(0.8, 0.1, 0.1), vertical_cutoff=None, normals="autograd"):
     """raymarching.py:63-182: a PIL image of resolution x resolution (ssaa x ssaa supersampled, LANCZOS-downsampled)."""
     return render_images(sdf_net, latent_code.reshape(1, -1), resolution=resolution, threshold=threshold, sdf_offset=sdf_offset,
                          iterations=iterations, ssaa=ssaa, radius=radius, crop=crop, color=color,
-                         vertical_cutoff=vertical_cutoff)[0]
+                         vertical_cutoff=vertical_cutoff, normals=normals)[0]
 
 
 def get_shadows(sdf_net, points, light_position, latent_code, threshold=0.001, sdf_offset=0, radius=1.0):

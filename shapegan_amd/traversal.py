@@ -230,14 +230,15 @@ def _frame_bytes(voxel_resolution, size, ssaa):
 
 
 def traversal_frames(sdf_net, frame_codes, voxel_resolution=128, level=SURFACE_LEVEL, size=1080, chunk=None, model_color=None,
-                     renderer=None, memory_budget=2 << 30, narrow_band=False):
+                     renderer=None, memory_budget=2 << 30, narrow_band=False, refine=0):
     """Generator of uint8 [size, size, 3] images, one per row of frame_codes [F, L]: frame f is
         viewer.set_mesh(sdf_net.get_mesh(frame_codes[f], voxel_resolution, level=level)); viewer.get_image()
     of a fresh MeshRenderer(size=size), byte for byte, but a chunk of frames goes through voxel_grids -> marching_cubes -> render_meshes
     together.  chunk: frames per pass (default: what memory_budget bytes hold, at most mesh.max_shapes_per_call).  One model_color for
     the whole call (a colour per frame would need a colour per shape in the raster shading kernel).  A code whose grid does not cross
     `level` yields floor and background.  renderer: a MeshRenderer to use (its size wins).  narrow_band: the grids come from the brick
-    path of SDFNet.voxel_grids, built for `level` (True, or a dict of its arguments brick / band / lipschitz; the same frames, byte for byte, whenever the meshes are the same)."""
+    path of SDFNet.voxel_grids, built for `level` (True, or a dict of its arguments brick / band / lipschitz; the same frames, byte for byte, whenever the meshes are the same).
+    refine = K > 0: every frame's mesh is get_mesh(..., refine=K) — vertices on the network's level set, its normals (surface.refine_meshes)."""
     from .rendering import MeshRenderer
     dev = next(sdf_net.parameters()).device
     codes = frame_codes.detach().reshape(-1, sdf_net.latent_code_size).to(device=dev, dtype=torch.float32)
@@ -251,6 +252,9 @@ def traversal_frames(sdf_net, frame_codes, voxel_resolution=128, level=SURFACE_L
         for a in range(0, codes.shape[0], per):
             grids = sdf_net.voxel_grids(codes[a:a + per], R, sphere_only=True, level=level, **narrow_band_options(narrow_band))
             batch = M.marching_cubes(grids, level=level, spacing=2.0 / R, origin=-1.0, pad=True, pad_value=1.0)
+            if refine:
+                from .surface import cell_diagonal, refine_meshes
+                batch, _ = refine_meshes(sdf_net, codes[a:a + per], batch, level=level, iterations=int(refine), max_move=cell_diagonal(R))
             for image in viewer.render_meshes(batch):
                 yield image
 
