@@ -625,6 +625,77 @@ int sg_mesh_sample(const float* vertices, const int64_t* faces, const int64_t* v
                    long F, const float* uniforms, long P, float* out, int* empty, void* workspace, size_t workspace_bytes,
                    hipStream_t stream);
 
+/* ---- K12b: mesh topology: connected components, their statistics, the compaction that keeps some ---------------------------------
+ * reference: what its callers took from trimesh one mesh at a time on the host (Trimesh.split, body_count, is_watertight, volume,
+ *            euler_number) -> a packed batch of meshes labelled, measured and cleaned on the device.
+ * Input: K12's packed meshes.  vertices / normals [V][3] fp32, faces [F][3] int64 local to their shape, vert_offsets / tri_offsets
+ * [S+1] int64, non-decreasing from 0 to V / F; S >= 1; shapes without triangles are legal anywhere, V = 0 and F = 0 too.  V and F
+ * up to 2^31 - 1, beyond that SG_ERR_ARG before any launch, as for S < 1, a negative size, C outside [0, V] or a NULL array that
+ * has elements.  A triangle that names an index outside [0, n_s) of its shape (vert_offsets[s] + n_s <= V) is SKIPPED by every
+ * entry point: it connects nothing, counts nowhere and is dropped by the compaction.
+ *
+ * sg_topo_label.  Two vertices of a shape are connected when a (not skipped) triangle names both; a triangle with a repeated index
+ * still connects its distinct vertices.  vertex_component [V] int32: the number of the vertex's component within its shape, the
+ * components of a shape numbered 0, 1, .. in increasing order of their lowest vertex index; -1 for a vertex no such triangle names.
+ * comp_offsets [S+1] int64: the exclusive sum of the components per shape; component c of shape s is number comp_offsets[s] + c of
+ * the batch, the caller reads the total C = comp_offsets[S] once (as it reads K12's totals).  Method: a union-find over the
+ * triangles (int32 parents, the root of larger index hooked under the smaller by compare-and-swap, paths halved by atomic minimum),
+ * a flatten pass, an exclusive scan of the root flags built as sg_mc_count builds its offsets.  The result is the partition: the
+ * root of a component is its lowest vertex whatever the schedule.  Visibility across the chip's L2s: inside the hooking kernel
+ * every read of a parent is a relaxed agent-scope atomic load or the value an atomic returned, and a root changes only by a
+ * compare-and-swap against the word itself; initialisation, hooking and flattening are separate kernels.  workspace: int32 words
+ * (parents, flags, roots, positions, per-workgroup totals), nothing kept between calls.
+ *
+ * sg_topo_keys: tri_keys [F] int32 = the batch-wide component number of each triangle (2^31 - 1 for a skipped one), edge_keys
+ * [F][3] int64 = per side a -> b of a triangle (v0 -> v1, v1 -> v2, v2 -> v0, GLOBAL vertex indices):
+ *   (min(a, b) << 32) | (max(a, b) << 1) | (1 when a > b),      2^63 - 1 for a == b and for the sides of a skipped triangle.
+ * The caller sorts both (any sort: equal keys are interchangeable; triangles stably, so that a component's triangles keep their
+ * order) and hands sg_topo_stats: tri_order [F] int64 = the triangle indices in sorted key order, seg_offsets [C+1] int64 =
+ * component c owns positions [seg_offsets[c], seg_offsets[c+1]) of tri_order, tile_offsets [C+1] int64 = the exclusive sum of
+ * ceil(n_c / 256) over the components (n_c = its triangles), edge_sorted [F][3] int64 = the sorted edge keys.
+ *
+ * sg_topo_stats, per component (arrays of length C, component c of shape s at comp_offsets[s] + c):
+ *   n_vertices, n_triangles int32;  n_edges int32 = its distinct undirected edges {a, b}, a != b;  n_open int32 = those that are
+ *   not closed, an edge being closed iff exactly one side runs a -> b and exactly one b -> a (so boundaries, non-manifold fans and
+ *   flipped neighbours all count as open);  area, volume float64: the sums over its triangles of
+ *     area_t = |(p1 - p0) x (p2 - p0)| / 2,      volume_t = p0 . (p1 x p2) / 6
+ *   in double from the fp32 corners (csrc/topology_core.h states both with explicit fma, contraction off).  With K12's orientation
+ *   a solid has positive volume, an internal cavity negative.  The sums have ONE order, shared by the GPU and the twin, so both are
+ *   bit-identical between them and from run to run: the component's triangles t[0..n) in increasing triangle index, in tiles of 256;
+ *     per tile k and group g = 0..3:  s[l] = term of t[256 k + 64 g + l] (0.0 beyond n), l = 0..63;
+ *                                     for off = 32, 16, .., 1:  s[l] += s[l + off] for l < off;   G[g] = s[0];
+ *     T[k] = ((G[0] + G[1]) + G[2]) + G[3];      sum = ((0.0 + T[0]) + T[1]) + ...      (tiles added in increasing k).
+ *   Counts use integer atomics only.  workspace: the per-tile sums (float64).
+ *
+ * sg_topo_keep_count / sg_topo_keep_emit, a pair like sg_mc_count / sg_mc_emit.  keep [C] uint8 (non-zero: keep).  count writes
+ * new_vert_offsets / new_tri_offsets [S+1] (every element) and keeps positions in `workspace` (int32 words); the caller reads the
+ * two totals once, sizes the outputs and calls emit with the same mesh and workspace.  emit writes the vertices and normals of the
+ * kept components (their bits copied unchanged) and their triangles, both in their original relative order, faces renumbered
+ * locally; vertices of component -1 and skipped triangles are dropped.  max_verts / max_tris: the capacities of out_vertices /
+ * out_normals [max_verts][3] and out_faces [max_tris][3]; nothing is written beyond them, every element below the totals is
+ * written, nothing is read from an output. */
+size_t sg_topo_label_workspace_bytes(long S, long V);
+int sg_topo_label(const int64_t* faces, const int64_t* vert_offsets, const int64_t* tri_offsets, long S, long V, long F,
+                  int* vertex_component, int64_t* comp_offsets, void* workspace, size_t workspace_bytes, hipStream_t stream);
+int sg_topo_keys(const int64_t* faces, const int64_t* vert_offsets, const int64_t* tri_offsets, long S, long V, long F,
+                 const int* vertex_component, const int64_t* comp_offsets, long C, int* tri_keys, int64_t* edge_keys,
+                 hipStream_t stream);
+size_t sg_topo_stats_workspace_bytes(long F, long C);
+int sg_topo_stats(const float* vertices, const int64_t* faces, const int64_t* vert_offsets, const int64_t* tri_offsets, long S, long V,
+                  long F, const int* vertex_component, const int64_t* comp_offsets, long C, const int64_t* tri_order,
+                  const int64_t* seg_offsets, const int64_t* tile_offsets, const int64_t* edge_sorted, int* n_vertices,
+                  int* n_triangles, int* n_edges, int* n_open, double* area, double* volume, void* workspace, size_t workspace_bytes,
+                  hipStream_t stream);
+size_t sg_topo_keep_workspace_bytes(long S, long V, long F);
+int sg_topo_keep_count(const int64_t* faces, const int64_t* vert_offsets, const int64_t* tri_offsets, long S, long V, long F,
+                       const int* vertex_component, const int64_t* comp_offsets, long C, const uint8_t* keep,
+                       int64_t* new_vert_offsets, int64_t* new_tri_offsets, void* workspace, size_t workspace_bytes,
+                       hipStream_t stream);
+int sg_topo_keep_emit(const float* vertices, const float* normals, const int64_t* faces, const int64_t* vert_offsets,
+                      const int64_t* tri_offsets, long S, long V, long F, const int64_t* new_vert_offsets, float* out_vertices,
+                      float* out_normals, int64_t* out_faces, long max_verts, long max_tris, void* workspace, size_t workspace_bytes,
+                      hipStream_t stream);
+
 /* ---- K13: point-cloud evaluation: Chamfer matrices, nearest neighbours, occupancy histograms -----------------------------------
  * Clouds are [S][P][3] fp32, contiguous.  Every pair (a, b) of points has ONE value, in f32:
  *   dx = ax - bx, dy = ay - by, dz = az - bz;   d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx))

@@ -1745,6 +1745,7 @@ int sg_scatter_max_gather_cpu(const float* x, const int* arg, float* out, long N
 #include "../csrc/mesh_core.h"
 #include "../csrc/raymarch_core.h"
 #include "../csrc/pointcloud_core.h"
+#include "../csrc/topology_core.h"
 
 extern "C" {
 
@@ -1866,6 +1867,190 @@ int sg_mesh_sample_cpu(const float* vertices, const int64_t* faces, const int64_
             sg_mesh_point(vertices + (vb + faces[f * 3]) * 3, vertices + (vb + faces[f * 3 + 1]) * 3, vertices + (vb + faces[f * 3 + 2]) * 3, u1, u2,
                           out + i * 3);
         }
+    }
+    return SG_OK;
+}
+
+// ---- K12b: mesh topology (csrc/topology.hip) -------------------------------------------------------------------------------------
+// The same partition, numbering, keys, counts and tile sums as the kernels, walked in order on one thread (the tile sums per component
+// in parallel): a sequential union-find whose roots are the lowest vertices, the header's tree per tile.
+static bool topo_sizes(long S, long V, long F) { return S >= 1 && S < 2147483647L && V >= 0 && F >= 0 && V <= 2147483647L && F <= 2147483647L; }
+
+static bool topo_corners(const int64_t* faces, const int64_t* vo, const int64_t* to, long S, long V, long f, long& s, long& a, long& b, long& c) {
+    s = sg_topo_shape_of(to, S, f);
+    return sg_topo_triangle(faces + f * 3, vo[s], vo[s + 1] - vo[s], V, a, b, c);
+}
+
+static long topo_component_of(const int64_t* vo, long S, long v, const int* vertex_component, const int64_t* comp_offsets, long C) {
+    const int label = vertex_component[v];
+    if (label < 0) return -1;
+    const long c = comp_offsets[sg_topo_shape_of(vo, S, v)] + label;
+    return c < C ? c : -1;
+}
+
+static int topo_find(std::vector<int>& parent, int x) {
+    while (parent[x] != x) {
+        parent[x] = parent[parent[x]];
+        x = parent[x];
+    }
+    return x;
+}
+
+// out[t] = the position of the first element of shape t among the set flags (t = S: their number); excl: the positions
+static void topo_scan(const std::vector<int>& flag, long n, int* excl, const int64_t* offsets, long S, int64_t* out) {
+    int run = 0;
+    for (long i = 0; i < n; ++i) {
+        excl[i] = run;
+        run += flag[i];
+    }
+    for (long t = 0; t <= S; ++t) {
+        const long o = offsets[t];
+        out[t] = t == S || o >= n ? run : (o < 0 ? 0 : excl[o]);
+    }
+}
+
+int sg_topo_label_cpu(const int64_t* faces, const int64_t* vert_offsets, const int64_t* tri_offsets, long S, long V, long F,
+                      int* vertex_component, int64_t* comp_offsets, void*, size_t, void*) {
+    CPU_CHECK(topo_sizes(S, V, F));
+    CPU_CHECK(vert_offsets && tri_offsets && comp_offsets && (V == 0 || vertex_component) && (F == 0 || faces));
+    std::vector<int> parent(V), named(V, 0), is_root(V), excl(V);
+    for (long v = 0; v < V; ++v) parent[v] = (int)v;
+    for (long f = 0; f < F; ++f) {
+        long s, c[3];
+        if (!topo_corners(faces, vert_offsets, tri_offsets, S, V, f, s, c[0], c[1], c[2])) continue;
+        for (int k = 0; k < 3; ++k) named[c[k]] = 1;
+        for (int k = 0; k < 2; ++k) {
+            const int ra = topo_find(parent, (int)c[k]), rb = topo_find(parent, (int)c[k + 1]);
+            if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
+        }
+    }
+    for (long v = 0; v < V; ++v) is_root[v] = topo_find(parent, (int)v) == (int)v && named[v];
+    topo_scan(is_root, V, excl.data(), vert_offsets, S, comp_offsets);
+    for (long v = 0; v < V; ++v)
+        vertex_component[v] = named[v] ? (int)((long)excl[topo_find(parent, (int)v)] - comp_offsets[sg_topo_shape_of(vert_offsets, S, v)]) : -1;
+    return SG_OK;
+}
+
+int sg_topo_keys_cpu(const int64_t* faces, const int64_t* vert_offsets, const int64_t* tri_offsets, long S, long V, long F,
+                     const int* vertex_component, const int64_t* comp_offsets, long C, int* tri_keys, int64_t* edge_keys, void*) {
+    CPU_CHECK(topo_sizes(S, V, F) && C >= 0 && C <= V);
+    CPU_CHECK(vert_offsets && tri_offsets && comp_offsets && (V == 0 || vertex_component) && (F == 0 || (faces && tri_keys && edge_keys)));
+    for (long f = 0; f < F; ++f) {
+        long s, a, b, c, comp = -1;
+        if (topo_corners(faces, vert_offsets, tri_offsets, S, V, f, s, a, b, c)) comp = topo_component_of(vert_offsets, S, a, vertex_component, comp_offsets, C);
+        tri_keys[f] = comp < 0 ? SG_TOPO_NO_COMPONENT : (int)comp;
+        edge_keys[3 * f] = comp < 0 ? SG_TOPO_NO_EDGE : sg_topo_edge_key(a, b);
+        edge_keys[3 * f + 1] = comp < 0 ? SG_TOPO_NO_EDGE : sg_topo_edge_key(b, c);
+        edge_keys[3 * f + 2] = comp < 0 ? SG_TOPO_NO_EDGE : sg_topo_edge_key(c, a);
+    }
+    return SG_OK;
+}
+
+int sg_topo_stats_cpu(const float* vertices, const int64_t* faces, const int64_t* vert_offsets, const int64_t* tri_offsets, long S,
+                      long V, long F, const int* vertex_component, const int64_t* comp_offsets, long C, const int64_t* tri_order,
+                      const int64_t* seg_offsets, const int64_t* tile_offsets, const int64_t* edge_sorted, int* n_vertices,
+                      int* n_triangles, int* n_edges, int* n_open, double* area, double* volume, void*, size_t, void*) {
+    CPU_CHECK(topo_sizes(S, V, F) && C >= 0 && C <= V);
+    CPU_CHECK(vert_offsets && tri_offsets && comp_offsets && seg_offsets && tile_offsets);
+    CPU_CHECK((V == 0 || (vertices && vertex_component)) && (F == 0 || (faces && tri_order && edge_sorted)));
+    CPU_CHECK(C == 0 || (n_vertices && n_triangles && n_edges && n_open && area && volume));
+    for (long c = 0; c < C; ++c) n_vertices[c] = n_edges[c] = n_open[c] = 0;
+    if (C == 0) return SG_OK;
+    for (long v = 0; v < V; ++v) {
+        const long comp = topo_component_of(vert_offsets, S, v, vertex_component, comp_offsets, C);
+        if (comp >= 0) ++n_vertices[comp];
+    }
+    for (long i = 0; i < 3 * F;) {
+        const int64_t key = edge_sorted[i];
+        if (key == SG_TOPO_NO_EDGE || key < 0) {
+            ++i;
+            continue;
+        }
+        long forward = 0, backward = 0, j = i;
+        for (; j < 3 * F && sg_topo_same_edge(edge_sorted[j], key); ++j) (edge_sorted[j] & 1 ? backward : forward) += 1;
+        const long low = sg_topo_edge_low(key);
+        const long comp = low < V ? topo_component_of(vert_offsets, S, low, vertex_component, comp_offsets, C) : -1;
+        if (comp >= 0) {
+            ++n_edges[comp];
+            if (!(forward == 1 && backward == 1)) ++n_open[comp];
+        }
+        i = j;
+    }
+#pragma omp parallel for schedule(dynamic, 16)
+    for (long c = 0; c < C; ++c) {
+        const long i0 = seg_offsets[c], i1 = seg_offsets[c + 1];
+        double sa = 0.0, sv = 0.0;
+        for (long t = 0; t < tile_offsets[c + 1] - tile_offsets[c]; ++t) {
+            double ta[SG_TOPO_TILE], tv[SG_TOPO_TILE];
+            for (int l = 0; l < SG_TOPO_TILE; ++l) {
+                const long i = i0 + t * SG_TOPO_TILE + l;
+                ta[l] = tv[l] = 0.0;
+                if (i >= i1 || i < 0 || i >= F) continue;
+                const long f = tri_order[i];
+                long s, a, b, cc;
+                if (f >= 0 && f < F && topo_corners(faces, vert_offsets, tri_offsets, S, V, f, s, a, b, cc))
+                    sg_topo_terms(vertices + a * 3, vertices + b * 3, vertices + cc * 3, ta[l], tv[l]);
+            }
+            for (int g = 0; g < SG_TOPO_TILE; g += 64)
+                for (int off = 32; off > 0; off >>= 1)
+                    for (int l = 0; l < off; ++l) {
+                        ta[g + l] += ta[g + l + off];
+                        tv[g + l] += tv[g + l + off];
+                    }
+            sa += ((ta[0] + ta[64]) + ta[128]) + ta[192];
+            sv += ((tv[0] + tv[64]) + tv[128]) + tv[192];
+        }
+        n_triangles[c] = (int)(i1 - i0);
+        area[c] = sa;
+        volume[c] = sv;
+    }
+    return SG_OK;
+}
+
+int sg_topo_keep_count_cpu(const int64_t* faces, const int64_t* vert_offsets, const int64_t* tri_offsets, long S, long V, long F,
+                           const int* vertex_component, const int64_t* comp_offsets, long C, const uint8_t* keep,
+                           int64_t* new_vert_offsets, int64_t* new_tri_offsets, void* workspace, size_t workspace_bytes, void*) {
+    CPU_CHECK(topo_sizes(S, V, F) && C >= 0 && C <= V);
+    CPU_CHECK(vert_offsets && tri_offsets && comp_offsets && new_vert_offsets && new_tri_offsets && workspace);
+    CPU_CHECK((V == 0 || vertex_component) && (F == 0 || faces) && (C == 0 || keep));
+    CPU_CHECK(workspace_bytes >= (size_t)(2 * V + 2 * F) * sizeof(int));
+    int *kept_v = (int*)workspace, *pos_v = kept_v + V, *kept_t = pos_v + V, *pos_t = kept_t + F;
+    std::vector<int> kv(V), kt(F);
+    for (long v = 0; v < V; ++v) {
+        const long comp = topo_component_of(vert_offsets, S, v, vertex_component, comp_offsets, C);
+        kept_v[v] = kv[v] = comp >= 0 && keep[comp] ? 1 : 0;
+    }
+    for (long f = 0; f < F; ++f) {
+        long s, a, b, c;
+        kept_t[f] = kt[f] = topo_corners(faces, vert_offsets, tri_offsets, S, V, f, s, a, b, c) && kv[a] ? 1 : 0;
+    }
+    topo_scan(kv, V, pos_v, vert_offsets, S, new_vert_offsets);
+    topo_scan(kt, F, pos_t, tri_offsets, S, new_tri_offsets);
+    return SG_OK;
+}
+
+int sg_topo_keep_emit_cpu(const float* vertices, const float* normals, const int64_t* faces, const int64_t* vert_offsets,
+                          const int64_t* tri_offsets, long S, long V, long F, const int64_t* new_vert_offsets, float* out_vertices,
+                          float* out_normals, int64_t* out_faces, long max_verts, long max_tris, void* workspace,
+                          size_t workspace_bytes, void*) {
+    CPU_CHECK(topo_sizes(S, V, F) && max_verts >= 0 && max_tris >= 0);
+    CPU_CHECK(vert_offsets && tri_offsets && new_vert_offsets && workspace);
+    CPU_CHECK((V == 0 || (vertices && normals)) && (F == 0 || faces));
+    CPU_CHECK((max_verts == 0 || (out_vertices && out_normals)) && (max_tris == 0 || out_faces));
+    CPU_CHECK(workspace_bytes >= (size_t)(2 * V + 2 * F) * sizeof(int));
+    const int *kept_v = (const int*)workspace, *pos_v = kept_v + V, *kept_t = pos_v + V, *pos_t = kept_t + F;
+    for (long v = 0; v < V; ++v) {
+        if (!kept_v[v] || pos_v[v] >= max_verts) continue;
+        memcpy(out_vertices + (long)pos_v[v] * 3, vertices + v * 3, 3 * sizeof(float));
+        memcpy(out_normals + (long)pos_v[v] * 3, normals + v * 3, 3 * sizeof(float));
+    }
+    for (long f = 0; f < F; ++f) {
+        long s, a, b, c;
+        if (!kept_t[f] || pos_t[f] >= max_tris || !topo_corners(faces, vert_offsets, tri_offsets, S, V, f, s, a, b, c)) continue;
+        const long base = new_vert_offsets[s], o = pos_t[f];
+        out_faces[o * 3] = pos_v[a] - base;
+        out_faces[o * 3 + 1] = pos_v[b] - base;
+        out_faces[o * 3 + 2] = pos_v[c] - base;
     }
     return SG_OK;
 }

@@ -166,6 +166,14 @@ SIGNATURES = {
     "sg_mc_emit": (c_int, [_P, _L, _I, _I, _I, _F, _I, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _L, _L, _P, _Z, _P]),
     "sg_mesh_sample_workspace_bytes": (_Z, [_L, _L]),
     "sg_mesh_sample": (c_int, [_P, _P, _P, _P, _L, _L, _P, _L, _P, _P, _P, _Z, _P]),
+    "sg_topo_label_workspace_bytes": (_Z, [_L, _L]),
+    "sg_topo_label": (c_int, [_P, _P, _P, _L, _L, _L, _P, _P, _P, _Z, _P]),
+    "sg_topo_keys": (c_int, [_P, _P, _P, _L, _L, _L, _P, _P, _L, _P, _P, _P]),
+    "sg_topo_stats_workspace_bytes": (_Z, [_L, _L]),
+    "sg_topo_stats": (c_int, [_P, _P, _P, _P, _L, _L, _L, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "sg_topo_keep_workspace_bytes": (_Z, [_L, _L, _L]),
+    "sg_topo_keep_count": (c_int, [_P, _P, _P, _L, _L, _L, _P, _P, _L, _P, _P, _P, _P, _Z, _P]),
+    "sg_topo_keep_emit": (c_int, [_P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P, _L, _L, _P, _Z, _P]),
     "sg_chamfer_matrix_workspace_bytes": (_Z, [_L, _L, _L, _L]),
     "sg_chamfer_matrix": (c_int, [_P, _P, _L, _L, _L, _L, _P, _P, _P, _Z, _P]),
     "sg_chamfer_nearest": (c_int, [_P, _P, _L, _L, _L, _P, _P, _P, _P, _P]),

@@ -136,6 +136,49 @@ class Mesh(object):
             raise ValueError("export: unknown mesh format %r (.obj, .stl and .ply are written)" % ext)
         return path
 
+    # ---- topology: the trimesh names, computed by the C++ twin (shapegan_amd.topology) ------------------------------------------------
+    def _components(self):
+        from . import topology
+        normals = self.vertex_normals if self.vertex_normals is not None else np.zeros_like(self.vertices)
+        batch = MeshBatch(torch.from_numpy(self.vertices), torch.from_numpy(normals), torch.from_numpy(self.faces),
+                          torch.tensor([0, self.vertices.shape[0]], dtype=torch.int64),
+                          torch.tensor([0, self.faces.shape[0]], dtype=torch.int64))
+        return batch, topology.components(batch)
+
+    def split(self):
+        """trimesh.Trimesh.split: the connected components as a list of Mesh, in the order of their lowest vertex index."""
+        from . import topology
+        batch, comps = self._components()
+        out = []
+        for c in range(len(comps)):
+            mask = torch.zeros(len(comps), dtype=torch.bool)
+            mask[c] = True
+            piece = topology.keep_components(batch, comps, mask).mesh(0)
+            if self.vertex_normals is None:
+                piece.vertex_normals = None
+            out.append(piece)
+        return out
+
+    @property
+    def body_count(self):
+        return len(self._components()[1])
+
+    @property
+    def is_watertight(self):
+        """Every edge is shared by exactly two triangles that run along it in opposite directions (and there is a triangle)."""
+        comps = self._components()[1]
+        return bool(len(comps) > 0 and comps.watertight.all())
+
+    @property
+    def volume(self):
+        """The signed volume enclosed: positive for outward-facing closed surfaces."""
+        return float(self._components()[1].volume.sum())
+
+    @property
+    def euler_number(self):
+        """Referenced vertices - distinct edges + triangles."""
+        return int(self._components()[1].euler.sum())
+
     def to_trimesh(self):
         import trimesh
         return trimesh.Trimesh(vertices=self.vertices, faces=self.faces, vertex_normals=self.vertex_normals, process=False)
@@ -170,6 +213,16 @@ class MeshBatch(object):
         v, n, f = self.vertices.cpu().numpy(), self.normals.cpu().numpy(), self.faces.cpu().numpy()
         vo, to = self._offsets()
         return [Mesh(v[vo[i]:vo[i + 1]], f[to[i]:to[i + 1]], n[vo[i]:vo[i + 1]]) for i in range(len(self))]
+
+    def components(self):
+        """shapegan_amd.topology.components of this batch."""
+        from . import topology
+        return topology.components(self)
+
+    def clean(self, rule=True):
+        """The MeshBatch of the components `rule` keeps (shapegan_amd.topology.clean_meshes)."""
+        from . import topology
+        return topology.clean_meshes(self, rule)[0]
 
     def sample_surface(self, count, generator=None, return_empty=False):
         """[S, count, 3] points on the device of the meshes, area-weighted; uniforms [S, count, 3] from torch.rand with

@@ -45,12 +45,13 @@ def shapes_per_chunk(voxel_resolution, padded_grid):
 
 
 def sample_point_clouds(sdf_net, sample_count, point_cloud_size, voxel_resolution=128, rescale='half_unit_sphere', latent_codes=None,
-                        narrow_band=False, generator=None):
+                        narrow_band=False, generator=None, clean=False):
     """get_uniform_surface_points(z, point_cloud_size, voxel_resolution, sphere_only=False, level=LEVEL) + rescale for
     `sample_count` latent codes (standard normal when None), in chunks of shapes_per_chunk(voxel_resolution, True).
     narrow_band: the grids come from the brick path of SDFNet.voxel_grids, built for LEVEL (True, or a dict of its
     arguments brick / band / lipschitz; voxel_resolution a multiple of the brick).
-    generator: the torch.Generator of the surface samples (default: the device's own)."""
+    generator: the torch.Generator of the surface samples (default: the device's own).
+    clean: a rule of topology.clean_meshes ("largest", True, a dict): the clouds are sampled from the cleaned meshes."""
     result = np.zeros((sample_count, point_cloud_size, 3))
     if latent_codes is None:
         latent_codes = standard_normal_distribution.sample((sample_count, LATENT_CODE_SIZE)).to(device)
@@ -60,14 +61,16 @@ def sample_point_clouds(sdf_net, sample_count, point_cloud_size, voxel_resolutio
         z = latent_codes[begin:min(begin + chunk, sample_count)]
         grids = sdf_net.voxel_grids(z, voxel_resolution, sphere_only=False, level=LEVEL, **narrow_band_options(narrow_band))
         batch = marching_cubes(grids, level=LEVEL, spacing=size / voxel_resolution, origin=-size / 2, pad=True, pad_value=1.0)
+        if clean:
+            batch = batch.clean(clean)
         points, empty = batch.sample_surface(point_cloud_size, generator=generator, return_empty=True)
         _collect(result, begin, points, empty, rescale)
     return result
 
 
-def sample_from_voxels(voxels, point_cloud_size, rescale='half_unit_sphere'):
+def sample_from_voxels(voxels, point_cloud_size, rescale='half_unit_sphere', clean=False):
     """Meshes each voxel grid of `voxels` [B,R,R,R] (numpy or tensor) padded with 1 at level 0 and samples it
-    (metrics.py:31-46); computed on `util.device`."""
+    (metrics.py:31-46); computed on `util.device`.  clean: as sample_point_clouds."""
     result = np.zeros((voxels.shape[0], point_cloud_size, 3))
     size = 2
     voxel_resolution = voxels.shape[1]
@@ -78,6 +81,8 @@ def sample_from_voxels(voxels, point_cloud_size, rescale='half_unit_sphere'):
     for begin in range(0, voxels.shape[0], chunk):
         batch = marching_cubes(voxels[begin:begin + chunk], level=0, spacing=size / voxel_resolution, origin=-size / 2, pad=True,
                                pad_value=1.0)
+        if clean:
+            batch = batch.clean(clean)
         points, empty = batch.sample_surface(point_cloud_size, return_empty=True)
         _collect(result, begin, points, empty, rescale)
     return result

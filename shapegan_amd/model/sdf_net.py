@@ -247,17 +247,22 @@ class SDFNet(SavableModule):
             result = narrow_band_grids(evaluate, S, R, dev, brick=brick, level=level, band=band, lipschitz=lipschitz, pad=pad, mask=mask)
         return result.grid, result.stats
 
-    def get_mesh(self, latent_code, voxel_resolution=64, sphere_only=True, raise_on_empty=False, level=0, narrow_band=False, refine=0):
+    def get_mesh(self, latent_code, voxel_resolution=64, sphere_only=True, raise_on_empty=False, level=0, narrow_band=False, refine=0,
+                 clean=False):
         """Marching cubes of the SDF grid (model/sdf_net.py:97-112) on the device: a mesh.Mesh, None when the grid does not cross
         `level` (ValueError with raise_on_empty).  Coordinates are the reference's: the grid of get_voxels padded once more with
         1, spacing 2 / R, shifted by -1 — grid index i lands at (i + 1 + t) 2/R - 1 (sphere_only) or (i + 2 + t) 2/R - 1 (the
         grid get_voxels pads itself).  narrow_band: the grid is built for `level` by the brick path of voxel_grids (True, or a dict
         of its arguments brick / band / lipschitz).  refine = K > 0: every vertex is then moved onto the network's own level set by K
-        Newton steps and given its exact normal (surface.refine_meshes, at most a cell diagonal away); 0 is the marching-cubes mesh."""
+        Newton steps and given its exact normal (surface.refine_meshes, at most a cell diagonal away); 0 is the marching-cubes mesh.
+        clean: a rule of topology.clean_meshes ("largest", True, a dict) applied to the marching-cubes mesh before refine; a mesh of
+        which nothing is left counts as empty.  False: no cleaning."""
         size = 2
         grids = self.voxel_grids(latent_code.reshape(1, -1), voxel_resolution, sphere_only=sphere_only, level=level,
                                  **narrow_band_options(narrow_band))
         batch = marching_cubes(grids, level=level, spacing=size / voxel_resolution, origin=-size / 2, pad=True, pad_value=1.0)
+        if clean:
+            batch = batch.clean(clean)
         if batch.faces.shape[0] == 0:
             if raise_on_empty:
                 raise ValueError("Surface level must be within volume data range.")
@@ -269,10 +274,10 @@ class SDFNet(SavableModule):
         return batch.mesh(0)
 
     def get_uniform_surface_points(self, latent_code, point_count=1000, voxel_resolution=64, sphere_only=True, level=0,
-                                   narrow_band=False):
+                                   narrow_band=False, clean=False):
         """get_mesh(...).sample(point_count) (model/sdf_net.py:114-116): AttributeError when the mesh is empty, as there."""
         mesh = self.get_mesh(latent_code, voxel_resolution=voxel_resolution, sphere_only=sphere_only, level=level,
-                             narrow_band=narrow_band)
+                             narrow_band=narrow_band, clean=clean)
         return mesh.sample(point_count)
 
     def get_normals(self, latent_code, points):

@@ -81,14 +81,17 @@ def fit_latent_codes(sdf_net, points, sdf, segment_offsets=None, points_per_shap
     return z, loss
 
 
-def reconstruct_meshes(sdf_net, latent_codes, voxel_resolution=64, level=0, narrow_band=False, refine=0):
+def reconstruct_meshes(sdf_net, latent_codes, voxel_resolution=64, level=0, narrow_band=False, refine=0, clean=False):
     """MeshBatch of the level sets of the codes [S,L]: shape s is SDFNet.get_mesh(latent_codes[s], voxel_resolution, level=level), all
     grids and the marching cubes in batched launches.  narrow_band: the grids come from the brick path of SDFNet.voxel_grids, built for
     `level` (True, or a dict of its arguments brick / band / lipschitz).  refine = K > 0: the vertices are moved onto the network's level
-    set by K Newton steps and carry its normals (surface.refine_meshes with the cell diagonal as the limit), as get_mesh(refine=K)."""
+    set by K Newton steps and carry its normals (surface.refine_meshes with the cell diagonal as the limit), as get_mesh(refine=K).
+    clean: a rule of topology.clean_meshes ("largest", True, a dict), applied after marching cubes and before refine."""
     codes = latent_codes.detach().reshape(-1, sdf_net.latent_code_size)
     grids = sdf_net.voxel_grids(codes, voxel_resolution, sphere_only=True, level=level, **narrow_band_options(narrow_band))
     batch = marching_cubes(grids, level=level, spacing=2 / voxel_resolution, origin=-1, pad=True, pad_value=1.0)
+    if clean:
+        batch = batch.clean(clean)
     if refine:
         from .surface import cell_diagonal, refine_meshes
         batch, _ = refine_meshes(sdf_net, codes, batch, level=level, iterations=int(refine), max_move=cell_diagonal(voxel_resolution))
@@ -121,6 +124,8 @@ def main(argv=None):
     ap.add_argument("--resolution", type=int, default=64)
     ap.add_argument("--narrow-band", action="store_true", help="evaluate the network only in bricks near the surface")
     ap.add_argument("--refine", type=int, default=0, help="Newton steps that move the mesh vertices onto the network's level set")
+    ap.add_argument("--clean", nargs="?", const="default", default=None, choices=("default", "largest"),
+                    help="drop floating pieces of the reconstructions: below 1 %% of the area (default) or all but the largest")
     ap.add_argument("--scan-count", type=int, default=50)
     ap.add_argument("--scan-resolution", type=int, default=1024)
     ap.add_argument("--chamfer-points", type=int, default=2048)
@@ -148,7 +153,9 @@ def main(argv=None):
     torch.save(codes.cpu(), args.out)
     batch = None
     if args.meshes or args.chamfer:
-        batch = reconstruct_meshes(net, codes, args.resolution, narrow_band=args.narrow_band, refine=args.refine)
+        from .topology import clean_option
+        batch = reconstruct_meshes(net, codes, args.resolution, narrow_band=args.narrow_band, refine=args.refine,
+                                   clean=clean_option(args.clean))
     if args.meshes:
         os.makedirs(args.meshes, exist_ok=True)
         for i, mesh in enumerate(batch.meshes()):

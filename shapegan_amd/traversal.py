@@ -28,6 +28,7 @@ import torch
 from . import lib as L
 from . import mesh as M
 from .brickgrid import options as narrow_band_options
+from .topology import clean_option
 from . import ops
 
 SURFACE_LEVEL = 0.011      # demo_latent_space.py:19
@@ -230,7 +231,7 @@ def _frame_bytes(voxel_resolution, size, ssaa):
 
 
 def traversal_frames(sdf_net, frame_codes, voxel_resolution=128, level=SURFACE_LEVEL, size=1080, chunk=None, model_color=None,
-                     renderer=None, memory_budget=2 << 30, narrow_band=False, refine=0):
+                     renderer=None, memory_budget=2 << 30, narrow_band=False, refine=0, clean=False):
     """Generator of uint8 [size, size, 3] images, one per row of frame_codes [F, L]: frame f is
         viewer.set_mesh(sdf_net.get_mesh(frame_codes[f], voxel_resolution, level=level)); viewer.get_image()
     of a fresh MeshRenderer(size=size), byte for byte, but a chunk of frames goes through voxel_grids -> marching_cubes -> render_meshes
@@ -238,7 +239,8 @@ def traversal_frames(sdf_net, frame_codes, voxel_resolution=128, level=SURFACE_L
     the whole call (a colour per frame would need a colour per shape in the raster shading kernel).  A code whose grid does not cross
     `level` yields floor and background.  renderer: a MeshRenderer to use (its size wins).  narrow_band: the grids come from the brick
     path of SDFNet.voxel_grids, built for `level` (True, or a dict of its arguments brick / band / lipschitz; the same frames, byte for byte, whenever the meshes are the same).
-    refine = K > 0: every frame's mesh is get_mesh(..., refine=K) — vertices on the network's level set, its normals (surface.refine_meshes)."""
+    refine = K > 0: every frame's mesh is get_mesh(..., refine=K) — vertices on the network's level set, its normals (surface.refine_meshes).
+    clean: a rule of topology.clean_meshes ("largest", True, a dict) applied to every frame's mesh before refine (no flickering floaters)."""
     from .rendering import MeshRenderer
     dev = next(sdf_net.parameters()).device
     codes = frame_codes.detach().reshape(-1, sdf_net.latent_code_size).to(device=dev, dtype=torch.float32)
@@ -252,6 +254,8 @@ def traversal_frames(sdf_net, frame_codes, voxel_resolution=128, level=SURFACE_L
         for a in range(0, codes.shape[0], per):
             grids = sdf_net.voxel_grids(codes[a:a + per], R, sphere_only=True, level=level, **narrow_band_options(narrow_band))
             batch = M.marching_cubes(grids, level=level, spacing=2.0 / R, origin=-1.0, pad=True, pad_value=1.0)
+            if clean:
+                batch = batch.clean(clean)
             if refine:
                 from .surface import cell_diagonal, refine_meshes
                 batch, _ = refine_meshes(sdf_net, codes[a:a + per], batch, level=level, iterations=int(refine), max_move=cell_diagonal(R))
@@ -400,6 +404,8 @@ def main(argv=None):
     ap.add_argument("--iterations", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--narrow-band", action="store_true", help="evaluate the network only in bricks near the surface")
+    ap.add_argument("--clean", nargs="?", const="default", default=None, choices=("default", "largest"),
+                    help="drop floating pieces of every frame's mesh: below 1 %% of the area (default) or all but the largest")
     args = ap.parse_args(argv)
 
     state = torch.load(args.net, map_location="cpu")
@@ -414,7 +420,8 @@ def main(argv=None):
     os.makedirs(args.out, exist_ok=True)
     panel = MapPanel(plan["embedding"], label_colors(labels, codes.shape[0]), plan["frame_positions"], plan["stops"][:-1], size=args.size,
                      device=args.device)
-    frames = traversal_frames(net, plan["frame_codes"], voxel_resolution=args.resolution, size=args.size, narrow_band=args.narrow_band)
+    frames = traversal_frames(net, plan["frame_codes"], voxel_resolution=args.resolution, size=args.size, narrow_band=args.narrow_band,
+                              clean=clean_option(args.clean))
     for f, (image, position) in enumerate(zip(frames, plan["frame_positions"])):
         Image.fromarray(np.concatenate((image, panel.image(position)), axis=1)).save(os.path.join(args.out, "frame-%05d.png" % f))
     print("\nUse this command to create a video:\n")
