@@ -18,7 +18,7 @@ SOURCES = ["conv3d.hip", "conv3d_halo.hip", "conv3d_edge.hip", "gemm.hip", "sdfn
 ABI_HEADER = os.path.join(HERE, "..", "include", "shapegan_hip.h")
 # the arithmetic the HIP kernels share with the twin: an edit rebuilds both libraries
 CORE_HEADERS = [os.path.join(CSRC, h) for h in ("core_fn.h", "mc_tables.h", "mesh_core.h", "raymarch_core.h", "pointcloud_core.h", "raster_core.h", "meshsdf_core.h", "tsne_core.h", "brickgrid_core.h", "project_core.h", "topology_core.h")]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "mfma_tile.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "sdfnet_tile.h")] + CORE_HEADERS + [ABI_HEADER]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "mfma_tile.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "sdfnet_tile.h"), os.path.join(CSRC, "sdfnet_frozen.h")] + CORE_HEADERS + [ABI_HEADER]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 

@@ -76,6 +76,17 @@ struct SgPerDeviceOnce {
     }
 };
 
+// the usual case: one kernel, its dynamic LDS size, the entry point's name for the message
+template <class K>
+static int sg_reserve_lds(SgPerDeviceOnce& once, K kern, size_t bytes, const char* entry) {
+    if (once.begin()) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        once.end();
+        if (e != hipSuccess) SG_FAIL(SG_ERR_HIP, "%s: cannot reserve %zu B LDS", entry, bytes);
+    }
+    return SG_OK;
+}
+
 static inline int sg_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 __device__ __forceinline__ float sg_wave_sum(float v) {

@@ -12,15 +12,18 @@
 //   2. forms the upstream gradient in the epilogue: out = tanh(v), d = out - clamp(target), dz8 = sign(d) (1 - out^2) / m;
 //   3. walks the chain back with the transposed packs of the same weight image, dZ_l = (T_{l+1} dZ_{l+1}) * ReLU'(H_l), reusing the
 //      forward's single [256][P] LDS tile as the B operand and the forward's own GEMM loop and fragment mapping — the lane that made
-//      a sign word is the lane that needs it;
+//      a sign word is the lane that needs it (sdfnet_frozen_bwd_tile in sdfnet_frozen.h, shared with K7d, sdfnet_project.hip);
 //   4. reduces dZ5 and dZ1 over the tile's points in registers (DPP) and stores [2][256] sums and the tile's sum of |d|.
 // Nothing else goes to memory: 16 B in per point, 2 KB out per TILE.  latent_reduce_kernel adds a shape's tiles in tile order.
 //
 // Tiles never straddle shapes and a lane beyond a shape's used points contributes exact zeros (its dz8 is 0), so a shape's result does
 // not depend on what else is in the call.  The points of a shape that a call uses are a window that wraps around its cloud: used
 // point i < m is seg_off[s] + (win_start + i) mod n — a fit loop walks mini-batches through the cloud without an index tensor.
+//
+// This file holds what is the latent fit's own: the loss epilogue (LatentFitIo::store), the window, the row sums and the reduction.
+// The sign keeping, the table row, the forward's arguments and the chain back are in sdfnet_frozen.h.
 #include "common.h"
-#include "sdfnet_tile.h"
+#include "sdfnet_frozen.h"
 #include "../../include/shapegan_hip.h"
 
 namespace sg {
@@ -48,29 +51,18 @@ struct LatentFitArgs {
     float* part;              // [T][kFitRow]
 };
 
-template <int NT>
-struct LatentFitIo {
+struct LatentFitIo : SdfSignKeeper {
     const LatentFitArgs* f;
     long beg, n, first;       // the shape's run and (win_start + i0) mod n
     int cnt;                  // used points of this tile
     float inv_den;            // divisor m as a float
     float* dz8s;              // LDS [P]
     float* absd;              // LDS [P]
-    unsigned* signs;          // registers [7][NT]
     __device__ __forceinline__ long index(long gp) const {
         const long i = first + gp;      // (gp < cnt <= n and first < n: one wrap at most)
         return beg + (i >= n ? i - n : i);
     }
     __device__ __forceinline__ float coord(const SdfFwdArgs&, long gp, int c) const { return f->points[index(gp) * 3 + c]; }
-    __device__ __forceinline__ bool ragged(const SdfFwdArgs&) const { return false; }
-    __device__ __forceinline__ int shape(const SdfFwdArgs&, long) const { return 0; }
-    __device__ __forceinline__ void keep(int layer, const unsigned (&mk)[NT]) const {
-        // (select chain with constant indices: `layer` is a loop variable in the forward, a dynamic index would put the words in scratch)
-#pragma unroll
-        for (int l = 0; l < 7; ++l)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) signs[l * NT + t] = layer == l ? mk[t] : signs[l * NT + t];
-    }
     __device__ __forceinline__ void store(const SdfFwdArgs&, long gp, float v) const {
         float dz = 0.f, ad = 0.f;
         if (gp < cnt) {
@@ -89,59 +81,37 @@ struct LatentFitIo {
 
 template <int P>
 __global__ void __launch_bounds__(512, 4) latent_fit_kernel(LatentFitArgs f) {
-    constexpr int NT = P / 32;
     __shared__ float s_dz8[P], s_abs[P];
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int kh = lane >> 5, r = lane & 31;
     const long tile = blockIdx.x;
-    const int s = f.tiles[2 * tile], i0 = f.tiles[2 * tile + 1];
+    const SdfTileRow row = sdf_tile_row(f.tiles, f.seg_off, f.S, tile);
+    const long n = row.n;
     float* const prow = f.part + tile * kFitRow;
-    long beg = 0, n = 0;
-    if (s >= 0 && s < f.S) {
-        beg = f.seg_off[s];
-        n = f.seg_off[s + 1] - beg;
-    }
     const long m = n <= 0 ? 0 : (f.win_count <= 0 || f.win_count > n ? n : f.win_count);
-    long cnt = i0 < 0 ? 0 : m - i0;
+    long cnt = row.i0 < 0 ? 0 : m - row.i0;
     if (cnt > P) cnt = P;
     if (cnt <= 0) {       // (a table row that names nothing: the whole workgroup leaves, its partial row is zero)
         for (int e = tid; e < 2 * kH + 1; e += 512) prow[e] = 0.f;
         return;
     }
-    unsigned signs[7 * NT];
+    unsigned signs[7];
 #pragma unroll
-    for (int e = 0; e < 7 * NT; ++e) signs[e] = 0u;
-    LatentFitIo<NT> io;
+    for (int e = 0; e < 7; ++e) signs[e] = 0u;
+    LatentFitIo io;
+    io.signs = signs;
     io.f = &f;
-    io.beg = beg;
+    io.beg = row.beg;
     io.n = n;
-    io.first = (f.win_start + i0) % n;
+    io.first = (f.win_start + row.i0) % n;
     io.cnt = (int)cnt;
     io.inv_den = (float)m;
     io.dz8s = s_dz8;
     io.absd = s_abs;
-    io.signs = signs;
 
-    SdfFwdArgs a;
-    a.points = f.points;
-    a.points_period = 0;
-    a.latent = nullptr;
-    a.latent_idx = nullptr;
-    a.L = 0;
-    a.packed = f.packed;
-    a.lay = f.lay;
-    a.zb1 = f.zb1 + (long)s * kH;      // (shape = p0 / pps = 0: the tile's own bias rows)
-    a.zb5 = f.zb5 + (long)s * kH;
-    a.pps = 1L << 40;
-    a.sid = nullptr;
-    a.out = nullptr;
-    a.acts = nullptr;
-    a.ldn = 0;
-    a.N = cnt;
-    a.nbig = 0;
-    a.eps = 0.f;
-    sdfnet_fwd_tile<P, true, false, false, LatentFitIo<NT>, true>(a, 0, io);
+    const SdfFwdArgs a = sdf_frozen_tile_args(f.points, f.packed, f.lay, f.zb1 + (long)row.s * kH, f.zb5 + (long)row.s * kH, cnt);
+    sdfnet_fwd_tile<P, true, false, false, LatentFitIo, true>(a, 0, io);
     __syncthreads();      // dz8 / |d| of every point are in LDS, every read of H7 is done
 
     // the tile's sum of |d| in point order (points beyond cnt hold 0)
@@ -152,82 +122,14 @@ __global__ void __launch_bounds__(512, 4) latent_fit_kernel(LatentFitArgs f) {
         prow[2 * kH] = l;
     }
 
-    float* const Hs = smem;      // [256][P], as in the forward
-    const float4* pk = reinterpret_cast<const float4*>(f.packed);
-    auto wtile = [&](long off) { return pk + (off >> 2) + (long)wave * (kH / 8) * 64; };
-    auto rowoff = [](int q) { return (q & 3) + 8 * (q >> 2); };
-    // this lane's element (q, t) of the tile: row wave * 32 + frag_row(q, kh), point t * 32 + r
-    lds_float* const hw = (lds_float*)Hs + (wave * 32 + 4 * kh) * P + r;
-    auto dpp_add = [&](float v, auto ctrl, auto rowmask) __attribute__((always_inline)) {
-        return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), decltype(ctrl)::value,
-                                                                         decltype(rowmask)::value, 0xf, false));
-    };
-    auto half_sum = [&](float v) __attribute__((always_inline)) {      // lane 31 / 63: the sum over the half-wave's 32 points
-        v = dpp_add(v, IntTag<0xB1>(), IntTag<0xf>());
-        v = dpp_add(v, IntTag<0x4E>(), IntTag<0xf>());
-        v = dpp_add(v, IntTag<0x141>(), IntTag<0xf>());
-        v = dpp_add(v, IntTag<0x140>(), IntTag<0xf>());
-        return dpp_add(v, IntTag<0x142>(), IntTag<0xa>());
-    };
-    WRing<4> wr;
-    auto noop = []() {};
-    wring_start(wr, wtile(f.lay.T7), lane);
-    __builtin_amdgcn_sched_barrier(0);
-    // dZ7 = (w8 (x) dz8) * ReLU'(H7)
-    {
-        const float* w8 = f.packed + f.lay.W8;
-        float d8[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) d8[t] = s_dz8[t * 32 + r];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const float wv = w8[wave * 32 + frag_row(q, kh)];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) hw[rowoff(q) * P + t * 32] = ((signs[6 * NT + t] >> q) & 1u) ? wv * d8[t] : 0.f;
-        }
-    }
-    __syncthreads();
-    // images 5 .. 0 (dZ6 .. dZ1): GEMM with the transposed pack of the layer above, ReLU' from the kept word, back into the tile
-    f32x16 acc[NT];
-#pragma unroll 1
-    for (int i = 5; i >= 0; --i) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[t][q] = 0.f;
-        mlp_gemm_ring<NT, 4, kH / 8>(acc, wr, Hs, P, lane, noop);
-        if (i > 0) {
-            const long nxt = i == 5 ? f.lay.T6 : i == 4 ? f.lay.T5x : i == 3 ? f.lay.T4 : i == 2 ? f.lay.T3 : f.lay.T2;
-            wring_start(wr, wtile(nxt), lane);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        unsigned mk[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            unsigned w = signs[t];
-#pragma unroll
-            for (int l = 1; l < 6; ++l) w = i == l ? signs[l * NT + t] : w;
-            mk[t] = w;
-        }
-        __syncthreads();      // every wave has read the tile
-        const bool sums = i == 4 || i == 0;      // dZ5 and dZ1: the rows behind the latent gradient
-        float* const dst = prow + (i == 0 ? 0 : kH) + wave * 32 + 4 * kh;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            float rsum = 0.f;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const float g = ((mk[t] >> q) & 1u) ? acc[t][q] : 0.f;
-                if (i > 0) hw[rowoff(q) * P + t * 32] = g;      // (dZ1 is only summed: nothing reads the tile after the last image)
-                rsum += g;
-            }
-            if (sums) {
-                rsum = half_sum(rsum);
-                if (r == 31) dst[rowoff(q)] = rsum;
-            }
-        }
-        if (i > 0) __syncthreads();
-    }
+    // dZ5 and dZ1 are the rows behind the latent gradient: their sums over the tile's points (lane 31 / 63 of a half-wave holds one)
+    sdfnet_frozen_bwd_tile<P>(f.packed, f.lay, smem, signs[0], signs[1], signs[2], signs[3], signs[4], signs[5], signs[6], s_dz8,
+                              [&](int i, int q, float g) __attribute__((always_inline)) {
+                                  if (i == 4 || i == 0) {
+                                      const float rsum = half_wave_sum(g);
+                                      if (r == 31) prow[(i == 0 ? 0 : kH) + wave * 32 + 4 * kh + frag_rowoff(q)] = rsum;
+                                  }
+                              });
 }
 
 // per shape: t1 / t5 [256][S] = the sums of its tiles' dZ1 / dZ5 rows and loss = sum |d| / m, tiles added in tile order (double)
@@ -265,8 +167,6 @@ __global__ void __launch_bounds__(512) latent_reduce_kernel(const float* __restr
     }
 }
 
-static size_t fit_lds_bytes(int P, int KUp) { return ((size_t)kH * P + (size_t)KUp * (P + 1) + 16 * P + 7 * kH) * sizeof(float); }
-
 }  // namespace sg
 
 using namespace sg;
@@ -292,14 +192,9 @@ int sg_sdfnet_latent_grad(const float* points, const float* target, const int64_
     f.win_count = win_count;
     f.tiles = tiles;
     f.part = partials;
-    const size_t lds = fit_lds_bytes(kFitTile, f.lay.KUp);
+    const size_t lds = sdf_fwd_lds_bytes(kFitTile, f.lay.KUp);
     static SgPerDeviceOnce once;
-    if (once.begin()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(latent_fit_kernel<kFitTile>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        once.end();
-        if (e != hipSuccess) SG_FAIL(SG_ERR_HIP, "sg_sdfnet_latent_grad: cannot reserve %zu B LDS", lds);
-    }
+    if (const int rc = sg_reserve_lds(once, latent_fit_kernel<kFitTile>, lds, "sg_sdfnet_latent_grad")) return rc;
     hipLaunchKernelGGL((latent_fit_kernel<kFitTile>), dim3((unsigned)ntiles), dim3(512), lds, stream, f);
     SG_CHECK_LAUNCH();
     return SG_OK;

@@ -435,14 +435,9 @@ int sg_raymarch_steps(const float* packed, const float* zb1, const float* zb5, f
     a.zb1 = zb1;
     a.zb5 = zb5;
     a.pps = 1;
-    const size_t lds = ((size_t)kH * kMarchTile + (size_t)a.lay.KUp * (kMarchTile + 1) + 16 * kMarchTile + 7 * kH) * sizeof(float);
+    const size_t lds = sdf_fwd_lds_bytes(kMarchTile, a.lay.KUp);
     static SgPerDeviceOnce once;
-    if (once.begin()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(raymarch_step_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        once.end();
-        if (e != hipSuccess) SG_FAIL(SG_ERR_HIP, "sg_raymarch_steps: cannot reserve %zu B LDS", lds);
-    }
+    if (const int rc = sg_reserve_lds(once, raymarch_step_kernel, lds, "sg_raymarch_steps")) return rc;
     MarchArgs m = march_args(pos, dir, dir_period, status, active, nrays, counts, seg_off, nseg, nshapes, first_iter);
     m.clampv = clampv;
     m.threshold = threshold;

@@ -402,20 +402,8 @@ __device__ __forceinline__ void sdfnet_bwd_tile2(const SdfBwdArgs& a, const long
     };
     // this lane's element q of a chain's tile: row wave*32 + frag_row(q, kh), point r
     lds_float* const gw[2] = {(lds_float*)G0 + (wave * 32 + 4 * kh) * kLdg + r, (lds_float*)G1 + (wave * 32 + 4 * kh) * kLdg + r};
-    auto rowoff = [](int q) { return (q & 3) + 8 * (q >> 2); };
 
     // ---- the w8 gradient partial and dZ7 = (w8 (x) dz8) * (H7 > 0), both chains at once (once per tile) ----
-    auto dpp_add = [&](float v, auto ctrl, auto rowmask) __attribute__((always_inline)) {
-        return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), decltype(ctrl)::value,
-                                                                         decltype(rowmask)::value, 0xf, false));
-    };
-    auto half_sum = [&](float v) __attribute__((always_inline)) {
-        v = dpp_add(v, IntTag<0xB1>(), IntTag<0xf>());
-        v = dpp_add(v, IntTag<0x4E>(), IntTag<0xf>());
-        v = dpp_add(v, IntTag<0x141>(), IntTag<0xf>());
-        v = dpp_add(v, IntTag<0x140>(), IntTag<0xf>());
-        return dpp_add(v, IntTag<0x142>(), IntTag<0xa>());
-    };
     WRing<RING> wr;
     auto pack_rsrc = [&](long toff) __attribute__((always_inline)) {
         const unsigned long long wq = (unsigned long long)(pk + (toff >> 2) + (long)wave * (kH / 8) * 64);
@@ -428,7 +416,7 @@ __device__ __forceinline__ void sdfnet_bwd_tile2(const SdfBwdArgs& a, const long
     auto norm_loads = [&](int i) __attribute__((always_inline)) {
         const __amdgpu_buffer_rsrc_t xres = layer_rsrc(a.acts, i);
 #pragma unroll
-        for (int q = 0; q < 16; ++q) xh[q] = buf_load(xres, hload[0], (unsigned)(rowoff(q) * a.ldn * 4));
+        for (int q = 0; q < 16; ++q) xh[q] = buf_load(xres, hload[0], (unsigned)(frag_rowoff(q) * a.ldn * 4));
         gbv = (a.packed + (kh ? a.lay.Be : a.lay.G))[i * kH + wave * 32 + r];
         rsi = pok[0] ? sdf_rstd_base(a.acts, a.ldn)[(long)i * a.ldn + p0 + r] : 0.f;
     };
@@ -444,10 +432,10 @@ __device__ __forceinline__ void sdfnet_bwd_tile2(const SdfBwdArgs& a, const long
             const float gq = GBs[wave * 64 + frag_row(q, kh)];
             const float dy = ((mk[0] >> q) & 1u) ? acc[0][q] : 0.f;
             if (nsums) {
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, half_sum(dy * xh[q])), gres, (int)bsoff,
-                                                      (int)(rowoff(q) * 4), 0);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, half_sum(dy)), bres, (int)bsoff,
-                                                      (int)(rowoff(q) * 4), 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, half_wave_sum(dy * xh[q])), gres, (int)bsoff,
+                                                      (int)(frag_rowoff(q) * 4), 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, half_wave_sum(dy)), bres, (int)bsoff,
+                                                      (int)(frag_rowoff(q) * 4), 0);
             }
             const float dyh = dy * gq;
             acc[0][q] = dyh;
@@ -474,8 +462,8 @@ __device__ __forceinline__ void sdfnet_bwd_tile2(const SdfBwdArgs& a, const long
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
             const float g = rsi * ((acc[0][q] - m1) - xh[q] * m2);
-            gw[0][rowoff(q) * kLdg] = g;
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, g), zres, (int)zstore[0], (int)(rowoff(q) * a.ldn * 4), SG_IMG_AUX);
+            gw[0][frag_rowoff(q) * kLdg] = g;
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, g), zres, (int)zstore[0], (int)(frag_rowoff(q) * a.ldn * 4), SG_IMG_AUX);
         }
     };
     if constexpr (NORM) {
@@ -495,8 +483,8 @@ __device__ __forceinline__ void sdfnet_bwd_tile2(const SdfBwdArgs& a, const long
             const float gq = GBs[wave * 64 + row], bq = GBs[wave * 64 + 32 + row];
             const float h = pok[0] ? fmaxf(fmaf(gq, xh[q], bq), 0.f) : 0.f;
             if (ext)
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, half_sum(h * d8)), w8res, (int)bsoff,
-                                                      (int)(rowoff(q) * 4), 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, half_wave_sum(h * d8)), w8res, (int)bsoff,
+                                                      (int)(frag_rowoff(q) * 4), 0);
             acc[0][q] = pok[0] ? w8[wave * 32 + row] * d8 : 0.f;
         }
         norm_part1(6);
@@ -508,7 +496,7 @@ __device__ __forceinline__ void sdfnet_bwd_tile2(const SdfBwdArgs& a, const long
 #pragma unroll
         for (int q = 0; q < 16; ++q)
 #pragma unroll
-            for (int h = 0; h < NH; ++h) hf[q][h] = buf_load(hres, hload[h], (unsigned)(rowoff(q) * a.ldn * 4));
+            for (int h = 0; h < NH; ++h) hf[q][h] = buf_load(hres, hload[h], (unsigned)(frag_rowoff(q) * a.ldn * 4));
         // (the first weight ring behind the H7 loads: its wait then covers them)
         wring_start(wr, pk + (a.lay.T7 >> 2) + (long)wave * (kH / 8) * 64, lane);
         __builtin_amdgcn_sched_barrier(0);
@@ -526,13 +514,13 @@ __device__ __forceinline__ void sdfnet_bwd_tile2(const SdfBwdArgs& a, const long
                 const bool on = pok[h] && hf[q][h] > 0.f;
                 const float g = on ? wv * d8 : 0.f;
                 s8 = fmaf(pok[h] ? hf[q][h] : 0.f, d8, s8);
-                gw[h][rowoff(q) * kLdg] = g;
+                gw[h][frag_rowoff(q) * kLdg] = g;
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, g), zres, (int)zstore[h],
-                                                      (int)(rowoff(q) * a.ldn * 4), SG_IMG_AUX);
+                                                      (int)(frag_rowoff(q) * a.ldn * 4), SG_IMG_AUX);
             }
             if (ext)
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, half_sum(s8)), w8res, (int)bsoff,
-                                                      (int)(rowoff(q) * 4), 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, half_wave_sum(s8)), w8res, (int)bsoff,
+                                                      (int)(frag_rowoff(q) * 4), 0);
         }
     }
     __syncthreads();
@@ -588,7 +576,7 @@ __device__ __forceinline__ void sdfnet_bwd_tile2(const SdfBwdArgs& a, const long
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             if (i < n) {
-                const float t = dpp_add(rs[i], IntTag<0xB1>(), IntTag<0xf>());
+                const float t = dpp_add<0xB1, 0xf>(rs[i]);
                 if (ssub == 0) a.bsum[(long)blockIdx.x * prow + (i == 0 ? blk : xblk + i - 1) * kH + srow] = t;
             }
         }
@@ -597,9 +585,9 @@ __device__ __forceinline__ void sdfnet_bwd_tile2(const SdfBwdArgs& a, const long
     // ---- epilogue of chain h for image `layer`, element q: dZ = acc * ReLU'(H) -> LDS tile, dz image ----
     auto epi_q = [&](int h, int q, const __amdgpu_buffer_rsrc_t zres) __attribute__((always_inline)) {
         const float g = ((mk[h] >> q) & 1u) ? acc[h][q] : 0.f;
-        gw[h][rowoff(q) * kLdg] = g;
+        gw[h][frag_rowoff(q) * kLdg] = g;
 #ifndef SG_ABL_NOSTORE
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, g), zres, (int)zstore[h], (int)(rowoff(q) * a.ldn * 4), SG_IMG_AUX);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, g), zres, (int)zstore[h], (int)(frag_rowoff(q) * a.ldn * 4), SG_IMG_AUX);
 #endif
     };
     auto zero = [&](int h) __attribute__((always_inline)) {
@@ -1056,9 +1044,6 @@ constexpr int kFinishMaxSplit = 32;
 constexpr long kFwdSlots = kCUs;       // one workgroup per CU (LDS)
 constexpr long kBwdSlots = 2 * kCUs;   // two per CU
 
-static size_t fwd_lds_bytes(int P, int KUp, bool norm = false) {
-    return ((size_t)kH * P + (size_t)KUp * (P + 1) + 16 * P + 7 * kH + (norm ? 8 * 64 : 0)) * sizeof(float);
-}
 static size_t bwd_lds_bytes(int P, int KUr, bool dx) { return ((size_t)2 * kH * kLdg + 4 * 64) * sizeof(float); }   // two chains [256][kLdg] + dz8 + xyz
 static size_t bwd_lds_bytes_norm() { return ((size_t)2 * kH * kLdg + 4 * 64 + 16 * 64) * sizeof(float); }   // + per-point means + gamma / beta
 
@@ -1204,7 +1189,7 @@ int sg_sdfgen_fwd(const float* points, const float* packed, const float* zb1, co
     a.eps = eps;
     if (acts) SG_CHECK_ARG(ldn >= N);
     if (acts && ldn > (1L << 24)) SG_FAIL(SG_ERR_ARG, "sg_sdfgen_fwd: at most 16 777 216 points per training call (ldn = %ld)", ldn);
-    const size_t lds = fwd_lds_bytes(64, a.lay.KUp, true);
+    const size_t lds = sdf_fwd_lds_bytes(64, a.lay.KUp, true);
     const TilePlan tp = tile_plan(N, 64, 2 * kFwdSlots);
     a.nbig = tp.nbig;
     const dim3 grid((unsigned)(tp.nbig + tp.nsmall));
@@ -1253,7 +1238,7 @@ int sg_sdfnet_fwd(const float* points, long points_period, const float* latent, 
         // 64-point tiles: 68 KB of LDS and < 128 VGPRs put two workgroups on a CU, so that one's barriers / write-back overlap
         // the other's MFMA phases (measured against 128-point tiles, one workgroup per CU: 8 x 32^3 inference 1.687 -> 1.654 ms,
         // 16 x 64^3 26.0 -> 25.0 ms, the training forward at 200 000 points 1.31 -> 1.24 ms)
-        const size_t lds = fwd_lds_bytes(64, a.lay.KUp);
+        const size_t lds = sdf_fwd_lds_bytes(64, a.lay.KUp);
         const TilePlan tp = tile_plan(N, 64, 2 * kFwdSlots);
         a.nbig = tp.nbig;
         const dim3 grid((unsigned)(tp.nbig + tp.nsmall));
@@ -1270,7 +1255,7 @@ int sg_sdfnet_fwd(const float* points, long points_period, const float* latent, 
         }
     } else {
         SG_CHECK_ARG(latent && kin_used == 3 + latent_size);
-        const size_t lds = fwd_lds_bytes(64, a.lay.KUp);
+        const size_t lds = sdf_fwd_lds_bytes(64, a.lay.KUp);
         if (lds > 160 * 1024) SG_FAIL(SG_ERR_ARG, "sg_sdfnet_fwd: latent size %d needs %zu B LDS (> 160 KiB)", latent_size, lds);
         const TilePlan tp = tile_plan(N, 64, kFwdSlots);
         a.nbig = tp.nbig;

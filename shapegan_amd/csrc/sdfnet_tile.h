@@ -1,6 +1,8 @@
 // shapegan_amd/csrc/sdfnet_tile.h — the forward tile of the fused SDFNet MLP (sdfnet.hip) and what it runs on: the packed
 // weight layout, the MFMA GEMM loops and sdfnet_fwd_tile.  A header so that a kernel in another file can run the same eight
-// layers on its own points (the sphere tracer, raymarch.hip); sdfnet.hip holds the kernels and entry points of the MLP itself.
+// layers on its own points; sdfnet.hip holds the kernels and entry points of the MLP itself.  Users: sdfnet.hip (sg_sdfnet_fwd /
+// sg_sdfgen_fwd and, for the fragment helpers, the training backward), raymarch.hip (the sphere tracer) and, through
+// sdfnet_frozen.h, latent_fit.hip (K7c) and sdfnet_project.hip (K7d), which also run the chain back on the tile.
 #pragma once
 #include "common.h"
 
@@ -175,7 +177,23 @@ __device__ __forceinline__ void mlp_gemm_ring(f32x16 (&acc)[NT], WRing<RING>& w,
     }
 }
 
-__device__ __forceinline__ int frag_row(int q, int kh) { return (q & 3) + 8 * (q >> 2) + 4 * kh; }
+// row of accumulator element q of a 32x32 MFMA tile for the half-wave kh; frag_rowoff: the part a lane that has 4 kh in its base adds
+__device__ __forceinline__ int frag_rowoff(int q) { return (q & 3) + 8 * (q >> 2); }
+__device__ __forceinline__ int frag_row(int q, int kh) { return frag_rowoff(q) + 4 * kh; }
+
+// v + (v of another lane), the lane picked by a DPP control; half_wave_sum: lane 31 / 63 ends up with the sum over its half-wave
+// (the 32 points of a column tile)
+template <int CTRL, int ROWMASK>
+__device__ __forceinline__ float dpp_add(float v) {
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROWMASK, 0xf, false));
+}
+__device__ __forceinline__ float half_wave_sum(float v) {
+    v = dpp_add<0xB1, 0xf>(v);
+    v = dpp_add<0x4E, 0xf>(v);
+    v = dpp_add<0x141, 0xf>(v);
+    v = dpp_add<0x140, 0xf>(v);
+    return dpp_add<0x142, 0xa>(v);
+}
 
 // The activation buffer of a training call: [7][256][ldn] fp32 images H1..H7 followed by the sign masks, unsigned short
 // [7][16][ldn]: bit q of masks[l][2 w + kh][p] = (H_{l+1}[32 w + frag_row(q, kh)][p] > 0)  (sg_sdfnet_acts_floats in the header).
@@ -235,7 +253,13 @@ struct SdfPointIo {
 };
 
 // KEEP: the sign word of every hidden layer (the one TRAIN stores to `acts`, same bit order) is handed to io.keep(layer, words) instead
-// of memory — for a kernel that runs the backward chain of the tile itself (latent_fit.hip).  Off in every other instantiation.
+// of memory — for a kernel that runs the backward chain of the tile itself (sdfnet_frozen.h).  Off in every other instantiation.
+// The tile's dynamic LDS, the size every kernel that calls sdfnet_fwd_tile launches with: H [256][P], X [KUp][P + 1], the layer-8
+// partials [16][P], the biases [7][256] and, NORM, gamma / beta of the layer in flight [8][64].
+static size_t sdf_fwd_lds_bytes(int P, int KUp, bool norm = false) {
+    return ((size_t)kH * P + (size_t)KUp * (P + 1) + 16 * P + 7 * kH + (norm ? 8 * 64 : 0)) * sizeof(float);
+}
+
 template <int P, bool SHAPE_BIAS, bool TRAIN, bool NORM = false, class Io = SdfPointIo<NORM>, bool KEEP = false>   // TRAIN: `acts` is given (H images + sign masks are written)
 __device__ __forceinline__ void sdfnet_fwd_tile(const SdfFwdArgs& a, const long p0, const Io& io = Io()) {
     constexpr int NT = P / 32;
@@ -416,7 +440,7 @@ __device__ __forceinline__ void sdfnet_fwd_tile(const SdfFwdArgs& a, const long 
                 Hs[row * P + t * 32 + r] = v;
                 if (save)
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, img), ares, (int)astore[t],
-                                                          (int)(((q & 3) + 8 * (q >> 2)) * a.ldn * 4), SG_IMG_AUX);
+                                                          (int)(frag_rowoff(q) * a.ldn * 4), SG_IMG_AUX);
             }
         }
         if constexpr (TRAIN) {

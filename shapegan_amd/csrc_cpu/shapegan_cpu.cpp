@@ -667,6 +667,42 @@ static inline void dense_t(const float* W, int K, const float* dz, float* dh, bo
         for (int k = 0; k < K; ++k) dh[k] += w[k] * g;
     }
 }
+// ---- one point of one shape with frozen weights, per-shape bias mode (kin_used = 3): the latent fit, the projection, the sphere tracer
+// weights of hidden layer l + 1, l = 1 .. 6 (its bias is v.b + 256 l; layer 5 takes zb5 and adds the point columns W5i instead)
+static inline const float* sdf_hidden_w(const CpuSdf& v, int l) {
+    const float* W[7] = {nullptr, v.W2, v.W3, v.W4, v.W5x, v.W6, v.W7};
+    return W[l];
+}
+// the forward of sg_sdfnet_fwd_cpu for point x with the shape's bias rows (the same `dense` calls in the same order): h[l] = H_{l+1},
+// returns the pre-activation of the last layer
+static float sdf_shape_point_fwd(const CpuSdf& v, const float* x, const float* zb1_row, const float* zb5_row, float (*h)[256]) {
+    dense(v.W1k, 3, x, zb1_row, h[0], true, false);
+    for (int l = 1; l < 7; ++l) {
+        if (l == 4) {
+            dense(v.W5x, 256, h[3], zb5_row, h[4], false, false);
+            dense(v.W5i, 3, x, nullptr, h[4], true, true);
+        } else {
+            dense(sdf_hidden_w(v, l), 256, h[l - 1], v.b + 256 * l, h[l], true, false);
+        }
+    }
+    float pre = v.b8[0];
+    for (int k = 0; k < 256; ++k) pre += v.w8[k] * h[6][k];
+    return pre;
+}
+// the chain of sg_sdfnet_bwd_cpu from the upstream gradient d8 of the pre-activation, ReLU' read from h: leaves dZ1 in g and calls
+// on_dz5(g) while g is dZ5
+extern "C++" {      // (a template: not in the C-linkage block around it)
+template <class OnDz5>
+static void sdf_shape_point_chain(const CpuSdf& v, const float (*h)[256], float d8, float* g, OnDz5 on_dz5) {
+    float gn[256];
+    for (int r = 0; r < 256; ++r) g[r] = h[6][r] > 0.f ? v.w8[r] * d8 : 0.f;
+    for (int layer = 5; layer >= 0; --layer) {
+        dense_t(sdf_hidden_w(v, layer + 1), 256, g, gn, false);
+        for (int r = 0; r < 256; ++r) g[r] = h[layer][r] > 0.f ? gn[r] : 0.f;
+        if (layer == 4) on_dz5(g);
+    }
+}
+}
 // the header's tile layout of the backward partials (sg_sdfnet_bwd_blocks / sg_sdfnet_bwd_tile_start)
 static void sdf_bwd_plan(long N, long& nbig, long& nsmall) {
     const long tiles = (N + 63) / 64, rem = tiles % 512, full = tiles - rem;
@@ -865,8 +901,6 @@ int sg_sdfnet_latent_grad_cpu(const float* points, const float* target, const in
     CPU_CHECK(nshapes >= 1 && win_start >= 0 && ntiles >= 1 && cutoff >= 0.f);
     for (long s = 0; s < nshapes; ++s) CPU_CHECK(seg_off[s + 1] - seg_off[s] >= 1);
     const CpuSdf v = sdf_view(packed, 3);
-    const float* Wt[7] = {nullptr, v.W2, v.W3, v.W4, v.W5x, v.W6, v.W7};
-    const float* bs[7] = {nullptr, v.b + 256, v.b + 512, v.b + 768, nullptr, v.b + 1280, v.b + 1536};
 #pragma omp parallel for schedule(dynamic)
     for (long t = 0; t < ntiles; ++t) {
         float* prow = partials + t * SG_SDFNET_LATENT_PARTIAL_ROW;
@@ -881,31 +915,15 @@ int sg_sdfnet_latent_grad_cpu(const float* points, const float* target, const in
         float labs = 0.f;
         for (long i = 0; i < cnt; ++i) {
             const long pi = beg + (win_start + i0 + i) % n;
-            float h[7][256], g[256], gn[256];
-            const float* x = points + pi * 3;
-            dense(v.W1k, 3, x, zb1 + s * 256, h[0], true, false);
-            for (int l = 1; l < 7; ++l) {
-                if (l == 4) {
-                    dense(v.W5x, 256, h[3], zb5 + s * 256, h[4], false, false);
-                    dense(v.W5i, 3, x, nullptr, h[4], true, true);
-                } else {
-                    dense(Wt[l], 256, h[l - 1], bs[l], h[l], true, false);
-                }
-            }
-            float pre = v.b8[0];
-            for (int k = 0; k < 256; ++k) pre += v.w8[k] * h[6][k];
-            const float o = tanhf(pre);
+            float h[7][256], g[256];
+            const float o = tanhf(sdf_shape_point_fwd(v, points + pi * 3, zb1 + s * 256, zb5 + s * 256, h));
             const float tg = fminf(fmaxf(target[pi], -cutoff), cutoff);
             const float d = o - tg;
             labs += fabsf(d);
             const float d8 = (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * ((1.f - o * o) / (float)m);
-            for (int r = 0; r < 256; ++r) g[r] = h[6][r] > 0.f ? v.w8[r] * d8 : 0.f;
-            for (int layer = 5; layer >= 0; --layer) {
-                dense_t(Wt[layer + 1], 256, g, gn, false);
-                for (int r = 0; r < 256; ++r) g[r] = h[layer][r] > 0.f ? gn[r] : 0.f;
-                if (layer == 4)
-                    for (int r = 0; r < 256; ++r) s5[r] += g[r];
-            }
+            sdf_shape_point_chain(v, h, d8, g, [&](const float* dz5) {
+                for (int r = 0; r < 256; ++r) s5[r] += dz5[r];
+            });
             for (int r = 0; r < 256; ++r) s1[r] += g[r];
         }
         for (int r = 0; r < 256; ++r) {
@@ -2060,18 +2078,8 @@ int sg_topo_keep_emit_cpu(const float* vertices, const float* normals, const int
 // order: the sets are the same).
 // pre-activation of the last layer for one point, per-shape mode (packed of sg_sdfnet_pack_shape_bias_cpu, kin_used = 3)
 static float rm_sdf_pre(const CpuSdf& v, const float* x, const float* zb1, const float* zb5) {
-    float h[256], h2[256];
-    dense(v.W1k, 3, x, zb1, h, true, false);
-    dense(v.W2, 256, h, v.b + 256, h2, true, false);
-    dense(v.W3, 256, h2, v.b + 512, h, true, false);
-    dense(v.W4, 256, h, v.b + 768, h2, true, false);
-    dense(v.W5x, 256, h2, zb5, h, false, false);
-    dense(v.W5i, 3, x, nullptr, h, true, true);
-    dense(v.W6, 256, h, v.b + 1280, h2, true, false);
-    dense(v.W7, 256, h2, v.b + 1536, h, true, false);
-    float s = v.b8[0];
-    for (int k = 0; k < 256; ++k) s += v.w8[k] * h[k];
-    return s;
+    float h[7][256];
+    return sdf_shape_point_fwd(v, x, zb1, zb5, h);
 }
 
 int sg_raymarch_rays_cpu(const double* camera, int width, long nshapes, double radius, float* dir, float* pos, unsigned char* status,
@@ -2984,8 +2992,6 @@ int sg_sdfnet_project_cpu(const float* points, const int64_t* seg_off, long nsha
     CPU_CHECK(iterations >= 0 && iterations <= 64 && (rule == SG_PROJECT_RULE_NEWTON || rule == SG_PROJECT_RULE_UNIT));
     CPU_CHECK(max_step >= 0.f && (out_points || iterations == 0));
     const CpuSdf v = sdf_view(packed, 3);
-    const float* Wt[7] = {nullptr, v.W2, v.W3, v.W4, v.W5x, v.W6, v.W7};
-    const float* bs[7] = {nullptr, v.b + 256, v.b + 512, v.b + 768, nullptr, v.b + 1280, v.b + 1536};
 #pragma omp parallel for schedule(dynamic)
     for (long t = 0; t < ntiles; ++t) {
         const long s = tiles[2 * t], i0 = tiles[2 * t + 1];
@@ -3002,26 +3008,9 @@ int sg_sdfnet_project_cpu(const float* points, const int64_t* seg_off, long nsha
             float* x = xs[i];
             float o = 0.f, gp[3] = {0.f, 0.f, 0.f};
             for (int round = 0; round <= iterations; ++round) {
-                float h[7][256], g[256], gn[256];
-                dense(v.W1k, 3, x, zb1 + s * 256, h[0], true, false);
-                for (int l = 1; l < 7; ++l) {
-                    if (l == 4) {
-                        dense(v.W5x, 256, h[3], zb5 + s * 256, h[4], false, false);
-                        dense(v.W5i, 3, x, nullptr, h[4], true, true);
-                    } else {
-                        dense(Wt[l], 256, h[l - 1], bs[l], h[l], true, false);
-                    }
-                }
-                float pre = v.b8[0];
-                for (int k = 0; k < 256; ++k) pre += v.w8[k] * h[6][k];
-                o = tanhf(pre);
-                const float d8 = 1.f - o * o;
-                for (int r = 0; r < 256; ++r) g[r] = h[6][r] > 0.f ? v.w8[r] * d8 : 0.f;
-                for (int layer = 5; layer >= 0; --layer) {
-                    dense_t(Wt[layer + 1], 256, g, gn, false);
-                    for (int r = 0; r < 256; ++r) g[r] = h[layer][r] > 0.f ? gn[r] : 0.f;
-                    if (layer == 4) dense_t(v.W5i, 3, g, gp, false);      // g is dZ5 here
-                }
+                float h[7][256], g[256];
+                o = tanhf(sdf_shape_point_fwd(v, x, zb1 + s * 256, zb5 + s * 256, h));
+                sdf_shape_point_chain(v, h, 1.f - o * o, g, [&](const float* dz5) { dense_t(v.W5i, 3, dz5, gp, false); });
                 dense_t(v.W1k, 3, g, gp, true);
                 if (round < iterations) sg_project_step(x, o, gp, level, rule, max_step);
             }

@@ -7,9 +7,11 @@ without any extra kernel — convolution and matmul are bilinear, LeakyReLU's de
 PyTorch is used for storage (device tensors), the autograd tape and stream handles only; all arithmetic on the
 hot path runs in libshapegan_hip.so.  There is no CPU fallback: tensors must live on the GPU.
 """
+import contextlib
 import ctypes
 import weakref
 
+import numpy as np
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -1023,7 +1025,6 @@ class _SideStream(object):
 
     def run(self):
         """Context in which launches go to the side stream (a plain no-op context for CPU tensors)."""
-        import contextlib
         return torch.cuda.stream(self.side) if self.side is not None else contextlib.nullcontext()
 
     def __exit__(self, *exc):
@@ -1067,7 +1068,6 @@ def _sdf_param_grads(ctx_params, needs, dz, dz8, acts, ldn, N, x_parts, kin_tota
     w8 = _param_grad_out(ctx_params[14], (1, _H), dev)
     b8 = _param_grad_out(ctx_params[15], (1,), dev)
     if bsum is not None:
-        import contextlib
         with (side.run() if side is not None else contextlib.nullcontext()):      # (under the GEMM batch below when a side stream is given)
             arr = (ctypes.c_void_p * 7)(*[ptr(t) for t in bouts])
             ws = workspace("sdf_finish", lib.sg_sdfnet_bwd_finish_workspace_bytes(N), dev)
@@ -1273,7 +1273,6 @@ class SDFNetShapes(Function):
                 # backward of the latent fold in one launch: latent columns dW1[:, 3:] = T1 @ z, dW5[:, 259:] = T5 @ z and the
                 # latent gradient gz = T1^T W1[:, 3:] + T5^T W5[:, 259:]
                 w1, w5 = f32c(params[0]), f32c(params[8])
-                import contextlib
                 with (overlap.run() if overlap is not None else contextlib.nullcontext()):
                     rw, rs = ctx.reg if (ctx.reg is not None and need_z) else (None, 0.0)
                     check(lib.sg_sdfnet_shape_bias_bwd(ptr(t1), ptr(t5), S, ptr(z), Lz, ptr(w1), ptr(w5),
@@ -1282,22 +1281,18 @@ class SDFNetShapes(Function):
         finally:
             if overlap is not None:
                 overlap.__exit__(None, None, None)
-        if fold:
-            pass
-        else:
-            if need_p:
-                gemm_raw(t1, False, z, False, out=grads[0], M=_H, N=Lz, K=S, lda=S, ldb=Lz, ldc=kin_total, c_off=3)
-                gemm_raw(t5, False, z, False, out=grads[8], M=_H, N=Lz, K=S, lda=S, ldb=Lz, ldc=_H + kin_total,
-                         c_off=_H + 3)
-            if need_z:
-                w1, w5 = f32c(params[0]), f32c(params[8])
-                g1 = gemm_raw(t1, True, w1, False, b_off=3, M=S, N=Lz, K=_H, lda=S, ldb=kin_total)
-                g5 = gemm_raw(t5, True, w5, False, b_off=_H + 3, M=S, N=Lz, K=_H, lda=S, ldb=_H + kin_total)
-                gz = _param_grad_out(z, g1.shape, dev)
-                check(lib.sg_axpby(ptr(g1), ptr(g5), ptr(gz), g1.numel(), 1.0, 1.0, stream()), "axpby")
-                if ctx.reg is not None:      # (more shapes than the one-launch fold takes: the regulariser's gradient as a torch op)
-                    rw, rs = ctx.reg
-                    gz += (z * rs) if rw is None else (z * (rw * rs).unsqueeze(1))
+        if not fold and need_p:
+            gemm_raw(t1, False, z, False, out=grads[0], M=_H, N=Lz, K=S, lda=S, ldb=Lz, ldc=kin_total, c_off=3)
+            gemm_raw(t5, False, z, False, out=grads[8], M=_H, N=Lz, K=S, lda=S, ldb=Lz, ldc=_H + kin_total, c_off=_H + 3)
+        if not fold and need_z:
+            w1, w5 = f32c(params[0]), f32c(params[8])
+            g1 = gemm_raw(t1, True, w1, False, b_off=3, M=S, N=Lz, K=_H, lda=S, ldb=kin_total)
+            g5 = gemm_raw(t5, True, w5, False, b_off=_H + 3, M=S, N=Lz, K=_H, lda=S, ldb=_H + kin_total)
+            gz = _param_grad_out(z, g1.shape, dev)
+            check(lib.sg_axpby(ptr(g1), ptr(g5), ptr(gz), g1.numel(), 1.0, 1.0, stream()), "axpby")
+            if ctx.reg is not None:      # (more shapes than the one-launch fold takes: the regulariser's gradient as a torch op)
+                rw, rs = ctx.reg
+                gz += (z * rs) if rw is None else (z * (rw * rs).unsqueeze(1))
         return (None, dx, gz, None, None, None, None, None) + tuple(grads)
 
 
@@ -1307,22 +1302,52 @@ _LATENT_ROW = 2 * _H + 1      # SG_SDFNET_LATENT_PARTIAL_ROW
 _LATENT_MAX_SHAPES = 6144     # what sg_sdfnet_shape_bias_bwd takes in one call; more shapes go in chunks (shapes are independent)
 
 
-def check_segments(points, sdf, latent_table, segment_offsets):
-    """The argument checks of the latent fit, before anything is launched: returns the run bounds as a host int64 array."""
-    import numpy as np
+def _check_points(points):
     if points.dim() != 2 or points.shape[1] != 3:
         raise ValueError("points must be [N, 3], got %s" % (tuple(points.shape),))
+
+
+def _check_offsets(segment_offsets, npoints, nshapes, rows_of):
+    """What the latent fit and the projector ask of the run bounds alike: returns them as a host int64 array.  `rows_of`: the
+    argument with one row per shape (for the message)."""
+    if segment_offsets.dim() != 1 or segment_offsets.dtype != torch.int64 or segment_offsets.numel() < 2:
+        raise ValueError("segment_offsets must be int64 [S + 1] with S >= 1")
+    if segment_offsets.numel() - 1 != nshapes:
+        raise ValueError("%s has %d rows for %d shapes" % (rows_of, nshapes, segment_offsets.numel() - 1))
+    off = segment_offsets.detach().cpu().numpy().astype(np.int64)
+    if off[0] < 0 or off[-1] > npoints:
+        raise ValueError("segment_offsets reach outside the %d points" % npoints)
+    return off
+
+
+def _shape_chunks(nshapes, limit):
+    """The shapes [a, b) of one launch each, at most `limit` shapes at a time (shapes are independent: chunked or not, equal bits)."""
+    for a in range(0, nshapes, limit):
+        yield a, min(nshapes, a + limit)
+
+
+def _shape_tiles(off, a, b, tile, count=0):
+    """The tile table of the shapes [a, b) with the run bounds `off`: tiles int32 [T, 2] = (shape - a, first used point), `tile`
+    points each over the first min(n, count) points of every run (count <= 0: all n), none for an empty run and none across two
+    shapes; tile_off int64 [b - a + 1]: the tiles of shape s are [tile_off[s - a], tile_off[s - a + 1])."""
+    n = np.diff(off[a:b + 1])
+    m = n if count <= 0 else np.minimum(n, count)
+    nt = (m + tile - 1) // tile
+    tile_off = np.zeros(b - a + 1, dtype=np.int64)
+    tile_off[1:] = np.cumsum(nt)
+    shape = np.repeat(np.arange(b - a, dtype=np.int64), nt)
+    first = (np.arange(tile_off[-1], dtype=np.int64) - tile_off[shape]) * tile
+    return np.stack([shape, first], axis=1).astype(np.int32), tile_off
+
+
+def check_segments(points, sdf, latent_table, segment_offsets):
+    """The argument checks of the latent fit, before anything is launched: returns the run bounds as a host int64 array."""
+    _check_points(points)
     if sdf.dim() != 1 or sdf.shape[0] != points.shape[0]:
         raise ValueError("sdf must be [N] = [%d], got %s" % (points.shape[0], tuple(sdf.shape)))
     if latent_table.dim() != 2 or latent_table.shape[1] < 1:
         raise ValueError("latent_table must be [S, L], got %s" % (tuple(latent_table.shape),))
-    if segment_offsets.dim() != 1 or segment_offsets.dtype != torch.int64 or segment_offsets.numel() < 2:
-        raise ValueError("segment_offsets must be int64 [S + 1] with S >= 1")
-    if segment_offsets.numel() - 1 != latent_table.shape[0]:
-        raise ValueError("latent_table has %d rows for %d shapes" % (latent_table.shape[0], segment_offsets.numel() - 1))
-    off = segment_offsets.detach().cpu().numpy().astype(np.int64)
-    if off[0] < 0 or off[-1] > points.shape[0]:
-        raise ValueError("segment_offsets reach outside the %d points" % points.shape[0])
+    off = _check_offsets(segment_offsets, points.shape[0], latent_table.shape[0], "latent_table")
     if (np.diff(off) < 1).any():
         raise ValueError("shape %d has no points" % int(np.argmax(np.diff(off) < 1)))
     return off
@@ -1346,20 +1371,11 @@ class LatentFit(object):
         self.plans = {}
 
     def _plan(self, count):
-        import numpy as np
         plan = self.plans.get(count)
         if plan is None:
             plan = []
-            for a in range(0, self.S, _LATENT_MAX_SHAPES):
-                b = min(self.S, a + _LATENT_MAX_SHAPES)
-                n = np.diff(self.off[a:b + 1])
-                m = n if count <= 0 else np.minimum(n, count)
-                nt = (m + _LATENT_TILE - 1) // _LATENT_TILE
-                tile_off = np.zeros(b - a + 1, dtype=np.int64)
-                tile_off[1:] = np.cumsum(nt)
-                shape = np.repeat(np.arange(b - a, dtype=np.int64), nt)
-                first = (np.arange(tile_off[-1], dtype=np.int64) - tile_off[shape]) * _LATENT_TILE
-                tiles = np.stack([shape, first], axis=1).astype(np.int32)
+            for a, b in _shape_chunks(self.S, _LATENT_MAX_SHAPES):
+                tiles, tile_off = _shape_tiles(self.off, a, b, _LATENT_TILE, count)
                 plan.append((a, b, torch.from_numpy(tiles).to(self.dev), torch.from_numpy(tile_off).to(self.dev), int(tile_off[-1])))
             self.plans[count] = plan
         return plan
@@ -1396,7 +1412,7 @@ class LatentFit(object):
 
 # ---- points onto a level set: value, point gradient and Newton steps with the weights frozen (csrc/sdfnet_project.hip) -------------
 _PROJECT_TILE = 32                 # SG_SDFNET_PROJECT_TILE
-_PROJECT_MAX_SHAPES = 6144         # shapes per launch, the chunks of LatentFit (shapes are independent: chunked or not, equal bits)
+_PROJECT_MAX_SHAPES = 6144         # shapes per launch, the chunks of LatentFit (_shape_chunks)
 _PROJECT_MAX_ITERATIONS = 64
 PROJECT_RULES = {"newton": 0, "unit": 1}      # SG_PROJECT_RULE_*: d / |g|^2, or the reference's d / |g| (model/sdf_net.py:146)
 
@@ -1404,21 +1420,13 @@ PROJECT_RULES = {"newton": 0, "unit": 1}      # SG_PROJECT_RULE_*: d / |g|^2, or
 def check_point_segments(points, nshapes, segment_offsets):
     """The argument checks of SurfaceProjector, before anything is launched: returns the run bounds as a host int64 array.
     segment_offsets None: the shapes own equal runs of the points, in order."""
-    import numpy as np
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError("points must be [N, 3], got %s" % (tuple(points.shape),))
+    _check_points(points)
     N = points.shape[0]
     if segment_offsets is None:
         if N < nshapes or N % nshapes != 0:
             raise ValueError("%d points do not divide among %d shapes: pass segment_offsets" % (N, nshapes))
         return np.arange(nshapes + 1, dtype=np.int64) * (N // nshapes)
-    if segment_offsets.dim() != 1 or segment_offsets.dtype != torch.int64 or segment_offsets.numel() < 2:
-        raise ValueError("segment_offsets must be int64 [S + 1] with S >= 1")
-    if segment_offsets.numel() - 1 != nshapes:
-        raise ValueError("latent_codes has %d rows for %d shapes" % (nshapes, segment_offsets.numel() - 1))
-    off = segment_offsets.detach().cpu().numpy().astype(np.int64)
-    if off[0] < 0 or off[-1] > N:
-        raise ValueError("segment_offsets reach outside the %d points" % N)
+    off = _check_offsets(segment_offsets, N, nshapes, "latent_codes")
     if (np.diff(off) < 0).any():
         raise ValueError("segment_offsets must not decrease")
     return off
@@ -1441,14 +1449,8 @@ class SurfaceProjector(object):
 
     @staticmethod
     def _tiles(off, a, b):
-        import numpy as np
-        n = np.diff(off[a:b + 1])
-        nt = (n + _PROJECT_TILE - 1) // _PROJECT_TILE
-        start = np.zeros(b - a + 1, dtype=np.int64)
-        start[1:] = np.cumsum(nt)
-        shape = np.repeat(np.arange(b - a, dtype=np.int64), nt)
-        first = (np.arange(start[-1], dtype=np.int64) - start[shape]) * _PROJECT_TILE
-        return np.stack([shape, first], axis=1).astype(np.int32)
+        """The tile table [T, 2] of the shapes [a, b) for a raw sg_sdfnet_project call (all points of every run)."""
+        return _shape_tiles(off, a, b, _PROJECT_TILE)[0]
 
     def run(self, points, off, seg_off, level=0.0, iterations=0, rule="newton", max_step=0.0, out_points=None):
         """out_points: None (a new tensor when iterations > 0, else `points` itself is returned) or the tensor to write, which may
@@ -1477,8 +1479,7 @@ class SurfaceProjector(object):
         else:
             out = torch.empty_like(pts) if covered else pts.clone()
         lib = _lib()
-        for a in range(0, self.S, _PROJECT_MAX_SHAPES):
-            b = min(self.S, a + _PROJECT_MAX_SHAPES)
+        for a, b in _shape_chunks(self.S, _PROJECT_MAX_SHAPES):
             tiles = self._tiles(off, a, b)
             if tiles.shape[0] == 0:
                 continue
@@ -1506,7 +1507,6 @@ class LatentFitComposed(object):
         self.plans = {}
 
     def _plan(self, count):
-        import numpy as np
         plan = self.plans.get(count)
         if plan is None:
             S, dev = self.S, self.dev

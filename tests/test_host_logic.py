@@ -575,3 +575,37 @@ def test_grouped_generator_pass_refuses_an_unserved_last_layer_before_touching_b
     with torch.no_grad():
         assert stack.run_stack_groups(layers, x, 3, outs) is False       # 96 channels: not served by sg_convT3d_k4s2p1_to1_pre
     assert int(layers[1].num_batches_tracked) == 0 and torch.equal(layers[1].running_mean, torch.zeros(96))
+
+
+@pytest.mark.parametrize("a,b", [(0, 5), (1, 4)])
+@pytest.mark.parametrize("count", [0, 16, 40])
+def test_shape_tiles_cover_every_used_point_once(count, a, b):
+    """ops._shape_tiles (the tile table of the latent fit and the projector) against a plain double loop: runs of 1, 31, 33, 0 and
+    70 points, whole windows and windows of 16 and 40 points, all shapes and the chunk [1, 4)."""
+    from shapegan_amd import ops
+    off = np.array((0, 1, 32, 65, 65, 135), dtype=np.int64)
+    tiles, tile_off = ops._shape_tiles(off, a, b, 32, count)
+    assert tiles.dtype == np.int32 and tiles.ndim == 2 and tiles.shape[1] == 2
+    assert tile_off.dtype == np.int64 and tile_off.shape == (b - a + 1,)
+    want_tiles, want_off = [], [0]
+    for s in range(a, b):
+        n = int(off[s + 1] - off[s])
+        m = n if count <= 0 else min(n, count)
+        for first in range(0, m, 32):
+            want_tiles.append((s - a, first))
+        want_off.append(len(want_tiles))
+    assert tiles.tolist() == [list(t) for t in want_tiles]
+    assert tile_off.tolist() == want_off
+    seen = [np.zeros(int(off[s + 1] - off[s]), dtype=np.int64) for s in range(a, b)]
+    for s, first in tiles.tolist():
+        assert 0 <= s < b - a and first % 32 == 0
+        n = len(seen[s])
+        m = n if count <= 0 else min(n, count)
+        assert first < m, "a tile without a used point"       # (so an empty run gets none)
+        seen[s][first:min(first + 32, m)] += 1                # the tile ends with its shape's used points: it crosses no shape
+    for s in range(b - a):
+        n = len(seen[s])
+        m = n if count <= 0 else min(n, count)
+        assert (seen[s][:m] == 1).all() and (seen[s][m:] == 0).all()
+        assert tile_off[s + 1] - tile_off[s] == (m + 31) // 32
+        assert (tiles[tile_off[s]:tile_off[s + 1], 0] == s).all()
