@@ -61,7 +61,13 @@ int sg_conv3d_k4s2p1_fwd_keep(const float* x, const float* w, const float* bias,
 long long sg_conv3d_k4s2p1_image_layout(int kind, const int* dims, size_t workspace_bytes);
 int sg_conv3d_k4s2p1_pack_images(int n, const int* kinds, const float* const* weights, void* const* workspaces,
                                  const size_t* workspace_bytes, const int* dims, int* served, hipStream_t stream);
-/* testing / tuning: force one forward implementation (0 = gather implicit GEMM, 1 = LDS-halo implicit GEMM) */
+/* testing / tuning: force one forward implementation (0 = gather implicit GEMM, 1 = LDS-halo implicit GEMM).  debug bit 8 (256)
+ * with impl 1: the depth-skip form of the 8^3 -> 4^3 kernel (conv_fwd_halo4_dskip_kernel; SG_ERR_ARG on other grids); without it a
+ * forced call gets conv_fwd_halo4_kernel.  The dispatching entries take the depth-skip form wherever the 4^3 kernel runs without a
+ * channel split.  Depth-skip forms (forward and input gradient) do not issue the products whose activation operand is the zero
+ * padding beyond the DEPTH range: for finite weights the result is that of the full sum; for a non-finite weight on such a tap the
+ * full sum is NaN (0 x inf) and the depth-skip form returns the convolution's definition, the sum over the in-range positions (as
+ * the weight-gradient skip form does).  The h / w padding is multiplied as before. */
 int sg_conv3d_k4s2p1_fwd_impl(const float* x, const float* w, const float* bias, float* y, int batch, int Cin,
                               int Cin_total, int Cx, int Cout, int ID, int IH, int IW, int act, float slope,
                               void* workspace, size_t workspace_bytes, int impl, int debug, hipStream_t stream);
@@ -84,6 +90,10 @@ int sg_conv3d_k4s2p1_dgrad_keep(const float* dy, const float* w, const float* bi
 int sg_conv3d_k4s2p1_dgrad_impl(const float* dy, const float* w, const float* bias, float* dx, int batch, int Cin,
                                 int Cin_total, int Cx, int Cout, int ID, int IH, int IW, int act, float slope,
                                 void* workspace, size_t workspace_bytes, int impl, hipStream_t stream); /* tests */
+/* (impl 1: the LDS-halo kernel, 3: one output parity per workgroup, 1 + 4 ppw: ppw parities; + 64: the depth-skip form of the
+ * 4^3 -> 8^3 64-row kernel, conv_dgrad_halo_dskip_kernel, at any batch size (SG_ERR_ARG on other grids) — without it a forced call
+ * gets conv_dgrad_halo_kernel<1> / conv_dgrad_halo32_kernel<1>; the dispatching entries take the depth-skip form for every 64-row
+ * 4^3 call.  Semantics of the depth-skip forms: see sg_conv3d_k4s2p1_fwd_impl.) */
 /* dw[Cout, Cin_total(first Cin channels written), 4,4,4] = sum_{n,o} dy * x-patches; split-K workspace optional */
 size_t sg_conv3d_k4s2p1_wgrad_workspace_bytes(int batch, int Cin, int Cout, int OD, int OH, int OW);
 int sg_conv3d_k4s2p1_wgrad_impl(const float* dy, const float* x, float* dw, int batch, int Cin, int Cin_total, int Cx,

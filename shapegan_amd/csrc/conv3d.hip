@@ -829,12 +829,13 @@ int sg_conv3d_k4s2p1_dgrad_impl(const float* dy, const float* w, const float* bi
                                 int Cin_total, int Cx, int Cout, int ID, int IH, int IW, int act, float slope,
                                 void* workspace, size_t workspace_bytes, int impl, hipStream_t stream) {
     SG_CHECK_ARG(dy && w && dx && batch > 0 && Cin > 0 && Cin <= Cin_total && Cin <= Cx && Cout > 0 && (impl & 1) &&
-                 (impl == 1 || impl == 3 || impl == 9 || impl == 17 || impl == 33));
+                 ((impl & ~64) == 1 || (impl & ~64) == 3 || (impl & ~64) == 9 || (impl & ~64) == 17 || (impl & ~64) == 33));
     ConvGeom g;
     if (make_geom(g, ID, IH, IW, Cx, Cout)) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_dgrad_impl: bad spatial dims");
     if (check_sizes(g, batch, "sg_conv3d_k4s2p1_dgrad_impl")) return SG_ERR_ARG;
     const int rc = halo_dgrad_try(dy, w, bias, dx, batch, Cin, Cin_total, g, Cout, act, slope, workspace, workspace_bytes,
-                                  stream, impl);   // 1: forced, 3: one parity per workgroup, 1 + 4 ppw: ppw parities
+                                  stream, impl);   // 1: forced, 3: one parity per workgroup, 1 + 4 ppw: ppw parities;
+                                                   // + 64: the depth-skip form of the 4^3 64-row kernel (4^3 grids only)
     if (rc != 1) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_dgrad_impl: shape not eligible for the LDS-halo kernel");
     SG_CHECK_LAUNCH();
     return SG_OK;

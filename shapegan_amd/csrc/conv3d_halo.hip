@@ -52,24 +52,42 @@ struct HaloFwdArgs {
     long npos;
 };
 
-// Wp[(mt*G + g)*64 + lane] = float4{ W[mt*32 + (lane&31)][8g + 2j + (lane>>5)] , j = 0..3 }   (G = Cin*8 groups)
-__global__ void __launch_bounds__(256) pack_fwd_weights_kernel(const float* __restrict__ w, float4* __restrict__ wp,
-                                                               int Cout, int Cin_total, int Cin, int ntile) {
-    const long G = (long)Cin * 8;
-    const long total = (long)ntile * G * 64;
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-        const int lane = (int)(e & 63);
-        const long q = e >> 6;
+// Element e of a forward weight image.
+// mode 0 (32x32x2 kernels): Wp[(mt*G + g)*64 + lane] = float4{ W[mt*32 + (lane&31)][8g + 2j + (lane>>5)] , j = 0..3 }   (G = Cin*8 groups)
+// mode 1 (conv_fwd_halo4_dskip_kernel, 16x16x4): 16-row tiles, G = Cin*4 groups g = (ci, kd):
+//         Wp[(mt*G + g)*64 + lane] = float4{ W[mt*16 + (lane&15)][ci][kd][kh = j][kw = lane>>4] , j = 0..3 }
+// Both images have ntile32 * Cin * 8 * 64 float4 (a 32-row tile = two 16-row tiles).
+__device__ __forceinline__ float4 fwd_image_element(const float* __restrict__ w, long e, int Cout, int Cin_total, int Cin, int mode) {
+    const int lane = (int)(e & 63);
+    const long q = e >> 6;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (mode == 0) {
+        const long G = (long)Cin * 8;
         const long g = q % G;
         const int mt = (int)(q / G);
         const int co = mt * 32 + (lane & 31);
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (co < Cout) {
             const float* src = w + (long)co * Cin_total * 64 + g * 8 + (lane >> 5);
             v = make_float4(src[0], src[2], src[4], src[6]);
         }
-        wp[e] = v;
+    } else {
+        const long G = (long)Cin * 4;
+        const long g = q % G;
+        const int mt = (int)(q / G);
+        const int co = mt * 16 + (lane & 15);
+        if (co < Cout) {
+            const float* src = w + (long)co * Cin_total * 64 + g * 16 + (lane >> 4);
+            v = make_float4(src[0], src[4], src[8], src[12]);
+        }
     }
+    return v;
+}
+// ntile counts 32-row tiles in both modes
+__global__ void __launch_bounds__(256) pack_fwd_weights_kernel(const float* __restrict__ w, float4* __restrict__ wp,
+                                                               int Cout, int Cin_total, int Cin, int ntile, int mode) {
+    const long total = (long)ntile * Cin * 8 * 64;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256)
+        wp[e] = fwd_image_element(w, e, Cout, Cin_total, Cin, mode);
 }
 
 // ---- addressing helpers shared by the three halo kernels ---------------------------------------------------------
@@ -429,7 +447,182 @@ __global__ void __launch_bounds__(512) conv_fwd_halo4_kernel(HaloFwdArgs a) {
     }
 }
 
+// ---- depth-skip form of conv_fwd_halo4_kernel ---------------------------------------------------------------------------------
+// Same workgroup (one sample x 64 output channels, the two K halves of every 8-channel stage, the whole padded sample as the
+// box), on v_mfma_f32_16x16x4_f32: a 16-column tile is ONE output depth plane od (4 x 4 positions), k = 4 is the four kw of one
+// (kd, kh).  8 waves = (K half) x (four 16-row blocks); a wave holds all four planes of its rows, 4 accumulators of 4 registers.
+//   The B fragment of (od, kd, kh) is the padded plane d' = 2 od + kd at row 2 oh + kh.  d' = 0 (od 0, kd 0) and d' = 9 (od 3,
+//   kd 3) are padding for every sample, stage and wave: those two tiles of the 16 per kh are not issued and not read — 14 MFMAs
+//   and 14 LDS reads per (channel, kh) instead of 16 and 16, a static and balanced skip.
+//   16 rows per wave (not 32 with a shared B fragment): 32 rows would leave 4 waves of one K half or a four-way K split with a
+//   four-way reduction; with 16 rows the LDS reads per MFMA cycle are those of conv_fwd_halo4_kernel (one ds_read_b32 per 32 MFMA
+//   cycles: a quarter of the LDS issue with four waves per SIMD) and the weight loads per workgroup are halved (every wave
+//   loads its own rows once).
+//   Box layout per channel: [10 d][5 row pairs][even h: even w | odd h: even w | even h: odd w | odd h: odd w], a half row of 5
+//   every 6 floats, 24 per row pair, plane = 120: word(h', w') = (h' >> 1) * 24 + (h' & 1) * 6 + (w' & 1) * 12 + (w' >> 1).  The
+//   lane's k index (lane >> 4) is kw, in the order of conv_fwd_halo4_kernel's k-pairs, so that the sum of every output runs over
+//   (ci, kd, kh, kw) in the same order there and here: for finite inputs the two forms agree bit for bit (the skipped products are
+//   exact zeros).  A read of (od, kd, kh) is h' = 2 oh + kh, w' = 2 ow + kw: the lanes 0 - 31 (kw 0, 1) read the words
+//   24 oh + 12 kw + ow (+ const) = banks 0 - 3, 12 - 15 | 24 - 27, 4 - 7 | 16 - 19, 28 - 31 | 8 - 11, 20 - 23 for oh = 0 .. 3: each
+//   of the 32 banks once (ds_read_b32: two groups of 32 lanes); the lanes 32 - 63 (kw 2, 3) the same one word on.  With the
+//   [even w | odd w] rows of 10 of conv_fwd_halo4_kernel the same read is 20 oh + 5 kw + ow: two-way conflicts on five banks.
+//   Accumulator of plane od, register v, lane l: channel co0 + 16 wr + 4 (l >> 4) + v at position (od, (l >> 2) & 3, l & 3).
+//   LDS 2 x 8 x 1200 x 4 B = 75 KB: two workgroups per CU as before.  Channel splits (csplit > 1) stay with conv_fwd_halo4_kernel.
+// Semantics: the skipped products are weight x (zero padding of x beyond the depth range): for finite weights the value of the
+// same sum with the zeros added; a non-finite weight on such a tap gives NaN in conv_fwd_halo4_kernel and the sum over the
+// in-range positions here.  The h / w padding is multiplied as before.
+constexpr int k4sHODD = 6, k4sWODD = 12, k4sPAIR = 24, k4sPLANE = 120, k4sCH = 10 * k4sPLANE;   // 1200 floats per channel
+__host__ __device__ constexpr int k4s_row(int h) { return (h >> 1) * k4sPAIR + (h & 1) * k4sHODD; }   // word of padded row h'
+constexpr int k4sBUF = k4CC * k4sCH;                                             // 9600 floats = 37.5 KB per buffer
+
+__global__ void __launch_bounds__(512) conv_fwd_halo4_dskip_kernel(HaloFwdArgs a) {
+    constexpr int kRing = 8;
+    extern __shared__ __attribute__((aligned(16))) float halo[];  // [2][k4CC][k4sCH]
+    lds_float* const hl = (lds_float*)halo;
+    const int n = blockIdx.x, co0 = blockIdx.y * 64;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kh2 = wave >> 2, wr = wave & 3, col = lane & 15, kq = lane >> 4;
+    const int oh = col >> 2, ow = col & 3;
+    const int lanebase = oh * k4sPAIR + (kq & 1) * k4sWODD + (kq >> 1) + ow;   // + (2 od + kd) * PLANE + k4s_row(kh)
+
+    f32x4 acc[4];
+#pragma unroll
+    for (int od = 0; od < 4; ++od)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) acc[od][v] = 0.f;
+
+    // zero both buffers once: the halo padding is never written again
+    for (int e = tid; e < 2 * k4sBUF; e += 512) hl[e] = 0.f;
+
+    const lds_float* bb[2][4];   // (buffer, own channel)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            bb[b][c] = hl + b * k4sBUF + (kh2 * 4 + c) * k4sCH + lanebase;
+            pin_vgpr(bb[b][c]);
+        }
+    const int G = a.Cin * 4;   // groups (ci, kd) of one 16-row tile
+    const __amdgpu_buffer_rsrc_t wres = make_rsrc(a.wp + ((long)(co0 / 16 + wr) * G) * 64);
+    const unsigned wvoff = lane * 16;
+
+    // copy: a channel is 512 contiguous floats; thread t moves element t of each of the stage's 8 channels
+    const int I3 = 512;
+    const __amdgpu_buffer_rsrc_t xres = make_rsrc(a.x + ((long)n * a.g.Cx) * I3);
+    unsigned xvoff = tid * 4;
+    lds_float* sdst = hl + ((tid >> 6) + 1) * k4sPLANE + k4s_row(((tid >> 3) & 7) + 1) + (((tid & 7) + 1) & 1) * k4sWODD +
+                      (((tid & 7) + 1) >> 1);
+    pin_vgpr(xvoff);
+    pin_vgpr(sdst);
+    float fv[k4CC];
+    __syncthreads();   // zero fill done before the first real voxels land
+#pragma unroll
+    for (int c = 0; c < k4CC; ++c) fv[c] = buf_load(xres, xvoff, c * (I3 * 4));
+    // weight groups of this wave in order: stage s, own channel c, kd -> group (s*8 + kh2*4 + c)*4 + kd = s*32 + kh2*16 + (c*4 + kd)
+    const int nstage = a.Cin / k4CC, nq = nstage * 16;
+    auto group_of = [&](int q) {
+        q = q < nq ? q : nq - 1;
+        return (q >> 4) * 32 + kh2 * 16 + (q & 15);
+    };
+    float4 aring[kRing];
+#pragma unroll
+    for (int u = 0; u < kRing; ++u) aring[u] = buf_load4(wres, wvoff, (unsigned)group_of(u) * 1024u);
+#pragma unroll
+    for (int c = 0; c < k4CC; ++c) sdst[c * k4sCH] = fv[c];
+    __syncthreads();
+
+    int qbase = kRing;
+    // B fragments of step (c, kd, kh): plane od at bb[c][(2 od + kd) * PLANE + k4s_row(kh)], read one step ahead; the dead tile's
+    // register is never loaded and never used
+    auto stage = [&](auto tag, int s) __attribute__((always_inline)) {
+        constexpr int CUR = decltype(tag)::value, NXT = CUR ^ 1;
+        int cnext = (s + 1) * k4CC;
+        cnext = cnext > a.Cin - k4CC ? a.Cin - k4CC : cnext;
+        const unsigned xs = (unsigned)cnext * (I3 * 4);
+        float bq[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int od = 1; od < 4; ++od) bq[od] = bb[CUR][0][(2 * od) * k4sPLANE];   // step (0, kd 0, kh 0): od 0 is dead
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int gidx = 0; gidx < 16; ++gidx) {
+            const int kd = gidx & 3;
+            const float4 a_cur = aring[gidx % kRing];
+            aring[gidx % kRing] = buf_load4(wres, wvoff, (unsigned)group_of(qbase + gidx) * 1024u);
+            // copy of the next box: channel c is loaded in group c and stored in group c + 8
+#pragma unroll
+            for (int c = 0; c < k4CC; ++c) {
+                if (c + 8 == gidx) sdst[NXT * k4sBUF + c * k4sCH] = fv[c];
+                if (c == gidx) fv[c] = buf_load(xres, xvoff, xs + c * (I3 * 4));
+            }
+            const float av[4] = {a_cur.x, a_cur.y, a_cur.z, a_cur.w};   // kh
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float b[4];
+#pragma unroll
+                for (int od = 0; od < 4; ++od) b[od] = bq[od];
+                const int tn = gidx * 4 + k + 1;   // the next step
+                if (tn < 64) {
+                    const int kdn = (tn >> 2) & 3, kn = tn & 3;
+                    const lds_float* hb = bb[CUR][tn >> 4];
+#pragma unroll
+                    for (int od = 0; od < 4; ++od) {
+                        if ((od == 0 && kdn == 0) || (od == 3 && kdn == 3)) continue;
+                        bq[od] = hb[(2 * od + kdn) * k4sPLANE + k4s_row(kn)];
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                // consecutive MFMAs go to different accumulators (40-cycle dependent latency against a 32-cycle issue)
+#pragma unroll
+                for (int od = 0; od < 4; ++od) {
+                    if ((od == 0 && kd == 0) || (od == 3 && kd == 3)) continue;
+                    acc[od] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[k], b[od], acc[od], 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        qbase += 16;
+        __syncthreads();
+    };
+    for (int s = 0; s + 1 < nstage; s += 2) {
+        stage(IntTag<0>(), s);
+        stage(IntTag<1>(), s + 1);
+    }
+    if (nstage & 1) stage(IntTag<0>(), nstage - 1);
+
+    // the K halves meet in LDS (the boxes are dead after the last barrier): waves 4-7 park, waves 0-3 add and store
+    float* red = halo + (wr * 16) * 64;
+    if (kh2 == 1) {
+#pragma unroll
+        for (int od = 0; od < 4; ++od)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) red[(od * 4 + v) * 64 + lane] = acc[od][v];
+    }
+    __syncthreads();
+    if (kh2 == 1) return;
+    // y[n][co][p], p = od*16 + oh*4 + ow: 16 consecutive floats per (co, plane)
+    float* yo = a.y + (long)n * a.Cout * 64 + col;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+        const int co = co0 + wr * 16 + 4 * kq + v;
+        if (co < a.Cout) {
+            const float bv = a.bias ? a.bias[co] : 0.f;
+#pragma unroll
+            for (int od = 0; od < 4; ++od)
+                yo[(long)co * 64 + od * 16] = sg_apply_act(acc[od][v] + red[(od * 4 + v) * 64 + lane] + bv, a.act, a.slope);
+        }
+    }
+}
+
 size_t halo_fwd_workspace_bytes(int Cin, int Cout) { return (size_t)((Cout + 127) / 128) * 128 * Cin * 64 * sizeof(float); }
+
+// Which form serves an 8^3 -> 4^3 forward (pure host logic).  Forced calls (tests, A/B): debug bit 8 asks for the depth-skip form,
+// without it they get conv_fwd_halo4_kernel.  The dispatch takes the depth-skip form wherever the input channels are not split over
+// workgroups (csplit > 1: small batches) — measured faster at 64 and 128 samples.
+bool halo_fwd4_dskip_chosen(int csplit, int force, int debug) {
+    if (debug & 256) return csplit == 1;
+    return !force && csplit == 1;
+}
 
 int halo_fwd_try(const float* x, const float* w, const float* bias, float* y, int batch, int Cin, int Cin_total,
                  const ConvGeom& g, int Cout, int act, float slope, void* workspace, size_t workspace_bytes,
@@ -451,14 +644,18 @@ int halo_fwd_try(const float* x, const float* w, const float* bias, float* y, in
             if (csplit == 1) return 0;
             if (workspace_bytes < halo_fwd_workspace_bytes(Cin, Cout) + (size_t)csplit * Cout * batch * 64 * sizeof(float)) return 0;
         }
+        // depth-skip form (conv_fwd_halo4_dskip_kernel) or conv_fwd_halo4_kernel: they read different weight images (job kinds 2, 0)
+        const bool dskip = halo_fwd4_dskip_chosen(csplit, force, debug);
+        if ((debug & 256) && !dskip) return 0;
         float4* wp = (float4*)workspace;
         const int ntile = mtiles * 2;
         const long total = (long)ntile * Cin * 8 * 64;
         int blocks = (int)((total + 255) / 256);
         if (blocks > 4096) blocks = 4096;
-        if (collect) return collect->add(0, w, wp, Cout, Cin_total, Cin, ntile);
+        if (collect) return collect->add(dskip ? 2 : 0, w, wp, Cout, Cin_total, Cin, ntile);
         if (!packed_already)
-            hipLaunchKernelGGL(pack_fwd_weights_kernel, dim3(blocks), dim3(256), 0, stream, w, wp, Cout, Cin_total, Cin, ntile);
+            hipLaunchKernelGGL(pack_fwd_weights_kernel, dim3(blocks), dim3(256), 0, stream, w, wp, Cout, Cin_total, Cin, ntile,
+                               dskip ? 1 : 0);
         HaloFwdArgs a;
         a.x = x;
         a.wp = wp;
@@ -481,9 +678,21 @@ int halo_fwd_try(const float* x, const float* w, const float* bias, float* y, in
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
             attr_once.end();
         }
+        if (dskip) {
+            const size_t lds4s = (size_t)2 * k4sBUF * sizeof(float);   // 75 KB
+            static SgPerDeviceOnce attr_once_s;
+            if (attr_once_s.begin()) {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_halo4_dskip_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4s);
+                attr_once_s.end();
+            }
+            hipLaunchKernelGGL(conv_fwd_halo4_dskip_kernel, dim3((unsigned)batch, mtiles), dim3(512), lds4s, stream, a);
+            return 1;
+        }
         hipLaunchKernelGGL(conv_fwd_halo4_kernel, dim3((unsigned)batch, mtiles, csplit), dim3(512), lds4, stream, a);
         return csplit > 1 ? 16 + csplit : 1;
     }
+    if (debug & 256) return 0;   // the depth-skip form exists for 4^3 outputs only
     // eligible: 8x8 position tiles exist, whole stages of 4 channels, enough output channels to fill 64-row MFMA tiles
     if (g.OW % 8 != 0 || g.OH % 8 != 0 || Cin % kCC != 0 || Cin < 8 || Cout < 32) return 0;
     if ((long)g.Cx * g.ID * g.IH * g.IW * 4 >= (long)kBufRange || (long)Cin * 8 * 1024 >= (long)kBufRange) return 0;
@@ -524,7 +733,7 @@ int halo_fwd_try(const float* x, const float* w, const float* bias, float* y, in
         if (blocks > 4096) blocks = 4096;
         if (collect) return collect->add(0, w, wp, Cout, Cin_total, Cin, ntile);
         if (!packed_already)
-            hipLaunchKernelGGL(pack_fwd_weights_kernel, dim3(blocks), dim3(256), 0, stream, w, wp, Cout, Cin_total, Cin, ntile);
+            hipLaunchKernelGGL(pack_fwd_weights_kernel, dim3(blocks), dim3(256), 0, stream, w, wp, Cout, Cin_total, Cin, ntile, 0);
     }
     HaloFwdArgs a;
     a.x = x;
@@ -587,32 +796,37 @@ struct HaloDgradArgs {
     float slope;
 };
 
-// wp[((p*MT + mt)*Cout + co)*64 + lane] = float4{ W[co][mt*32 + (lane&31)][tap(p, t = 2j + (lane>>5))], j = 0..3 }
-__global__ void __launch_bounds__(256) pack_dgrad_frag_kernel(const float* __restrict__ w, float4* __restrict__ wp,
-                                                              int Cout, int Cin_total, int Cin, int MT) {
-    const long total = 8L * MT * Cout * 64;
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-        const int lane = (int)(e & 63);
-        long q = e >> 6;
-        const int co = (int)(q % Cout);
-        q /= Cout;
-        const int mt = (int)(q % MT);
-        const int p = (int)(q / MT);
-        const int ci = mt * 32 + (lane & 31);
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (ci < Cin) {
-            const float* src = w + ((long)co * Cin_total + ci) * 64;
+// Element e of an input-gradient weight image, tap(p, t) = 1 - p + 2t per dimension.
+// mode 0: wp[((p*MT + mt)*Cout + co)*64 + lane] = float4{ W[co][mt*32 + (lane&31)][tap(p, t = 2j + (lane>>5))], j = 0..3 }
+// mode 1 (conv_dgrad_halo_dskip_kernel, 16x16x4): the same index, float4{ W[co][mt*32 + 16*(j&1) + (lane&15)][tap(p, td = j>>1,
+//         th = lane>>5, tw = (lane>>4)&1)], j = 0..3 } — the same size
+__device__ __forceinline__ float4 dgrad_image_element(const float* __restrict__ w, long e, int Cout, int Cin_total, int Cin, int MT,
+                                                      int mode) {
+    const int lane = (int)(e & 63);
+    long q = e >> 6;
+    const int co = (int)(q % Cout);
+    q /= Cout;
+    const int mt = (int)(q % MT);
+    const int p = (int)(q / MT);
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int t = 2 * j + (lane >> 5);
-                const int kd = 1 - ((p >> 2) & 1) + 2 * ((t >> 2) & 1);
-                const int kh = 1 - ((p >> 1) & 1) + 2 * ((t >> 1) & 1);
-                const int kw = 1 - (p & 1) + 2 * (t & 1);
-                v[j] = src[kd * 16 + kh * 4 + kw];
-            }
+    for (int j = 0; j < 4; ++j) {
+        const int ci = mode == 0 ? mt * 32 + (lane & 31) : mt * 32 + 16 * (j & 1) + (lane & 15);
+        const int t = mode == 0 ? 2 * j + (lane >> 5) : 4 * (j >> 1) + (lane >> 4);   // t = 4 td + 2 th + tw
+        if (ci < Cin) {
+            const int kd = 1 - ((p >> 2) & 1) + 2 * ((t >> 2) & 1);
+            const int kh = 1 - ((p >> 1) & 1) + 2 * ((t >> 1) & 1);
+            const int kw = 1 - (p & 1) + 2 * (t & 1);
+            v[j] = w[((long)co * Cin_total + ci) * 64 + kd * 16 + kh * 4 + kw];
         }
-        wp[e] = make_float4(v[0], v[1], v[2], v[3]);
     }
+    return make_float4(v[0], v[1], v[2], v[3]);
+}
+__global__ void __launch_bounds__(256) pack_dgrad_frag_kernel(const float* __restrict__ w, float4* __restrict__ wp,
+                                                              int Cout, int Cin_total, int Cin, int MT, int mode) {
+    const long total = 8L * MT * Cout * 64;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256)
+        wp[e] = dgrad_image_element(w, e, Cout, Cin_total, Cin, MT, mode);
 }
 
 // ---- several weight images in ONE launch ------------------------------------------------------------------------------------
@@ -620,51 +834,19 @@ __global__ void __launch_bounds__(256) pack_dgrad_frag_kernel(const float* __res
 // of the 16.8 ms WGAN step in thirty launches.  sg_conv3d_k4s2p1_pack_images (conv3d.hip) runs halo_fwd_try / halo_dgrad_try in
 // COLLECT mode — they plan exactly as for a real call and hand their packing job to the collector instead of launching it — and
 // this kernel does all collected jobs at once (grid y = job); the convolutions that follow are told their image is in place.
+// Job kinds: 0 / 2 forward image mode 0 / 1, 1 / 3 input-gradient image mode 0 / 1.
 __global__ void __launch_bounds__(256) pack_images_kernel(PackJobs jobs) {
     const PackJob& j = jobs.job[blockIdx.y];
     float4* __restrict__ wp = j.wp;
     const float* __restrict__ w = j.w;
-    if (j.kind == 0) {          // pack_fwd_weights_kernel
-        const long G = (long)j.Cin * 8;
-        const long total = (long)j.nt * G * 64;
-        for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-            const int lane = (int)(e & 63);
-            const long q = e >> 6;
-            const long g = q % G;
-            const int mt = (int)(q / G);
-            const int co = mt * 32 + (lane & 31);
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (co < j.Cout) {
-                const float* src = w + (long)co * j.Cin_total * 64 + g * 8 + (lane >> 5);
-                v = make_float4(src[0], src[2], src[4], src[6]);
-            }
-            wp[e] = v;
-        }
+    if ((j.kind & 1) == 0) {    // pack_fwd_weights_kernel
+        const long total = (long)j.nt * j.Cin * 8 * 64;
+        for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256)
+            wp[e] = fwd_image_element(w, e, j.Cout, j.Cin_total, j.Cin, j.kind >> 1);
     } else {                    // pack_dgrad_frag_kernel
-        const int MT = j.nt;
-        const long total = 8L * MT * j.Cout * 64;
-        for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-            const int lane = (int)(e & 63);
-            long q = e >> 6;
-            const int co = (int)(q % j.Cout);
-            q /= j.Cout;
-            const int mt = (int)(q % MT);
-            const int p = (int)(q / MT);
-            const int ci = mt * 32 + (lane & 31);
-            float v[4] = {0.f, 0.f, 0.f, 0.f};
-            if (ci < j.Cin) {
-                const float* src = w + ((long)co * j.Cin_total + ci) * 64;
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    const int t = 2 * jj + (lane >> 5);
-                    const int kd = 1 - ((p >> 2) & 1) + 2 * ((t >> 2) & 1);
-                    const int kh = 1 - ((p >> 1) & 1) + 2 * ((t >> 1) & 1);
-                    const int kw = 1 - (p & 1) + 2 * (t & 1);
-                    v[jj] = src[kd * 16 + kh * 4 + kw];
-                }
-            }
-            wp[e] = make_float4(v[0], v[1], v[2], v[3]);
-        }
+        const long total = 8L * j.nt * j.Cout * 64;
+        for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256)
+            wp[e] = dgrad_image_element(w, e, j.Cout, j.Cin_total, j.Cin, j.nt, j.kind >> 1);
     }
 }
 int halo_pack_jobs_launch(const PackJobs& jobs, hipStream_t stream) {
@@ -956,7 +1138,247 @@ __global__ void __launch_bounds__(256) conv_dgrad_halo32_kernel(HaloDgradArgs a)
     conv_dgrad_halo_body<MODE, true>(a);
 }
 
+// ---- depth-skip form of conv_dgrad_halo_kernel<1> (4^3 -> 8^3, 64-row workgroups) -------------------------------------------
+// Same workgroup (a pair of samples x 64 input channels x ppw parities), same dy boxes, same copy and weight pipelines, same
+// stores; what changes is the MFMA: v_mfma_f32_16x16x4_f32 on 16-column tiles that are ONE depth plane qd (4 x 4 positions) of
+// the wave's sample.  A wave (row block wm, sample wn) holds 2 row halves x 4 depth planes = 8 accumulators of 4 registers.
+//   k = 4 of an MFMA is (th, tw) = (lane >> 5, (lane >> 4) & 1), td is the outer pair: per channel 2 td x 4 qd x 2 row halves.
+//   The B fragment of (qd, td) is the box plane hd = qd + 1 - td at the lane's (qh + 1 - th, qw + 1 - tw): it depends on hd only,
+//   so the five planes of a channel are read ONCE (one ds_read_b32 each) and serve both td and both row halves.
+//   Plane hd is dy depth qd + pd - td: at output parity pd = 0 plane 0 is depth -1, at pd = 1 plane 4 is depth 4 — padding for
+//   every sample, every stage and every wave.  The tile (qd 0, td 1) at pd = 0 and (qd 3, td 0) at pd = 1 is therefore not
+//   issued and its plane not read: 14 MFMAs and 4 LDS reads per channel instead of 16 and 5.  pd is constant per parity pass: the
+//   stage body is instantiated for both and chosen by a wave-uniform branch outside the stages, which stay one basic block.
+//   LDS banks: a lane reads word (qh + 1 - th) * 5 + (qw + 1 - tw) + const of a 5 x 5 plane: 25 consecutive words, distinct
+//   banks of the 32 (ds_read_b32: two groups of 32 lanes), equal addresses broadcast.
+//   Accumulator of (row half rh, plane qd), register v, lane l: channel ci0 + wm*32 + rh*16 + 4*(l >> 4) + v at position
+//   (qd, (l >> 2) & 3, l & 3).
+// Semantics: the skipped products are weight x (zero padding of dy beyond the depth range).  For finite weights the result is
+// that of the same sum with the zeros added; a non-finite weight on such a tap gives NaN (0 x inf) in conv_dgrad_halo_kernel<1>
+// and the sum over the in-range positions here (as in the weight-gradient skip form).  The h / w padding is multiplied as before.
+// Weight image: wp[((p*MT + mt)*Cout + co)*64 + lane] = float4{ W[co][mt*32 + rh*16 + (lane&15)][tap(p; td, th, tw)],
+// (td, rh) = (0,0), (0,1), (1,0), (1,1) } — the size of the 32x32x2 image (pack mode 1 of pack_dgrad_frag_kernel).
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) conv_dgrad_halo_dskip_kernel(HaloDgradArgs a) {
+    constexpr int kDCC = 16, kDNF = 16, kDBUF = kDNF * 256;
+    using BX = DBox<1>;
+    constexpr int kDB = BX::CH;
+    extern __shared__ __attribute__((aligned(16))) float box[];  // [2][kDBUF], a buffer = [kDCC][kDB] + tail
+    const uint32_t n = blockIdx.x * 2;  // first sample of the pair
+    const int ci0 = blockIdx.y * 64;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1, col = lane & 15, kq = lane >> 4;
+    const int qh = col >> 2, qw = col & 3, th = kq >> 1, tw = kq & 1;
+    const int lanebase = wn * BX::WNOFF + (qh + 1 - th) * BX::BW + (qw + 1 - tw);   // + hd * PL: plane hd of the wave's sample
+
+    f32x4 acc[2][4];   // (row half, depth plane)
+#pragma unroll
+    for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) acc[rh][qd][v] = 0.f;
+
+    lds_float* const bl = (lds_float*)box;
+    // one read address per lane; buffer, channel and plane are immediate offsets (at most 2*kDBUF floats = 32 KB < the 16-bit field)
+    const lds_float* bb = bl + lanebase;
+    pin_vgpr(bb);
+    lds_float* sdst = bl + tid;   // element f of a stage goes to sdst[256 f] (+ buffer)
+    pin_vgpr(sdst);
+
+    const int G = a.Cout;  // one k-group per output channel
+    const int par0 = blockIdx.z * a.ppw, par_end = par0 + a.ppw;
+    const unsigned par_bytes = (unsigned)(a.mtiles * 2) * (unsigned)G * 1024u;   // weight image: [parity][row tile][G][64] float4
+    const __amdgpu_buffer_rsrc_t wres = make_rsrc(a.wp + ((long)(blockIdx.y * 2 + wm) * G) * 64);
+    const unsigned wvoff = lane * 16;
+
+    // copy bookkeeping: exactly that of conv_dgrad_halo_body<1, false> (offset | edge-class words, see there)
+    const int O3 = a.g.OD * a.g.OH * a.g.OW;
+    const int obias = (a.g.OH + 1) * a.g.OW + 1;
+    const __amdgpu_buffer_rsrc_t dres = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(a.dy + (long)n * a.g.Cy * O3 - obias), 0, 1 << 26, 0x00020000);
+    const unsigned chan_bytes = (unsigned)O3 * 4u;
+    unsigned gword[kDNF], goff[kDNF];
+#pragma unroll
+    for (int f = 0; f < kDNF; ++f) {
+        const int e = tid + 256 * f;
+        const int ci = e / kDB;
+        int rem = e - ci * kDB;
+        const int smp = rem / 125;
+        rem -= smp * 125;
+        const int hd = rem / BX::PL, hh = (rem - hd * BX::PL) / BX::BW, hw = rem % BX::BW;
+        const int od = hd - 1, oh = hh - 1, ow = hw - 1;   // parity 0; parity bit p adds p
+        const bool never = e >= kDCC * kDB || (int)n + smp >= a.batch;
+        const unsigned cls = (od < 0 ? 1u << 26 : 0u) | (od + 1 >= a.g.OD ? 1u << 27 : 0u) | (oh < 0 ? 1u << 28 : 0u) |
+                             (oh + 1 >= a.g.OH ? 1u << 29 : 0u) | (ow < 0 ? 1u << 30 : 0u) | (ow + 1 >= a.g.OW ? 1u << 31 : 0u);
+        const int off0 = (smp * a.g.Cy + ci) * O3 + (od * a.g.OH + oh) * a.g.OW + ow + obias;   // >= 0
+        gword[f] = never ? 0xffffffffu : ((unsigned)off0 * 4u) | cls;
+        pin_vgpr(gword[f]);
+    }
+    unsigned pshift = 0;
+    auto set_goff = [&](int par) __attribute__((always_inline)) {
+        const int pd = (par >> 2) & 1, ph = (par >> 1) & 1, pw = par & 1;
+        const unsigned mask = 0x03ffffffu | (pd ? 1u << 27 : 1u << 26) | (ph ? 1u << 29 : 1u << 28) | (pw ? 1u << 31 : 1u << 30);
+#pragma unroll
+        for (int f = 0; f < kDNF; ++f) goff[f] = gword[f] & mask;
+        pshift = (unsigned)((pd * a.g.OH + ph) * a.g.OW + pw) * 4u;
+    };
+    const long I3 = (long)a.g.ID * a.g.IH * a.g.IW;
+    // stores: buffer resource on the wave's sample, one lane offset per depth plane (position of parity 0 + the lane's row of the
+    // 4-row block: 4 * kq channels), the accumulator's row block and the parity shift in the scalar offset
+    const int nn = (int)n + wn;
+    const __amdgpu_buffer_rsrc_t ores = make_rsrc(a.dx + (long)(nn < a.batch ? nn : 0) * a.g.Cx * I3);
+    const __amdgpu_buffer_rsrc_t bres = make_rsrc(a.bias ? a.bias : a.dx);
+    unsigned ovoff[4];
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+        ovoff[qd] = (unsigned)(((2 * qd) * a.g.IH + 2 * qh) * a.g.IW + 2 * qw + 4 * kq * (int)I3) * 4u;
+        pin_vgpr(ovoff[qd]);
+    }
+    const unsigned bvoff = kq * 16;
+    const int clim = a.Cin - 4 * kq;   // the lane's channel cis + 4 kq exists iff cis < clim (Cin % 8 == 0, a 16-row half may be cut)
+    const bool paired = a.ppw >= 2;
+    float keep[2][4][4];
+#pragma unroll
+    for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) keep[rh][qd][v] = 0.f;
+    auto write_parity = [&](int par) __attribute__((always_inline)) {   // dx[n'][ci][2q + p] = act(acc + bias[ci]); acc = 0
+        const int pd = (par >> 2) & 1, ph = (par >> 1) & 1, pw = par & 1;
+        const unsigned oshift = (unsigned)((pd * a.g.IH + ph) * a.g.IW) * 4u;   // of the (pd, ph, pw = 0) element
+        if (nn < a.batch) {
+#pragma unroll
+            for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    const int cis = ci0 + wm * 32 + rh * 16 + v;   // scalar part of the channel; the lane adds 4 * kq
+                    if (cis < clim) {
+                        const float bv = a.bias ? buf_load(bres, bvoff, (unsigned)cis * 4u) : 0.f;
+                        const int soff = (int)((unsigned)cis * (unsigned)I3 * 4u + oshift);
+#pragma unroll
+                        for (int qd = 0; qd < 4; ++qd) {
+                            const float val = sg_apply_act(acc[rh][qd][v] + bv, a.act, a.slope);
+                            if (paired && pw == 0) {
+                                keep[rh][qd][v] = val;
+                            } else if (paired) {   // (pw 0, pw 1) as one 8-byte piece
+                                typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+                                u32x2 pr;
+                                pr.x = __builtin_bit_cast(unsigned, keep[rh][qd][v]);
+                                pr.y = __builtin_bit_cast(unsigned, val);
+                                __builtin_amdgcn_raw_buffer_store_b64(pr, ores, (int)ovoff[qd], soff, 0);
+                            } else {
+                                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, val), ores, (int)ovoff[qd],
+                                                                      soff + 4 * pw, 0);
+                            }
+                        }
+                    }
+                }
+        }
+#pragma unroll
+        for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) acc[rh][qd][v] = 0.f;
+    };
+
+    set_goff(par0);
+    float fv[kDNF];
+    constexpr int kRing = 8;   // <= kDCC: the ring never reaches past the next stage
+    float4 aring[kRing];
+    unsigned wcur = (unsigned)par0 * par_bytes;   // scalar byte offset of (parity, stage) in the weight image
+#pragma unroll
+    for (int f = 0; f < kDNF; ++f) fv[f] = buf_load(dres, goff[f], pshift);
+#pragma unroll
+    for (int u = 0; u < kRing; ++u) aring[u] = buf_load4(wres, wvoff, wcur + (unsigned)u * 1024u);
+#pragma unroll
+    for (int f = 0; f < kDNF; ++f) sdst[256 * f] = fv[f];
+    __syncthreads();
+
+    const int nstage = a.Cout / kDCC;
+    // One stage, one basic block; PD selects the four live planes H0 .. H0 + 3 and the dead (qd, td) tile at compile time.
+    auto stage = [&](auto tag, auto pdtag, unsigned dys, unsigned wnext) __attribute__((always_inline)) {
+        constexpr int CUR = decltype(tag)::value, NXT = CUR ^ 1, PD = decltype(pdtag)::value;
+        constexpr int H0 = PD ? 0 : 1;
+        float bq[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) bq[i] = bb[CUR * kDBUF + (H0 + i) * BX::PL];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int c = 0; c < kDCC; ++c) {  // one k-group per channel
+            const float4 a_cur = aring[c % kRing];
+            aring[c % kRing] = c + kRing < kDCC ? buf_load4(wres, wvoff, wcur + (unsigned)(c + kRing) * 1024u)
+                                                : buf_load4(wres, wvoff, wnext + (unsigned)(c + kRing - kDCC) * 1024u);
+            float b[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) b[i] = bq[i];
+            if (c + 1 < kDCC) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) bq[i] = bb[CUR * kDBUF + (c + 1) * kDB + (H0 + i) * BX::PL];
+            }
+            if (c < kDCC / 2) {  // copy of the next box: two loads per group in the first half of the stage ...
+#pragma unroll
+                for (int f = 2 * c; f < 2 * c + 2; ++f) fv[f] = buf_load(dres, goff[f], dys + pshift);
+            } else {             // ... each value goes to LDS 8 groups after its load
+#pragma unroll
+                for (int f = 2 * (c - kDCC / 2); f < 2 * (c - kDCC / 2) + 2; ++f) sdst[NXT * kDBUF + 256 * f] = fv[f];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const float av[2][2] = {{a_cur.x, a_cur.y}, {a_cur.z, a_cur.w}};   // [td][rh]
+            // consecutive MFMAs go to different accumulators (40-cycle dependent latency against a 32-cycle issue)
+#pragma unroll
+            for (int td = 0; td < 2; ++td)
+#pragma unroll
+                for (int qd = 0; qd < 4; ++qd) {
+                    constexpr int kDead0 = 0, kDead1 = 4;   // the padding plane at pd = 0 / pd = 1
+                    const int hd = qd + 1 - td;
+                    if (hd == (PD ? kDead1 : kDead0)) continue;
+#pragma unroll
+                    for (int rh = 0; rh < 2; ++rh)
+                        acc[rh][qd] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[td][rh], b[hd - H0], acc[rh][qd], 0, 0, 0);
+                }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        wcur = wnext;
+        __syncthreads();
+    };
+    auto run_parity = [&](auto pdtag, int par) __attribute__((always_inline)) {
+        const bool more = par + 1 < par_end;
+        // the stage after this parity's last one: the next parity's first (new box origin) or, at the very end, the last
+        // stage again (copied into the idle buffer, never read)
+        const unsigned wlast = more ? (unsigned)(par + 1) * par_bytes : (unsigned)par * par_bytes + (unsigned)(nstage - 1) * kDCC * 1024u;
+        const unsigned dlast = more ? 0u : (unsigned)(nstage - 1) * kDCC * chan_bytes;
+        int s = 0;
+        for (; s + 1 < nstage; s += 2) {   // stages in pairs: the buffer index is a compile-time constant
+            stage(IntTag<0>(), pdtag, (unsigned)(s + 1) * kDCC * chan_bytes, wcur + kDCC * 1024u);
+            const bool last = s + 2 == nstage;
+            if (last && more) set_goff(par + 1);
+            stage(IntTag<1>(), pdtag, last ? dlast : (unsigned)(s + 2) * kDCC * chan_bytes, last ? wlast : wcur + kDCC * 1024u);
+        }
+        if (s < nstage) stage(IntTag<0>(), pdtag, dlast, wlast);   // odd stage count: only with one parity per workgroup
+    };
+    for (int par = par0; par < par_end; ++par) {
+        if ((par >> 2) & 1)   // wave-uniform: pd of this parity pass
+            run_parity(IntTag<1>(), par);
+        else
+            run_parity(IntTag<0>(), par);
+        write_parity(par);
+    }
+}
+
 size_t halo_dgrad_workspace_bytes(int Cin, int Cout) { return (size_t)8 * ((Cin + 63) / 64) * 64 * Cout * 8 * sizeof(float); }
+
+// Which form serves a 4^3 -> 8^3 input gradient with 64-row workgroups (pure host logic).  Forced calls (tests, A/B): force bit 6
+// asks for the depth-skip form, without it they get conv_dgrad_halo_kernel<1>.  The dispatch takes the depth-skip form for every
+// 64-row 4^3 call — measured faster at 64, 128 and 256 samples.  Other grids and the 32-row workgroups
+// have no depth-skip form.
+bool halo_dgrad_dskip_chosen(bool mode1, bool r32, int force) {
+    if (!mode1 || r32) return false;
+    return !force || (force & 64);
+}
 
 int halo_dgrad_try(const float* dy, const float* w, const float* bias, float* dx, int batch, int Cin, int Cin_total,
                    const ConvGeom& g, int Cout, int act, float slope, void* workspace, size_t workspace_bytes,
@@ -977,12 +1399,24 @@ int halo_dgrad_try(const float* dy, const float* w, const float* bias, float* dx
     if (tiles >= (1L << 31) || mtiles > 65535) return 0;
     float4* wp = (float4*)workspace;
     if ((long)8 * mtiles * 2 * Cout * 1024 >= (long)kBufRange) return 0;
-    if (collect) return collect->add(1, w, wp, Cout, Cin_total, Cin, mtiles * 2);
+    // parities per workgroup: as many as keep >= 512 workgroups (2 per CU); force bit 1 (impl 3): one parity per workgroup
+    int ppw = 8;
+    while (ppw > 1 && (tiles * mtiles * (8 / ppw) < 512 || (force & 2) || (Cout / 16) % 2 != 0)) ppw >>= 1;
+    if (((force >> 2) & 15) && (Cout / 16) % 2 == 0) ppw = (force >> 2) & 15;   // tests: impl = 1 + 4 * ppw forces 2, 4 or 8 parities
+    // 32-row workgroups (four waves, one column tile each): when only 32 rows of the tile exist (Cin <= 32), and when 64-row workgroups
+    // would leave CUs without one (small batches: 128 workgroups at 16 samples of a 4^3 grid) — twice as many, half as long
+    const bool r32 = !(force & 64) && (Cin <= 32 || tiles * mtiles * (8 / ppw) < 256);   // (force bit 6: 64-row workgroups at any size)
+    // depth-skip form of the 4^3 64-row kernel (conv_dgrad_halo_dskip_kernel, its own weight image: job kind 3); force bit 6 asks
+    // for it (0 if the grid is not 4^3)
+    const bool dskip = halo_dgrad_dskip_chosen(mode1, r32, force);
+    if ((force & 64) && !dskip) return 0;
+    if (collect) return collect->add(dskip ? 3 : 1, w, wp, Cout, Cin_total, Cin, mtiles * 2);
     if (!packed_already) {
         const long total = 8L * mtiles * 2 * Cout * 64;
         int blocks = (int)((total + 255) / 256);
         if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(pack_dgrad_frag_kernel, dim3(blocks), dim3(256), 0, stream, w, wp, Cout, Cin_total, Cin, mtiles * 2);
+        hipLaunchKernelGGL(pack_dgrad_frag_kernel, dim3(blocks), dim3(256), 0, stream, w, wp, Cout, Cin_total, Cin, mtiles * 2,
+                           dskip ? 1 : 0);
     }
     HaloDgradArgs a;
     a.dy = dy;
@@ -999,11 +1433,6 @@ int halo_dgrad_try(const float* dy, const float* w, const float* bias, float* dx
     a.dntd = FastDiv(ntd);
     a.act = act;
     a.slope = slope;
-    // parities per workgroup: as many as keep >= 512 workgroups (2 per CU); force bit 1 (impl 3): one parity per workgroup
-    int ppw = 8;
-    while (ppw > 1 && (tiles * mtiles * (8 / ppw) < 512 || (force & 2) || (Cout / 16) % 2 != 0)) ppw >>= 1;
-    if ((force >> 2) && (Cout / 16) % 2 == 0) ppw = force >> 2;   // tests: impl = 1 + 4 * ppw forces 2, 4 or 8 parities
-    if ((long)8 * mtiles * 2 * Cout * 1024 >= (long)kBufRange) return 0;
     a.ppw = ppw;
     // registers admit 3 workgroups per CU; take 3 only when the grid then needs fewer CU-slots in total (a 2048-workgroup
     // grid is 4 full rounds at 2 per CU but 2.67 rounds at 3): otherwise a larger LDS request caps the CU at 2
@@ -1013,11 +1442,10 @@ int halo_dgrad_try(const float* dy, const float* w, const float* bias, float* dx
         const long cost2 = ((wgs + 511) / 512) * 2, cost3 = ((wgs + 767) / 768) * 3;
         if (cost2 <= cost3) lds = 56 * 1024;
     }
-    // 32-row workgroups (four waves, one column tile each): when only 32 rows of the tile exist (Cin <= 32), and when 64-row workgroups
-    // would leave CUs without one (small batches: 128 workgroups at 16 samples of a 4^3 grid) — twice as many, half as long
-    const bool r32 = Cin <= 32 || tiles * mtiles * (8 / ppw) < 256;
     const dim3 grid((unsigned)tiles, r32 ? (unsigned)((Cin + 31) / 32) : (unsigned)mtiles, 8 / ppw);
-    if (mode1 && r32)
+    if (dskip)
+        hipLaunchKernelGGL(conv_dgrad_halo_dskip_kernel, grid, dim3(256), lds, stream, a);
+    else if (mode1 && r32)
         hipLaunchKernelGGL((conv_dgrad_halo32_kernel<1>), grid, dim3(256), lds, stream, a);
     else if (mode1)
         hipLaunchKernelGGL((conv_dgrad_halo_kernel<1>), grid, dim3(256), lds, stream, a);
