@@ -706,6 +706,59 @@ int sg_topo_keep_emit(const float* vertices, const float* normals, const int64_t
                       float* out_normals, int64_t* out_faces, long max_verts, long max_tris, void* workspace, size_t workspace_bytes,
                       hipStream_t stream);
 
+/* ---- K12c: mesh simplification: quadric vertex clustering of packed meshes --------------------------------------------------------
+ * reference: its STL export meshes at 256^3 (create_plot.py:914-933) and nothing after marching cubes makes such a mesh smaller; what
+ *            trimesh users take from simplify_* -> one pass over a whole batch on the device (Lindstrom 2000, Garland-Heckbert quadrics).
+ * Input: K12's packed meshes with K12b's rule for a triangle that COUNTS.  S in [1, 2^20), V and F up to 2^31 - 1, else SG_ERR_ARG
+ * before any launch.  The contract (keys, clusters, quadrics, placement, surviving triangles) and the order of every sum are stated
+ * in csrc/simplify_core.h and shared with the twin: every output is bit-identical between the two and from run to run.
+ *
+ * The grid of shape s lives on the device: origin [S][3] fp32, cell [S][2] fp32 = (h_s, inv_h_s), cells [S] int32 = n_s.  The caller
+ * (shapegan_amd/simplify.py) refuses n > 16384 and an h that is not a positive finite number before any launch; a kernel that meets
+ * other values clamps n into [1, 16384] and takes a negative or non-finite product to cell 0, so a key is a key whatever it reads.
+ *
+ * sg_simplify_bounds: lo, hi [S][3] fp32 = the bounding box of the finite coordinates of each shape ([0, 0] on an axis without one).
+ * sg_simplify_keys: keys [V] int64 = s << 42 | ix << 28 | iy << 14 | iz.
+ * sg_simplify_count: counts [S] int32 = the counting triangles of each shape whose three keys differ (integer atomics): what a grid
+ *   would leave, without a sort.
+ * The caller sorts the keys STABLY (sorted_keys, order [V] int64: the vertex at each sorted position).
+ * sg_simplify_clusters: sorted_cluster [V] int32 = the cluster number (batch-wide, in key order) at each sorted position,
+ *   vertex_cluster [V] int32 = the same per vertex, cluster_offsets [S+1] int64 = the clusters before each shape; the caller reads
+ *   C = cluster_offsets[S] once.  workspace: int32 words.
+ * sg_simplify_corners: corner_keys [F][3] int64 = per counting triangle one record cluster << 31 | triangle for each DISTINCT
+ *   cluster among its corners, 2^63 - 1 in every other slot (and for a triangle that does not count); the caller sorts them.
+ * sg_simplify_place: cluster_vertices, cluster_normals [C][3] fp32.  One wave per cluster walks its run of sorted vertices and its
+ *   run of sorted corner records (both found by bisection) in tiles of 64; placement 0 = quadric, 1 = mean.
+ * sg_simplify_faces_count / sg_simplify_faces_emit, a pair like sg_topo_keep_count / _emit: count marks the clusters that a
+ *   surviving triangle names, writes new_vert_offsets / new_tri_offsets [S+1] (every element) and keeps positions in `workspace`
+ *   (int32 words); the caller reads the two totals once, sizes the outputs and calls emit with the same mesh and workspace.  emit
+ *   writes the named clusters' vertices and normals in cluster order and the surviving triangles in input order with their winding,
+ *   faces local to their shape; nothing is written beyond max_verts / max_tris, every element below the totals is written, nothing
+ *   is read from an output.  Coincident duplicate triangles are kept. */
+int sg_simplify_bounds(const float* vertices, const int64_t* vert_offsets, long S, long V, float* lo, float* hi, hipStream_t stream);
+int sg_simplify_keys(const float* vertices, const int64_t* vert_offsets, long S, long V, const float* origin, const float* cell,
+                     const int* cells, int64_t* keys, hipStream_t stream);
+int sg_simplify_count(const int64_t* faces, const int64_t* vert_offsets, const int64_t* tri_offsets, long S, long V, long F,
+                      const int64_t* keys, int* counts, hipStream_t stream);
+size_t sg_simplify_clusters_workspace_bytes(long S, long V);
+int sg_simplify_clusters(const int64_t* sorted_keys, const int64_t* order, const int64_t* vert_offsets, long S, long V,
+                         int* sorted_cluster, int* vertex_cluster, int64_t* cluster_offsets, void* workspace, size_t workspace_bytes,
+                         hipStream_t stream);
+int sg_simplify_corners(const int64_t* faces, const int64_t* vert_offsets, const int64_t* tri_offsets, long S, long V, long F,
+                        const int* vertex_cluster, int64_t* corner_keys, hipStream_t stream);
+int sg_simplify_place(const float* vertices, const float* normals, const int64_t* faces, const int64_t* vert_offsets,
+                      const int64_t* tri_offsets, long S, long V, long F, const int64_t* sorted_keys, const int64_t* order,
+                      const int* sorted_cluster, const int64_t* corner_sorted, long C, const float* origin, const float* cell,
+                      int placement, float* cluster_vertices, float* cluster_normals, hipStream_t stream);
+size_t sg_simplify_faces_workspace_bytes(long S, long C, long F);
+int sg_simplify_faces_count(const int64_t* faces, const int64_t* vert_offsets, const int64_t* tri_offsets, long S, long V, long F,
+                            const int* vertex_cluster, const int64_t* cluster_offsets, long C, int64_t* new_vert_offsets,
+                            int64_t* new_tri_offsets, void* workspace, size_t workspace_bytes, hipStream_t stream);
+int sg_simplify_faces_emit(const float* cluster_vertices, const float* cluster_normals, const int64_t* faces,
+                           const int64_t* vert_offsets, const int64_t* tri_offsets, long S, long V, long F, const int* vertex_cluster,
+                           long C, const int64_t* new_vert_offsets, float* out_vertices, float* out_normals, int64_t* out_faces,
+                           long max_verts, long max_tris, void* workspace, size_t workspace_bytes, hipStream_t stream);
+
 /* ---- K13: point-cloud evaluation: Chamfer matrices, nearest neighbours, occupancy histograms -----------------------------------
  * Clouds are [S][P][3] fp32, contiguous.  Every pair (a, b) of points has ONE value, in f32:
  *   dx = ax - bx, dy = ay - by, dz = az - bz;   d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx))

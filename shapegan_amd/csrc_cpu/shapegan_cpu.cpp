@@ -1764,6 +1764,7 @@ int sg_scatter_max_gather_cpu(const float* x, const int* arg, float* out, long N
 #include "../csrc/raymarch_core.h"
 #include "../csrc/pointcloud_core.h"
 #include "../csrc/topology_core.h"
+#include "../csrc/simplify_core.h"
 
 extern "C" {
 
@@ -2069,6 +2070,202 @@ int sg_topo_keep_emit_cpu(const float* vertices, const float* normals, const int
         out_faces[o * 3] = pos_v[a] - base;
         out_faces[o * 3 + 1] = pos_v[b] - base;
         out_faces[o * 3 + 2] = pos_v[c] - base;
+    }
+    return SG_OK;
+}
+
+// ---- K12c: mesh simplification (csrc/simplify.hip) -------------------------------------------------------------------------------
+// The same keys, cluster numbers, corner records, sums (the header's tiles of 64) and compaction as the kernels, walked in order; the
+// clusters are placed in parallel.
+static bool simp_sizes(long S, long V, long F) {
+    return S >= 1 && S < SG_SIMPLIFY_MAX_SHAPES && V >= 0 && F >= 0 && V <= 2147483647L && F <= 2147483647L;
+}
+
+int sg_simplify_bounds_cpu(const float* vertices, const int64_t* vert_offsets, long S, long V, float* lo, float* hi, void*) {
+    CPU_CHECK(simp_sizes(S, V, 0));
+    CPU_CHECK(vert_offsets && lo && hi && (V == 0 || vertices));
+    for (long s = 0; s < S; ++s) {
+        const long v0 = std::max<long>(vert_offsets[s], 0), v1 = std::min<long>(vert_offsets[s + 1], V);
+        for (int k = 0; k < 3; ++k) {
+            int mn = sg_float_key(3.4028234663852886e38f), mx = sg_float_key(-3.4028234663852886e38f);
+            for (long v = v0; v < v1; ++v) {
+                const float x = vertices[v * 3 + k];
+                if (!(fabsf(x) <= 3.4028234663852886e38f)) continue;
+                mn = std::min(mn, sg_float_key(x));
+                mx = std::max(mx, sg_float_key(x));
+            }
+            lo[s * 3 + k] = mn <= mx ? sg_key_float(mn) : 0.0f;
+            hi[s * 3 + k] = mn <= mx ? sg_key_float(mx) : 0.0f;
+        }
+    }
+    return SG_OK;
+}
+
+int sg_simplify_keys_cpu(const float* vertices, const int64_t* vert_offsets, long S, long V, const float* origin, const float* cell,
+                         const int* cells, int64_t* keys, void*) {
+    CPU_CHECK(simp_sizes(S, V, 0));
+    CPU_CHECK(vert_offsets && origin && cell && cells && (V == 0 || (vertices && keys)));
+    for (long v = 0; v < V; ++v) {
+        const long s = sg_topo_shape_of(vert_offsets, S, v);
+        keys[v] = sg_simplify_key(s, vertices + v * 3, origin + s * 3, cell[s * 2 + 1], cells[s]);
+    }
+    return SG_OK;
+}
+
+int sg_simplify_count_cpu(const int64_t* faces, const int64_t* vert_offsets, const int64_t* tri_offsets, long S, long V, long F,
+                          const int64_t* keys, int* counts, void*) {
+    CPU_CHECK(simp_sizes(S, V, F));
+    CPU_CHECK(vert_offsets && tri_offsets && counts && (V == 0 || keys) && (F == 0 || faces));
+    for (long s = 0; s < S; ++s) counts[s] = 0;
+    for (long f = 0; f < F; ++f) {
+        long s, a, b, c;
+        if (!topo_corners(faces, vert_offsets, tri_offsets, S, V, f, s, a, b, c)) continue;
+        if (keys[a] != keys[b] && keys[b] != keys[c] && keys[a] != keys[c]) ++counts[s];
+    }
+    return SG_OK;
+}
+
+int sg_simplify_clusters_cpu(const int64_t* sorted_keys, const int64_t* order, const int64_t* vert_offsets, long S, long V,
+                             int* sorted_cluster, int* vertex_cluster, int64_t* cluster_offsets, void*, size_t, void*) {
+    CPU_CHECK(simp_sizes(S, V, 0));
+    CPU_CHECK(vert_offsets && cluster_offsets && (V == 0 || (sorted_keys && order && sorted_cluster && vertex_cluster)));
+    std::vector<int> head(V), excl(V);
+    for (long i = 0; i < V; ++i) head[i] = i == 0 || sorted_keys[i] != sorted_keys[i - 1];
+    topo_scan(head, V, excl.data(), vert_offsets, S, cluster_offsets);
+    for (long i = 0; i < V; ++i) {
+        sorted_cluster[i] = excl[i] + head[i] - 1;
+        if (order[i] >= 0 && order[i] < V) vertex_cluster[order[i]] = sorted_cluster[i];
+    }
+    return SG_OK;
+}
+
+int sg_simplify_corners_cpu(const int64_t* faces, const int64_t* vert_offsets, const int64_t* tri_offsets, long S, long V, long F,
+                            const int* vertex_cluster, int64_t* corner_keys, void*) {
+    CPU_CHECK(simp_sizes(S, V, F));
+    CPU_CHECK(vert_offsets && tri_offsets && (V == 0 || vertex_cluster) && (F == 0 || (faces && corner_keys)));
+    for (long f = 0; f < F; ++f) {
+        long s, a, b, c;
+        const bool counts = topo_corners(faces, vert_offsets, tri_offsets, S, V, f, s, a, b, c);
+        sg_simplify_corner_keys(counts, counts ? vertex_cluster[a] : 0, counts ? vertex_cluster[b] : 0, counts ? vertex_cluster[c] : 0, f,
+                                corner_keys + 3 * f);
+    }
+    return SG_OK;
+}
+
+// the header's tree over one tile: s[l] += s[l + off] for off = 32 .. 1; returns s[0]
+static double simp_tile(double* s) {
+    for (int off = 32; off > 0; off >>= 1)
+        for (int l = 0; l < off; ++l) s[l] += s[l + off];
+    return s[0];
+}
+
+int sg_simplify_place_cpu(const float* vertices, const float* normals, const int64_t* faces, const int64_t* vert_offsets,
+                          const int64_t* tri_offsets, long S, long V, long F, const int64_t* sorted_keys, const int64_t* order,
+                          const int* sorted_cluster, const int64_t* corner_sorted, long C, const float* origin, const float* cell,
+                          int placement, float* cluster_vertices, float* cluster_normals, void*) {
+    CPU_CHECK(simp_sizes(S, V, F) && C >= 0 && C <= V);
+    CPU_CHECK(placement == SG_SIMPLIFY_QUADRIC || placement == SG_SIMPLIFY_MEAN);
+    CPU_CHECK(vert_offsets && tri_offsets && origin && cell);
+    CPU_CHECK(V == 0 || (vertices && normals && sorted_keys && order && sorted_cluster));
+    CPU_CHECK(F == 0 || placement == SG_SIMPLIFY_MEAN || (faces && corner_sorted));
+    CPU_CHECK(C == 0 || (cluster_vertices && cluster_normals));
+#pragma omp parallel for schedule(dynamic, 64)
+    for (long c = 0; c < C; ++c) {
+        const long v0 = std::lower_bound(sorted_cluster, sorted_cluster + V, (int)c) - sorted_cluster;
+        const long v1 = c + 1 > 2147483647L ? V : std::lower_bound(sorted_cluster, sorted_cluster + V, (int)(c + 1)) - sorted_cluster;
+        if (v0 >= v1) {
+            for (int k = 0; k < 3; ++k) cluster_vertices[c * 3 + k] = cluster_normals[c * 3 + k] = 0.0f;
+            continue;
+        }
+        const int64_t key = sorted_keys[v0];
+        const long s = std::min(std::max(sg_simplify_key_shape(key), 0L), S - 1);
+        const float h = cell[s * 2];
+        double p0[3];
+        sg_simplify_centre(key, origin + s * 3, h, p0);
+        double vsum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, tile[9][SG_SIMPLIFY_TILE];
+        for (long base = v0; base < v1; base += SG_SIMPLIFY_TILE) {
+            for (int l = 0; l < SG_SIMPLIFY_TILE; ++l) {
+                const long i = base + l, v = i < v1 ? order[i] : -1;
+                for (int k = 0; k < 3; ++k) {
+                    tile[k][l] = v >= 0 && v < V ? (double)vertices[v * 3 + k] : 0.0;
+                    tile[3 + k][l] = v >= 0 && v < V ? (double)normals[v * 3 + k] : 0.0;
+                }
+            }
+            for (int k = 0; k < 6; ++k) vsum[k] += simp_tile(tile[k]);
+        }
+        double q[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (placement == SG_SIMPLIFY_QUADRIC) {
+            const int64_t* end = corner_sorted + 3 * F;
+            const long c0 = std::lower_bound(corner_sorted, end, (int64_t)c << 31) - corner_sorted;
+            const long c1 = std::lower_bound(corner_sorted, end, (int64_t)(c + 1) << 31) - corner_sorted;
+            for (long base = c0; base < c1; base += SG_SIMPLIFY_TILE) {
+                for (int l = 0; l < SG_SIMPLIFY_TILE; ++l) {
+                    double x[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+                    const long i = base + l;
+                    if (i < c1) {
+                        const long f = sg_simplify_corner_triangle(corner_sorted[i]);
+                        long ts, a, b, cc;
+                        if (f < F && topo_corners(faces, vert_offsets, tri_offsets, S, V, f, ts, a, b, cc))
+                            sg_simplify_quadric(vertices + a * 3, vertices + b * 3, vertices + cc * 3, p0, x);
+                    }
+                    for (int k = 0; k < 9; ++k) tile[k][l] = x[k];
+                }
+                for (int k = 0; k < 9; ++k) q[k] += simp_tile(tile[k]);
+            }
+        }
+        const double count = (double)(v1 - v0);
+        const double mean[3] = {vsum[0] / count, vsum[1] / count, vsum[2] / count};
+        sg_simplify_place(q, mean, p0, h, placement, cluster_vertices + c * 3);
+        sg_simplify_normal(vsum + 3, cluster_normals + c * 3);
+    }
+    return SG_OK;
+}
+
+int sg_simplify_faces_count_cpu(const int64_t* faces, const int64_t* vert_offsets, const int64_t* tri_offsets, long S, long V, long F,
+                                const int* vertex_cluster, const int64_t* cluster_offsets, long C, int64_t* new_vert_offsets,
+                                int64_t* new_tri_offsets, void* workspace, size_t workspace_bytes, void*) {
+    CPU_CHECK(simp_sizes(S, V, F) && C >= 0 && C <= V);
+    CPU_CHECK(vert_offsets && tri_offsets && cluster_offsets && new_vert_offsets && new_tri_offsets && workspace);
+    CPU_CHECK((V == 0 || vertex_cluster) && (F == 0 || faces));
+    CPU_CHECK(workspace_bytes >= (size_t)(2 * C + 2 * F) * sizeof(int));
+    int *named = (int*)workspace, *pos_c = named + C, *kept = pos_c + C, *pos_t = kept + F;
+    std::vector<int> nm(C, 0), kt(F, 0);
+    for (long f = 0; f < F; ++f) {
+        long s, a, b, c;
+        if (!topo_corners(faces, vert_offsets, tri_offsets, S, V, f, s, a, b, c)) continue;
+        const long ca = vertex_cluster[a], cb = vertex_cluster[b], cc = vertex_cluster[c];
+        if (ca != cb && cb != cc && ca != cc && ca >= 0 && cb >= 0 && cc >= 0 && ca < C && cb < C && cc < C) kt[f] = nm[ca] = nm[cb] = nm[cc] = 1;
+    }
+    for (long c = 0; c < C; ++c) named[c] = nm[c];
+    for (long f = 0; f < F; ++f) kept[f] = kt[f];
+    topo_scan(nm, C, pos_c, cluster_offsets, S, new_vert_offsets);
+    topo_scan(kt, F, pos_t, tri_offsets, S, new_tri_offsets);
+    return SG_OK;
+}
+
+int sg_simplify_faces_emit_cpu(const float* cluster_vertices, const float* cluster_normals, const int64_t* faces,
+                               const int64_t* vert_offsets, const int64_t* tri_offsets, long S, long V, long F,
+                               const int* vertex_cluster, long C, const int64_t* new_vert_offsets, float* out_vertices,
+                               float* out_normals, int64_t* out_faces, long max_verts, long max_tris, void* workspace,
+                               size_t workspace_bytes, void*) {
+    CPU_CHECK(simp_sizes(S, V, F) && C >= 0 && C <= V && max_verts >= 0 && max_tris >= 0);
+    CPU_CHECK(vert_offsets && tri_offsets && new_vert_offsets && workspace);
+    CPU_CHECK((C == 0 || (cluster_vertices && cluster_normals)) && (V == 0 || vertex_cluster) && (F == 0 || faces));
+    CPU_CHECK((max_verts == 0 || (out_vertices && out_normals)) && (max_tris == 0 || out_faces));
+    CPU_CHECK(workspace_bytes >= (size_t)(2 * C + 2 * F) * sizeof(int));
+    const int *named = (const int*)workspace, *pos_c = named + C, *kept = pos_c + C, *pos_t = kept + F;
+    for (long c = 0; c < C; ++c) {
+        if (!named[c] || pos_c[c] >= max_verts) continue;
+        memcpy(out_vertices + (long)pos_c[c] * 3, cluster_vertices + c * 3, 3 * sizeof(float));
+        memcpy(out_normals + (long)pos_c[c] * 3, cluster_normals + c * 3, 3 * sizeof(float));
+    }
+    for (long f = 0; f < F; ++f) {
+        long s, a, b, c;
+        if (!kept[f] || pos_t[f] >= max_tris || !topo_corners(faces, vert_offsets, tri_offsets, S, V, f, s, a, b, c)) continue;
+        const long base = new_vert_offsets[s], o = pos_t[f];
+        out_faces[o * 3] = pos_c[vertex_cluster[a]] - base;
+        out_faces[o * 3 + 1] = pos_c[vertex_cluster[b]] - base;
+        out_faces[o * 3 + 2] = pos_c[vertex_cluster[c]] - base;
     }
     return SG_OK;
 }

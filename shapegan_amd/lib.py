@@ -174,6 +174,16 @@ SIGNATURES = {
     "sg_topo_keep_workspace_bytes": (_Z, [_L, _L, _L]),
     "sg_topo_keep_count": (c_int, [_P, _P, _P, _L, _L, _L, _P, _P, _L, _P, _P, _P, _P, _Z, _P]),
     "sg_topo_keep_emit": (c_int, [_P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P, _L, _L, _P, _Z, _P]),
+    "sg_simplify_bounds": (c_int, [_P, _P, _L, _L, _P, _P, _P]),
+    "sg_simplify_keys": (c_int, [_P, _P, _L, _L, _P, _P, _P, _P, _P]),
+    "sg_simplify_count": (c_int, [_P, _P, _P, _L, _L, _L, _P, _P, _P]),
+    "sg_simplify_clusters_workspace_bytes": (_Z, [_L, _L]),
+    "sg_simplify_clusters": (c_int, [_P, _P, _P, _L, _L, _P, _P, _P, _P, _Z, _P]),
+    "sg_simplify_corners": (c_int, [_P, _P, _P, _L, _L, _L, _P, _P, _P]),
+    "sg_simplify_place": (c_int, [_P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P, _L, _P, _P, _I, _P, _P, _P]),
+    "sg_simplify_faces_workspace_bytes": (_Z, [_L, _L, _L]),
+    "sg_simplify_faces_count": (c_int, [_P, _P, _P, _L, _L, _L, _P, _P, _L, _P, _P, _P, _Z, _P]),
+    "sg_simplify_faces_emit": (c_int, [_P, _P, _P, _P, _P, _L, _L, _L, _P, _L, _P, _P, _P, _P, _L, _L, _P, _Z, _P]),
     "sg_chamfer_matrix_workspace_bytes": (_Z, [_L, _L, _L, _L]),
     "sg_chamfer_matrix": (c_int, [_P, _P, _L, _L, _L, _L, _P, _P, _P, _Z, _P]),
     "sg_chamfer_nearest": (c_int, [_P, _P, _L, _L, _L, _P, _P, _P, _P, _P]),

@@ -179,6 +179,19 @@ class Mesh(object):
         """Referenced vertices - distinct edges + triangles."""
         return int(self._components()[1].euler.sum())
 
+    def simplify(self, **options):
+        """The mesh simplified by quadric vertex clustering on the C++ twin: shapegan_amd.simplify.simplify_meshes of a batch of one
+        (cell= / cells= / target_triangles=, placement=).  A mesh without vertex normals comes back without them."""
+        from . import simplify
+        normals = self.vertex_normals if self.vertex_normals is not None else np.zeros_like(self.vertices)
+        batch = MeshBatch(torch.from_numpy(self.vertices), torch.from_numpy(normals), torch.from_numpy(self.faces),
+                          torch.tensor([0, self.vertices.shape[0]], dtype=torch.int64),
+                          torch.tensor([0, self.faces.shape[0]], dtype=torch.int64))
+        out = simplify.simplify_meshes(batch, **options)[0].mesh(0)
+        if self.vertex_normals is None:
+            out.vertex_normals = None
+        return out
+
     def to_trimesh(self):
         import trimesh
         return trimesh.Trimesh(vertices=self.vertices, faces=self.faces, vertex_normals=self.vertex_normals, process=False)
@@ -223,6 +236,12 @@ class MeshBatch(object):
         """The MeshBatch of the components `rule` keeps (shapegan_amd.topology.clean_meshes)."""
         from . import topology
         return topology.clean_meshes(self, rule)[0]
+
+    def simplify(self, **options):
+        """The MeshBatch simplified by quadric vertex clustering (shapegan_amd.simplify.simplify_meshes: cell= / cells= /
+        target_triangles=, placement=)."""
+        from . import simplify
+        return simplify.simplify_meshes(self, **options)[0]
 
     def sample_surface(self, count, generator=None, return_empty=False):
         """[S, count, 3] points on the device of the meshes, area-weighted; uniforms [S, count, 3] from torch.rand with

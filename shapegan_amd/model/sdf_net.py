@@ -248,7 +248,7 @@ class SDFNet(SavableModule):
         return result.grid, result.stats
 
     def get_mesh(self, latent_code, voxel_resolution=64, sphere_only=True, raise_on_empty=False, level=0, narrow_band=False, refine=0,
-                 clean=False):
+                 clean=False, simplify=None):
         """Marching cubes of the SDF grid (model/sdf_net.py:97-112) on the device: a mesh.Mesh, None when the grid does not cross
         `level` (ValueError with raise_on_empty).  Coordinates are the reference's: the grid of get_voxels padded once more with
         1, spacing 2 / R, shifted by -1 — grid index i lands at (i + 1 + t) 2/R - 1 (sphere_only) or (i + 2 + t) 2/R - 1 (the
@@ -256,7 +256,9 @@ class SDFNet(SavableModule):
         of its arguments brick / band / lipschitz).  refine = K > 0: every vertex is then moved onto the network's own level set by K
         Newton steps and given its exact normal (surface.refine_meshes, at most a cell diagonal away); 0 is the marching-cubes mesh.
         clean: a rule of topology.clean_meshes ("largest", True, a dict) applied to the marching-cubes mesh before refine; a mesh of
-        which nothing is left counts as empty.  False: no cleaning."""
+        which nothing is left counts as empty.  False: no cleaning.  simplify: an int (the most triangles to keep) or a dict of the
+        arguments of simplify.simplify_meshes, applied last, after clean and refine (a grid so coarse that no triangle
+        survives gives a Mesh without triangles, not None); None: the mesh as it is."""
         size = 2
         grids = self.voxel_grids(latent_code.reshape(1, -1), voxel_resolution, sphere_only=sphere_only, level=level,
                                  **narrow_band_options(narrow_band))
@@ -271,6 +273,9 @@ class SDFNet(SavableModule):
             from ..surface import cell_diagonal, refine_meshes
             batch, _ = refine_meshes(self, latent_code.reshape(1, -1), batch, level=level, iterations=int(refine),
                                      max_move=cell_diagonal(voxel_resolution))
+        if simplify is not None and simplify is not False:
+            from ..simplify import apply_option
+            batch = apply_option(batch, simplify)
         return batch.mesh(0)
 
     def get_uniform_surface_points(self, latent_code, point_count=1000, voxel_resolution=64, sphere_only=True, level=0,

@@ -81,12 +81,13 @@ def fit_latent_codes(sdf_net, points, sdf, segment_offsets=None, points_per_shap
     return z, loss
 
 
-def reconstruct_meshes(sdf_net, latent_codes, voxel_resolution=64, level=0, narrow_band=False, refine=0, clean=False):
+def reconstruct_meshes(sdf_net, latent_codes, voxel_resolution=64, level=0, narrow_band=False, refine=0, clean=False, simplify=None):
     """MeshBatch of the level sets of the codes [S,L]: shape s is SDFNet.get_mesh(latent_codes[s], voxel_resolution, level=level), all
     grids and the marching cubes in batched launches.  narrow_band: the grids come from the brick path of SDFNet.voxel_grids, built for
     `level` (True, or a dict of its arguments brick / band / lipschitz).  refine = K > 0: the vertices are moved onto the network's level
     set by K Newton steps and carry its normals (surface.refine_meshes with the cell diagonal as the limit), as get_mesh(refine=K).
-    clean: a rule of topology.clean_meshes ("largest", True, a dict), applied after marching cubes and before refine."""
+    clean: a rule of topology.clean_meshes ("largest", True, a dict), applied after marching cubes and before refine.  simplify: an int
+    (the most triangles per shape) or a dict of the arguments of simplify.simplify_meshes, applied last; None: nothing."""
     codes = latent_codes.detach().reshape(-1, sdf_net.latent_code_size)
     grids = sdf_net.voxel_grids(codes, voxel_resolution, sphere_only=True, level=level, **narrow_band_options(narrow_band))
     batch = marching_cubes(grids, level=level, spacing=2 / voxel_resolution, origin=-1, pad=True, pad_value=1.0)
@@ -95,6 +96,9 @@ def reconstruct_meshes(sdf_net, latent_codes, voxel_resolution=64, level=0, narr
     if refine:
         from .surface import cell_diagonal, refine_meshes
         batch, _ = refine_meshes(sdf_net, codes, batch, level=level, iterations=int(refine), max_move=cell_diagonal(voxel_resolution))
+    if simplify is not None and simplify is not False:
+        from .simplify import apply_option
+        batch = apply_option(batch, simplify)
     return batch
 
 
@@ -126,6 +130,8 @@ def main(argv=None):
     ap.add_argument("--refine", type=int, default=0, help="Newton steps that move the mesh vertices onto the network's level set")
     ap.add_argument("--clean", nargs="?", const="default", default=None, choices=("default", "largest"),
                     help="drop floating pieces of the reconstructions: below 1 %% of the area (default) or all but the largest")
+    ap.add_argument("--simplify", type=int, default=None, metavar="N",
+                    help="simplify the reconstructions to at most N triangles each (after --clean and --refine)")
     ap.add_argument("--scan-count", type=int, default=50)
     ap.add_argument("--scan-resolution", type=int, default=1024)
     ap.add_argument("--chamfer-points", type=int, default=2048)
@@ -155,7 +161,7 @@ def main(argv=None):
     if args.meshes or args.chamfer:
         from .topology import clean_option
         batch = reconstruct_meshes(net, codes, args.resolution, narrow_band=args.narrow_band, refine=args.refine,
-                                   clean=clean_option(args.clean))
+                                   clean=clean_option(args.clean), simplify=args.simplify)
     if args.meshes:
         os.makedirs(args.meshes, exist_ok=True)
         for i, mesh in enumerate(batch.meshes()):
