@@ -546,7 +546,10 @@ def writers_known(*tensors):
 # belongs to it.  In a plain backward (no create_graph) the weight-gradient kernels write straight into that slice and hand
 # autograd a view of it: AccumulateGrad adopts the view as p.grad (no `p.grad += g` launch, no copy), post-accumulate hooks
 # fire as usual.  Only the FIRST contribution of a zero_grad() cycle may do this (a second write would clobber the first);
-# later contributions come back as ordinary tensors and autograd adds them in place — into the same slice.
+# later contributions come back as ordinary tensors and autograd adds them in place — into the same slice.  That holds across
+# backward calls.  Two contributions to one parameter WITHIN one backward (a module applied twice in one graph) are summed by the
+# engine before AccumulateGrad sees either: p.grad is then an ordinary tensor holding the sum, the slice holds the first
+# contribution only, and the optimizers read p.grad (optim._Base._segments) or copy it in (optim._Flat.adopt_grads).
 import weakref  # noqa: E402
 
 

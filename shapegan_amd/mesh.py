@@ -259,13 +259,13 @@ def sample_packed(vertices, faces, vert_offsets, tri_offsets, uniforms):
     S, P = uniforms.shape[0], uniforms.shape[1]
     dev = uniforms.device
     F = faces.shape[0]
-    uniforms = f32c(uniforms)
+    vertices, faces, uniforms = f32c(vertices), faces.contiguous(), f32c(uniforms)
     out = torch.empty((S, P, 3), dtype=torch.float32, device=dev)
     empty = torch.empty(S, dtype=torch.int32, device=dev)
     lib = L.load()
     ws = L.workspace("mesh_sample", lib.sg_mesh_sample_workspace_bytes(S, F), dev)
     try:
-        check(lib.sg_mesh_sample(ptr(f32c(vertices)), ptr(faces.contiguous()), ptr(vert_offsets), ptr(tri_offsets), S, F,
+        check(lib.sg_mesh_sample(ptr(vertices), ptr(faces), ptr(vert_offsets), ptr(tri_offsets), S, F,
                                  ptr(uniforms), P, ptr(out), ptr(empty), ptr(ws), ws.numel(), stream()), "mesh_sample")
     finally:
         L.reset_call_state()

@@ -426,10 +426,10 @@ class ActBwd(Function):
         if ctx.needs_input_grad[0] and ctx.act in (ACT_TANH, ACT_SIGMOID):
             # d/dy of dy*(1-y^2) resp. dy*y*(1-y): the second-order term of a double backward through tanh / sigmoid
             # (zero almost everywhere for LeakyReLU / ReLU).  Needs dy, which forward did not have to keep otherwise.
-            dy = ctx.dy
+            # (ggx may arrive as a stride-0 expand: its contiguous copy must be held until the call has been made)
+            dy, ggc = f32c(ctx.dy.detach()), f32c(ggx.detach())
             g_y = torch.empty_like(y)
-            check(_lib().sg_act_bwd_dy(ptr(y), ptr(f32c(dy.detach())), ptr(f32c(ggx.detach())), ptr(g_y), y.numel(), ctx.act,
-                                       stream()), "act_bwd_dy")
+            check(_lib().sg_act_bwd_dy(ptr(y), ptr(dy), ptr(ggc), ptr(g_y), y.numel(), ctx.act, stream()), "act_bwd_dy")
         return g_y, g_dy, None, None
 
 
@@ -893,14 +893,16 @@ class BatchNormAct(Function):
         N, C, S, training, act, slope = ctx.cfg
         gy = f32c(gy)
         dx = torch.empty_like(x)
-        dgamma = _param_grad_out(gamma, gamma.shape, x.device)
-        dbeta = _param_grad_out(beta, beta.shape, x.device)
+        # (a frozen gamma / beta gets scratch: its slice of the flat gradient buffer is not this backward's to write)
+        dgamma = _param_grad_out(gamma if ctx.needs_input_grad[1] else None, gamma.shape, x.device)
+        dbeta = _param_grad_out(beta if ctx.needs_input_grad[2] else None, beta.shape, x.device)
         lib = _lib()
         ws = workspace("bn", lib.sg_bn_workspace_bytes(C), x.device)
         check(lib.sg_bn_bwd(ptr(gy), ptr(x), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), ptr(dx), ptr(dgamma),
                             ptr(dbeta), N, C, S, 1 if training else 0, act, slope, ptr(ws), ws.numel(), stream()),
               "bn_bwd")
-        return dx, dgamma, dbeta, None, None, None, None, None, None, None, None
+        return (dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None,
+                None, None, None, None, None, None, None, None)
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -940,7 +942,8 @@ class _PackCache(object):
             lib = _lib()
             dev = params[0].device
             packed = torch.empty(lib.sg_sdfnet_packed_floats(kin_used), dtype=torch.float32, device=dev)
-            arr = (ctypes.c_void_p * 16)(*[ptr(f32c(p.detach())) for p in params])
+            held = [f32c(p.detach()) for p in params]      # (a converted copy lives until the call has been made)
+            arr = (ctypes.c_void_p * 16)(*[ptr(t) for t in held])
             check(lib.sg_sdfnet_pack(arr, latent, kin_used, ptr(packed), stream()), "sdfnet_pack")
             self.entries[dev] = (key, packed)
         return packed
@@ -962,13 +965,15 @@ class _PackCache(object):
         zb5 = torch.empty((S, _H), dtype=torch.float32, device=dev)
         if packed is None:
             packed = torch.empty(lib.sg_sdfnet_packed_floats(3), dtype=torch.float32, device=dev)
-            arr = (ctypes.c_void_p * 16)(*[ptr(f32c(p.detach())) for p in params])
+            held = [f32c(p.detach()) for p in params]
+            arr = (ctypes.c_void_p * 16)(*[ptr(t) for t in held])
             check(lib.sg_sdfnet_pack_shape_bias(arr, Lz, ptr(packed), ptr(z), S, ptr(zb1), ptr(zb5), stream()), "sdfnet_pack_shape_bias")
             self.entries[dev] = (key, packed)
             self.fold = None
         else:
-            check(lib.sg_sdfnet_shape_bias(ptr(z), S, Lz, ptr(f32c(params[0])), ptr(f32c(params[1])), ptr(f32c(params[8])),
-                                           ptr(f32c(params[9])), ptr(zb1), ptr(zb5), stream()), "sdfnet_shape_bias")
+            w1, b1, w5, b5 = f32c(params[0]), f32c(params[1]), f32c(params[8]), f32c(params[9])
+            check(lib.sg_sdfnet_shape_bias(ptr(z), S, Lz, ptr(w1), ptr(b1), ptr(w5), ptr(b5), ptr(zb1), ptr(zb5), stream()),
+                  "sdfnet_shape_bias")
         return packed, zb1, zb5
 
     def prepare_fold(self, params, z):
@@ -1072,9 +1077,10 @@ def _sdf_param_grads(ctx_params, needs, dz, dz8, acts, ldn, N, x_parts, kin_tota
             arr = (ctypes.c_void_p * 7)(*[ptr(t) for t in bouts])
             ws = workspace("sdf_finish", lib.sg_sdfnet_bwd_finish_workspace_bytes(N), dev)
             seg_off, S, t1, t5 = seg if seg is not None else (None, 0, None, None)
+            tk = L.tickets("sdf_finish", dev)
             check(lib.sg_sdfnet_bwd_finish(ptr(dz), ptr(bsum), ldn, N, 1 if extended else 0, arr, ptr(w8), ptr(b8), ptr(w1),
                                            kin_total, ptr(w5) + 4 * _H if extended else None, _H + kin_total, ptr(seg_off), S,
-                                           ptr(t1), ptr(t5), ptr(ws), ws.numel(), ptr(L.tickets("sdf_finish", dev)), stream()),
+                                           ptr(t1), ptr(t5), ptr(ws), ws.numel(), ptr(tk), stream()),
                   "sdfnet_bwd_finish")
     else:
         for layer_dz, out in enumerate(bouts):
@@ -1251,8 +1257,9 @@ class SDFNetShapes(Function):
                 seg = (seg_off, S, t1, t5)
             else:
                 ws = workspace("sdf_finish", lib.sg_sdfnet_bwd_finish_workspace_bytes(N), dev)
+                tk = L.tickets("sdf_finish", dev)
                 check(lib.sg_sdfnet_bwd_finish(ptr(dz), ptr(bsum), N, N, 0, None, None, None, None, 0, None, 0, ptr(seg_off), S,
-                                               ptr(t1), ptr(t5), ptr(ws), ws.numel(), ptr(L.tickets("sdf_finish", dev)), stream()),
+                                               ptr(t1), ptr(t5), ptr(ws), ws.numel(), ptr(tk), stream()),
                       "sdfnet_bwd_finish")
         fold = (need_p or need_z) and S <= _FOLD_MAX_SHAPES
         if fold and need_z:
@@ -1562,8 +1569,9 @@ class _GenPackCache(object):
         if entry is None or entry[0] != key or not L.writers_known(*params) or _capturing(params[0]):
             lib = _lib()
             packed = torch.empty(lib.sg_sdfnet_packed_floats(3), dtype=torch.float32, device=dev)
-            lins = (ctypes.c_void_p * 16)(*[ptr(f32c(p.detach())) for p in params[:16]])
-            norms = (ctypes.c_void_p * 14)(*[ptr(f32c(p.detach())) for p in params[16:]])
+            held = [f32c(p.detach()) for p in params]      # (a converted copy lives until the call has been made)
+            lins = (ctypes.c_void_p * 16)(*[ptr(t) for t in held[:16]])
+            norms = (ctypes.c_void_p * 14)(*[ptr(t) for t in held[16:]])
             check(lib.sg_sdfgen_pack(lins, norms, ptr(packed), stream()), "sdfgen_pack")
             entry = (key, packed)
             self.entries[dev] = entry
@@ -1633,9 +1641,10 @@ class SDFGenFused(Function):
         barr = (ctypes.c_void_p * 7)(*[ptr(t) for t in bouts])
         narr = (ctypes.c_void_p * 14)(*[ptr(t) for t in ngr])
         ws = workspace("sdfgen_finish", lib.sg_sdfgen_bwd_finish_workspace_bytes(N), dev)
+        tk = L.tickets("sdfgen_finish", dev, 32)
         check(lib.sg_sdfgen_bwd_finish(ptr(dz), ptr(bsum), N, N, barr, ptr(w8), ptr(b8), ptr(w1), 3, ptr(w5) + 4 * _H, _H + 3, narr,
-                                       ptr(seg_off), S, ptr(t1), ptr(t5), ptr(ws), ws.numel(),
-                                       ptr(L.tickets("sdfgen_finish", dev, 32)), stream()), "sdfgen_bwd_finish")
+                                       ptr(seg_off), S, ptr(t1), ptr(t5), ptr(ws), ws.numel(), ptr(tk), stream()),
+              "sdfgen_bwd_finish")
         # the six 256 x 256 x N products dZ_l relu(gamma xhat_{l-1} + beta)^T in one launch (+ one finalize)
         hidden = [_param_grad_out(params[pi], (_H, _H), dev) for pi in (2, 4, 6, 10, 12)]
         pairs = ((4, 3), (1, 0), (2, 1), (3, 2), (5, 4), (6, 5))
@@ -1717,7 +1726,8 @@ class RowDot(Function):
         h, w = f32c(h), f32c(w)
         B, C, K = h.shape
         out = torch.empty((B, C), dtype=torch.float32, device=h.device)
-        check(_lib().sg_rowdot(ptr(h), ptr(w), ptr(f32c(bias)) if bias is not None else None, ptr(out), B, C, K, stream()), "rowdot")
+        bias = f32c(bias) if bias is not None else None
+        check(_lib().sg_rowdot(ptr(h), ptr(w), ptr(bias), ptr(out), B, C, K, stream()), "rowdot")
         ctx.save_for_backward(h, w)
         ctx.has_bias = bias is not None
         return out
@@ -1793,7 +1803,8 @@ class _PointPackCache(object):
         if entry is None or entry[0] != key or not L.writers_known(*weights) or _capturing(weights[0]):
             lib = _lib()
             packed = torch.empty(lib.sg_pointnet_packed_floats(), dtype=torch.float32, device=dev)
-            arr = (ctypes.c_void_p * 4)(*[ptr(f32c(p.detach())) for p in weights])
+            held = [f32c(p.detach()) for p in weights]      # (a converted copy lives until the call has been made)
+            arr = (ctypes.c_void_p * 4)(*[ptr(t) for t in held])
             check(lib.sg_pointnet_pack(arr, ptr(packed), stream()), "pointnet_pack")
             entry = (key, packed)
             self.entries[dev] = entry
@@ -1810,7 +1821,8 @@ def pointnet_select(cache, x, weights, biases):
     out = torch.empty((B, 512), dtype=torch.float32, device=x.device)
     idx = torch.empty((B, 512), dtype=torch.int32, device=x.device)
     ws = workspace("pointnet_select", lib.sg_pointnet_select_workspace_bytes(B, P), x.device)
-    barr = (ctypes.c_void_p * 4)(*[ptr(f32c(b.detach())) for b in biases])
+    held = [f32c(b.detach()) for b in biases]
+    barr = (ctypes.c_void_p * 4)(*[ptr(t) for t in held])
     check(lib.sg_pointnet_select(ptr(x), ptr(packed), barr, B, P, ptr(out), ptr(idx), ptr(ws), ws.numel(), stream()), "pointnet_select")
     return out, idx
 
@@ -1865,8 +1877,9 @@ class MeanSplit(Function):
         n, n_first, w_first, w_rest = ctx.args
         if ctx.dx_unit is not None and L.is_unit_gradient(g):
             return ctx.dx_unit, None, None, None
+        g = f32c(g)
         dx = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
-        check(_lib().sg_loss_mean_split_bwd(ptr(f32c(g)), ptr(dx), n, n_first, w_first, w_rest, stream()), "loss_mean_split_bwd")
+        check(_lib().sg_loss_mean_split_bwd(ptr(g), ptr(dx), n, n_first, w_first, w_rest, stream()), "loss_mean_split_bwd")
         return dx, None, None, None
 
 
@@ -2204,8 +2217,9 @@ class WeightedL1(Function):
     @once_differentiable
     def backward(ctx, g):
         out, target = ctx.saved_tensors
+        g = f32c(g)
         d = torch.empty_like(out)
-        check(_lib().sg_loss_weighted_l1_bwd(ptr(out), ptr(target), ptr(f32c(g)), ptr(d), out.numel(), ctx.neg_weight,
+        check(_lib().sg_loss_weighted_l1_bwd(ptr(out), ptr(target), ptr(g), ptr(d), out.numel(), ctx.neg_weight,
                                              stream()), "loss_weighted_l1_bwd")
         return d, None, None
 
@@ -2243,8 +2257,9 @@ class KLD(Function):
     @once_differentiable
     def backward(ctx, g):
         mean, lv = ctx.saved_tensors
+        g = f32c(g)
         dm, dl = torch.empty_like(mean), torch.empty_like(lv)
-        check(_lib().sg_loss_kld_bwd(ptr(mean), ptr(lv), ptr(f32c(g)), ptr(dm), ptr(dl), mean.numel(), stream()),
+        check(_lib().sg_loss_kld_bwd(ptr(mean), ptr(lv), ptr(g), ptr(dm), ptr(dl), mean.numel(), stream()),
               "loss_kld_bwd")
         return dm, dl
 
@@ -2270,8 +2285,9 @@ class BCEConst(Function):
     @once_differentiable
     def backward(ctx, g):
         (p,) = ctx.saved_tensors
+        g = f32c(g)
         dp = torch.empty_like(p)
-        check(_lib().sg_loss_bce_bwd(ptr(p), ptr(f32c(g)), ptr(dp), p.numel(), ctx.target, stream()), "loss_bce_bwd")
+        check(_lib().sg_loss_bce_bwd(ptr(p), ptr(g), ptr(dp), p.numel(), ctx.target, stream()), "loss_bce_bwd")
         return dp, None
 
 
@@ -2294,8 +2310,9 @@ class NegMeanLog(Function):
     @once_differentiable
     def backward(ctx, g):
         (p,) = ctx.saved_tensors
+        g = f32c(g)
         dp = torch.empty_like(p)
-        check(_lib().sg_loss_neg_mean_log_bwd(ptr(p), ptr(f32c(g)), ptr(dp), p.numel(), stream()), "loss_neg_mean_log_bwd")
+        check(_lib().sg_loss_neg_mean_log_bwd(ptr(p), ptr(g), ptr(dp), p.numel(), stream()), "loss_neg_mean_log_bwd")
         return dp
 
 
@@ -2352,8 +2369,9 @@ class MeanSq(Function):
     @once_differentiable
     def backward(ctx, g):
         x, rw = ctx.saved_tensors
+        g = f32c(g)
         dx = torch.empty_like(x)
-        check(_lib().sg_loss_meansq_bwd(ptr(x), ptr(rw), ptr(f32c(g)), ptr(dx), x.shape[0], x.shape[1], ctx.denom,
+        check(_lib().sg_loss_meansq_bwd(ptr(x), ptr(rw), ptr(g), ptr(dx), x.shape[0], x.shape[1], ctx.denom,
                                         stream()), "loss_meansq_bwd")
         return dx, None, None
 
@@ -2379,9 +2397,10 @@ class DeepSDFLoss(Function):
         # the gradient for an upstream 1 comes out of the same launch (the loss is the root of lib.backward() in the trainer)
         ctx.d_unit = torch.empty_like(out) if ctx.needs_input_grad[0] else None
         ctx.dz_unit = torch.empty_like(z) if ctx.needs_input_grad[2] else None
+        tk = L.tickets("deepsdf", out.device)
         check(_lib().sg_loss_deepsdf_fused(ptr(out), ptr(target), out.numel(), ptr(z), ptr(rw), rows, width, float(denom),
                                            ptr(loss), ptr(ctx.d_unit), ptr(ctx.dz_unit), ptr(ws), ws.numel(),
-                                           ptr(L.tickets("deepsdf", out.device)), stream()), "loss_deepsdf_fused")
+                                           ptr(tk), stream()), "loss_deepsdf_fused")
         ctx.denom = float(denom)
         ctx.save_for_backward(out, target, z, rw)
         return loss
@@ -2392,9 +2411,10 @@ class DeepSDFLoss(Function):
         out, target, z, rw = ctx.saved_tensors
         if L.is_unit_gradient(g) and (ctx.d_unit is not None or ctx.dz_unit is not None):
             return ctx.d_unit, None, ctx.dz_unit, None, None
+        g = f32c(g)
         d, dz = torch.empty_like(out), torch.empty_like(z)
         check(_lib().sg_loss_deepsdf_bwd(ptr(out), ptr(target), out.numel(), ptr(z), ptr(rw), z.shape[0], z.shape[1],
-                                         ctx.denom, ptr(f32c(g)), ptr(d), ptr(dz), stream()), "loss_deepsdf_bwd")
+                                         ctx.denom, ptr(g), ptr(d), ptr(dz), stream()), "loss_deepsdf_bwd")
         return d, None, dz, None, None
 
 
@@ -2423,8 +2443,9 @@ class GradientPenalty(Function):
     @once_differentiable
     def backward(ctx, g):
         g2, norms = ctx.saved_tensors
+        g = f32c(g)
         dg = torch.empty_like(g2)
-        check(_lib().sg_gradient_penalty_bwd(ptr(g2), ptr(norms), ptr(f32c(g)), ptr(dg), g2.shape[0], g2.shape[1],
+        check(_lib().sg_gradient_penalty_bwd(ptr(g2), ptr(norms), ptr(g), ptr(dg), g2.shape[0], g2.shape[1],
                                              ctx.weight, stream()), "gradient_penalty_bwd")
         return dg.reshape(ctx.shape), None
 
@@ -2690,8 +2711,9 @@ def tsne_step(y, P, velocity, gains, exaggeration, momentum, lr, min_gain=0.01, 
         kl = torch.empty(1, dtype=torch.float64, device=dev)
     ws = workspace("tsne_gradient", lib.sg_tsne_gradient_workspace_bytes(N), dev)
     try:
+        grad = _tsne_state("grad", grad, N)
         check(lib.sg_tsne_step(ptr(y), ptr(P), N, float(exaggeration), ptr(plogp), ptr(velocity), ptr(gains), float(momentum), float(lr),
-                               float(min_gain), ptr(_tsne_state("grad", grad, N)), ptr(kl if plogp is not None else None), ptr(ws),
+                               float(min_gain), ptr(grad), ptr(kl if plogp is not None else None), ptr(ws),
                                ws.numel(), stream()), "tsne_step")
     finally:
         L.reset_call_state()

@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 import shapegan_amd.lib as L
+import autograd_cases as AG
 import conv_patterns as GRIDS
 import sdfnet_forms as FORMS
 import test_gpu_modules as M
@@ -423,3 +424,17 @@ def test_grouped_generator_pass_cpu(on_cpu):
     M.test_generator_forward_groups_equals_separate_evaluations(3, 5)
     M.test_wgan_step_with_grouped_generator_pass_equals_the_updates_one_by_one(n_units=1)
     M.test_wgan_step_on_real_batches_delivered_into_the_trainers_slots()
+
+
+# ---- the autograd layer branch by branch (bodies from tests/autograd_cases.py: float64 autograd of the torch composition) --------
+@pytest.mark.parametrize("name,order,layout", AG.PARAMS)
+def test_autograd_table(on_cpu, name, order, layout, monkeypatch):
+    AG.body(name, order, layout, monkeypatch)
+
+
+def test_sample_packed_converts_float64_vertices_and_strided_faces(on_cpu):
+    AG.body_sample_packed_inputs()
+
+
+def test_once_differentiable_losses_raise_at_second_order(on_cpu):
+    AG.body_once_differentiable_losses_raise()

@@ -609,3 +609,24 @@ def test_shape_tiles_cover_every_used_point_once(count, a, b):
         assert (seen[s][:m] == 1).all() and (seen[s][m:] == 0).all()
         assert tile_off[s + 1] - tile_off[s] == (m + 31) // 32
         assert (tiles[tile_off[s]:tile_off[s + 1], 0] == s).all()
+
+
+def test_no_address_is_taken_of_a_tensor_nobody_holds():
+    """`ptr(f32c(x))`, `ptr(x.contiguous())`, `ptr(x.detach())`: where the inner call makes a copy, that copy has no other reference
+    and is freed as soon as ptr() returns — before the C call that was given its address runs.  Every tensor whose address goes
+    into a call is bound to a name first; this fails on any ptr(...) whose argument is itself a call expression."""
+    import ast
+    import glob
+    pkg = os.path.join(ROOT, "shapegan_amd")
+    files = sorted(set(glob.glob(os.path.join(pkg, "*.py")) + glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True)))
+    assert len(files) > 20
+    bad = []
+    for path in files:
+        for node in ast.walk(ast.parse(open(path).read(), path)):
+            if not isinstance(node, ast.Call):
+                continue
+            fn = node.func
+            name = fn.id if isinstance(fn, ast.Name) else fn.attr if isinstance(fn, ast.Attribute) else None
+            if name == "ptr" and any(isinstance(a, ast.Call) for a in node.args):
+                bad.append("%s:%d: %s" % (os.path.relpath(path, ROOT), node.lineno, ast.unparse(node)))
+    assert not bad, "ptr() of a temporary:\n" + "\n".join(bad)
