@@ -1,21 +1,28 @@
-"""Builds libshapegan_hip.so (the C-ABI HIP library) in-tree for gfx950.
+"""Builds libshapegan_hip.so (the C-ABI HIP library), libshapegan_comm.so and libshapegan_cpu.so (the C++ twin) in-tree for gfx950.
 
     python -m shapegan_amd.build            # incremental
     python -m shapegan_amd.build --force
 
 hipcc cross-compiles without a GPU; the .so is git-ignored but travels with the repo snapshot to the GPU box.
+
+include/shapegan_hip.h is the only statement of the ABI.  Before the twin is compiled, its `sg_<name>_cpu` prototypes are generated
+from the header (abi.py) into csrc/_obj/twin_prototypes.h and put in front of the source, so a twin whose parameter list differs
+from the header's is a compile error ("conflicting declaration of C function"); lib.py reads its ctypes table from the same header.
+A new entry point takes a prototype in the header, its definition in a HIP source, and its twin or its name in abi.NO_TWIN.
 """
 import os
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
+from . import abi
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libshapegan_hip.so")
 SOURCES = ["conv3d.hip", "conv3d_halo.hip", "conv3d_edge.hip", "gemm.hip", "sdfnet.hip", "latent_fit.hip", "sdfnet_project.hip", "batchnorm.hip", "elementwise.hip", "pointnet.hip", "losses.hip", "sdf_batch.hip", "head.hip", "mesh.hip", "raymarch.hip", "pointcloud.hip", "raster.hip", "emd.hip", "meshsdf.hip", "tsne.hip", "brickgrid.hip", "topology.hip", "simplify.hip"]
-ABI_HEADER = os.path.join(HERE, "..", "include", "shapegan_hip.h")
+ABI_HEADER = abi.HEADER
 # the arithmetic the HIP kernels share with the twin: an edit rebuilds both libraries
 CORE_HEADERS = [os.path.join(CSRC, h) for h in ("core_fn.h", "mc_tables.h", "mesh_core.h", "raymarch_core.h", "pointcloud_core.h", "raster_core.h", "meshsdf_core.h", "tsne_core.h", "brickgrid_core.h", "project_core.h", "topology_core.h", "simplify_core.h")]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "mfma_tile.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "sdfnet_tile.h"), os.path.join(CSRC, "sdfnet_frozen.h")] + CORE_HEADERS + [ABI_HEADER]
@@ -73,14 +80,18 @@ def build(force=False, verbose=True):
 
 
 CPU_LIB = os.path.join(HERE, "libshapegan_cpu.so")
+TWIN_PROTOTYPES = os.path.join(OBJ, "twin_prototypes.h")
 
 
 def build_cpu(force=False, verbose=True):
     """libshapegan_cpu.so: the plain-C++ twin of the C ABI (csrc_cpu/shapegan_cpu.cpp), g++ + OpenMP, no GPU code."""
     src = os.path.join(HERE, "csrc_cpu", "shapegan_cpu.cpp")
-    if not (force or _stale(CPU_LIB, [src, ABI_HEADER] + CORE_HEADERS)):
+    if not (force or _stale(CPU_LIB, [src, ABI_HEADER, abi.__file__] + CORE_HEADERS)):
         return CPU_LIB
-    cmd = [os.environ.get("CXX", "g++"), "-O3", "-fopenmp", "-fPIC", "-shared", "-std=c++17", "-Wall", src, "-o", CPU_LIB]
+    os.makedirs(OBJ, exist_ok=True)
+    with open(TWIN_PROTOTYPES, "w") as f:
+        f.write(abi.twin_prototypes(abi.DECLARATIONS))
+    cmd = [os.environ.get("CXX", "g++"), "-O3", "-fopenmp", "-fPIC", "-shared", "-std=c++17", "-Wall", "-include", TWIN_PROTOTYPES, src, "-o", CPU_LIB]
     if verbose:
         print(" ".join(cmd), flush=True)
     r = subprocess.run(cmd, capture_output=True, text=True)

@@ -121,7 +121,7 @@ def chamfer_distance(a, b, return_indices=False):
     return (d, ia, ib) if return_indices else d
 
 
-_EMD_MAX_POINTS = 2048            # include/shapegan_hip.h, K15
+_EMD_MAX_POINTS = L.abi.DEFINES["SG_EMD_MAX_POINTS"]            # include/shapegan_hip.h, K15
 _EMD_STATUS = {1: "the auction reached the round cap (SG_EMD_ROUND_CAP)", 2: "eps is too small for the distances of this pair"}
 
 

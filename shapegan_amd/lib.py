@@ -4,239 +4,34 @@ plain-C++ twin of the same C ABI (`sg_<name>_cpu`, csrc_cpu/shapegan_cpu.cpp; SU
 Dispatch is by the DEVICE OF THE TENSORS of a call and nothing else: GPU tensors go to the HIP library, CPU tensors to the
 twin, a call that mixes them raises.  There is no fallback in either direction: a missing libshapegan_hip.so raises as soon
 as a GPU tensor (or any size query) needs it, a missing twin raises when a CPU tensor shows up; neither library ever stands
-in for the other, and no eager-PyTorch path exists.  Signatures mirror include/shapegan_hip.h one to one.
+in for the other, and no eager-PyTorch path exists.
+
+include/shapegan_hip.h is the only statement of the ABI: the ctypes table below (restype and argtypes of every entry point), the
+ACT_* codes and the ABI number are read from it by abi.py when this module is imported, and build.py generates from it the
+`sg_<name>_cpu` prototypes the compiler holds the twin to.  A new entry point takes a prototype in the header, its definition in
+the HIP source, and its twin in csrc_cpu/shapegan_cpu.cpp or its name in abi.NO_TWIN; nothing is transcribed here.
 """
 import ctypes
 import os
 import threading
-from ctypes import c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_void_p
+from ctypes import c_char_p, c_int
 
 import torch
+
+from . import abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SHAPEGAN_HIP_LIB") or os.path.join(_HERE, "libshapegan_hip.so")  # override: A/B builds
 
-ACT_NONE, ACT_LEAKY, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
+ACT_NONE, ACT_LEAKY, ACT_RELU, ACT_TANH, ACT_SIGMOID = (abi.DEFINES["SG_ACT_%s_C" % a] for a in ("NONE", "LEAKY", "RELU", "TANH", "SIGMOID"))
 
-_P, _I, _L, _F, _Z, _D = c_void_p, c_int, c_long, c_float, c_size_t, c_double
-
-# name -> (restype, argtypes); every symbol include/shapegan_hip.h declares
-SIGNATURES = {
-    "sg_abi_version": (c_int, []),
-    "sg_last_error": (c_char_p, []),
-    "sg_conv3d_k4s2p1_fwd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
-    "sg_conv3d_k4s2p1_fwd": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _Z, _P]),
-    "sg_conv3d_k4s2p1_fwd_keep": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _Z, _I, _P]),
-    "sg_conv3d_k4s2p1_pack_images": (c_int, [_I, _P, _P, _P, _P, _P, _P, _P]),
-    "sg_conv3d_k4s2p1_image_layout": (ctypes.c_longlong, [_I, _P, _Z]),
-    "sg_conv3d_k4s2p1_fwd_impl": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _Z, _I, _I, _P]),
-    "sg_conv3d_k4s2p1_dgrad_workspace_bytes": (_Z, [_I, _I]),
-    "sg_conv3d_k4s2p1_dgrad_workspace_bytes_for": (_Z, [_I, _I, _I, _I, _I, _I]),
-    "sg_conv3d_k4s2p1_dgrad": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _Z, _P]),
-    "sg_conv3d_k4s2p1_dgrad_keep": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _Z, _I, _P]),
-    "sg_conv3d_k4s2p1_dgrad_impl": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _Z, _I, _P]),
-    "sg_conv3d_k4s2p1_wgrad_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
-    "sg_conv3d_k4s2p1_wgrad_impl": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _Z, _I, _P]),
-    "sg_conv3d_k4s2p1_wgrad": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
-    "sg_conv3d_k4s2p1_wgrad_act_eligible": (c_int, [_I, _I, _I, _I, _I, _I, _I]),
-    "sg_conv3d_k4s2p1_wgrad_act": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _Z, _P]),
-    "sg_convT3d_k4s2p1_fwd": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _Z, _P]),
-    "sg_convT3d_k4s2p1_to1_pre_eligible": (c_int, [_I, _I, _I, _I, _I]),
-    "sg_convT3d_k4s2p1_to1_pre": (c_int, [_P, _P, _P, _P, _P, _P, _I, _F, _I, _I, _I, _I, _I, _I, _F, _P]),
-    "sg_convT3d_k4s2p1_to1_pre_impl": (c_int, [_P, _P, _P, _P, _P, _P, _I, _F, _I, _I, _I, _I, _I, _I, _F, _I, _P]),
-    "sg_convT3d_k4s2p1_to1_pre_grouped": (c_int, [_P, _P, _P, _P, _P, _P, _I, _F, _I, _I, _I, _I, _I, _I, _F, _I, _L, _P]),
-    "sg_convT3d_k4s2p1_dgrad": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
-    "sg_convT3d_k4s2p1_wgrad": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
-    "sg_gemm_workspace_bytes": (_Z, [_I, _I]),
-    "sg_gemm": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _I, _I, _I, _I, _I, _F, _P, _Z, _P]),
-    "sg_colsum": (c_int, [_P, _P, _I, _I, _L, _P]),
-    "sg_rowsum": (c_int, [_P, _P, _L, _L, _L, _P]),
-    "sg_rowsum_multi": (c_int, [_P, _P, _P, _I, _L, _L, _L, _P]),
-    "sg_segsum": (c_int, [_P, _P, _L, _L, _P, _L, _P]),
-    "sg_bn_workspace_bytes": (_Z, [_I]),
-    "sg_bn_train_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _F, _F, _I, _F, _P, _Z, _P]),
-    "sg_bn_train_stats": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _F, _F, _P, _Z, _P]),
-    "sg_bn_train_fwd_grouped": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _F, _F, _I, _F, _P, _Z, _P]),
-    "sg_bn_train_stats_grouped": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _F, _F, _P, _Z, _P]),
-    "sg_bn_eval_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _F, _I, _F, _P]),
-    "sg_bn_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _F, _P, _Z, _P]),
-    "sg_act_fwd": (c_int, [_P, _P, _L, _I, _F, _P]),
-    "sg_act_bwd": (c_int, [_P, _P, _P, _L, _I, _F, _P]),
-    "sg_act_bwd_rowsum": (c_int, [_P, _P, _P, _P, _L, _L, _I, _F, _P]),
-    "sg_sdfnet_packed_floats": (_Z, [_I]),
-    "sg_sdfnet_acts_floats": (_Z, [_L]),
-    "sg_sdfnet_pack": (c_int, [_P, _I, _I, _P, _P]),
-    "sg_sdfnet_fwd": (c_int, [_P, _L, _P, _P, _I, _P, _I, _P, _P, _L, _P, _P, _P, _L, _L, _P]),
-    "sg_sdfnet_bwd_blocks": (c_long, [_L]),
-    "sg_sdfnet_bwd_tile_start": (c_long, [_L, _L]),
-    "sg_sdfnet_shape_bias": (c_int, [_P, _L, _I, _P, _P, _P, _P, _P, _P, _P]),
-    "sg_sdfnet_pack_shape_bias": (c_int, [_P, _I, _P, _P, _L, _P, _P, _P]),
-    "sg_sdfnet_shape_bias_bwd": (c_int, [_P, _P, _L, _P, _I, _P, _P, _P, _P, _P, _P, _F, _P]),
-    "sg_sdfgen_acts_floats": (_Z, [_L]),
-    "sg_sdfgen_packed_norm_offset": (_L, [_I]),
-    "sg_sdfgen_pack": (c_int, [_P, _P, _P, _P]),
-    "sg_sdfgen_fwd": (c_int, [_P, _P, _P, _P, _L, _P, _F, _P, _P, _L, _L, _P]),
-    "sg_sdfgen_bwd_blocks": (_L, [_L]),
-    "sg_sdfgen_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _P]),
-    "sg_sdfgen_bwd_finish_workspace_bytes": (_Z, [_L]),
-    "sg_sdfgen_bwd_finish": (c_int, [_P, _P, _L, _L, _P, _P, _P, _P, _L, _P, _L, _P, _P, _L, _P, _P, _P, _Z, _P, _P]),
-    "sg_sdfnet_bwd_finish_workspace_bytes": (_Z, [_L]),
-    "sg_sdfnet_bwd_finish": (c_int, [_P, _P, _L, _L, _I, _P, _P, _P, _P, _L, _P, _L, _P, _L, _P, _P, _P, _Z, _P, _P]),
-    "sg_sdfnet_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _I, _L, _L, _P]),
-    "sg_sdfnet_latent_grad": (c_int, [_P, _P, _P, _L, _P, _P, _P, _F, _L, _L, _P, _L, _P, _P]),
-    "sg_sdfnet_latent_reduce": (c_int, [_P, _P, _P, _L, _L, _P, _P, _P, _P]),
-    "sg_sdfnet_project": (c_int, [_P, _P, _L, _P, _P, _P, _F, _I, _I, _F, _P, _L, _P, _P, _P, _P]),
-    "sg_axpby": (c_int, [_P, _P, _P, _L, _F, _F, _P]),
-    "sg_reduce_workspace_bytes": (_Z, []),
-    "sg_reduce_sum": (c_int, [_P, _P, _L, _F, _P, _Z, _P]),
-    "sg_gather_rows": (c_int, [_P, _P, _P, _L, _I, _P]),
-    "sg_scatter_add_rows": (c_int, [_P, _L, _P, _P, _L, _I, _P]),
-    "sg_sdf_batch_sort_max_shapes": (c_int, []),
-    "sg_sdf_batch_sort_workspace_bytes": (_Z, [_L, _L]),
-    "sg_sdf_batch_sort": (c_int, [_P, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _Z, _P]),
-    "sg_rmsprop_step": (c_int, [_P, _P, _P, _L, _F, _F, _F, _F, _F, _P]),
-    "sg_adam_step": (c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _L, _F, _P]),
-    "sg_adam_step_dev": (c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _P, _P, _F, _P]),
-    "sg_adam_step_guarded": (c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _L, _F, _P, _P]),
-    "sg_adam_step_dev_guarded": (c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _P, _P, _F, _P, _P]),
-    "sg_adam_step_dev_multi": (c_int, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "sg_clamp": (c_int, [_P, _L, _F, _F, _P]),
-    "sg_clamp_multi": (c_int, [_P, _P, _I, _F, _F, _P]),
-    "sg_voxel_prepare": (c_int, [_P, _P, _L, _F, _F, _P]),
-    "sg_gemm_nt_workspace_bytes": (_Z, [_I, _I, _L]),
-    "sg_gemm_nt": (c_int, [_P, _L, _P, _L, _P, _L, _I, _I, _L, _P, _Z, _P]),
-    "sg_gemm_nt_batched_workspace_bytes": (_Z, [_I, _I, _I, _L]),
-    "sg_gemm_nt_batched": (c_int, [_P, _P, _L, _P, _P, _L, _P, _P, _P, _I, _I, _I, _L, _P, _Z, _P]),
-    "sg_gemm_nt_batched_lnrelu": (c_int, [_P, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _P, _Z, _P]),
-    "sg_layernorm_fwd": (c_int, [_P, _L, _P, _L, _P, _P, _P, _L, _P, _P, _L, _I, _F, _I, _P]),
-    "sg_layernorm_bwd_workspace_bytes": (_Z, [_L, _I]),
-    "sg_layernorm_bwd": (c_int, [_P, _L, _P, _L, _P, _P, _L, _P, _L, _P, _P, _P, _L, _P, _P, _L, _I, _I, _P, _Z, _P]),
-    "sg_colsum_tall_workspace_bytes": (_Z, [_L, _L, _I]),
-    "sg_colsum_tall": (c_int, [_P, _P, _L, _L, _L, _I, _L, _P, _Z, _P]),
-    "sg_pointnet_packed_floats": (_Z, []),
-    "sg_pointnet_pack": (c_int, [_P, _P, _P]),
-    "sg_pointnet_select_workspace_bytes": (_Z, [_L, _L]),
-    "sg_pointnet_select": (c_int, [_P, _P, _P, _L, _L, _P, _P, _P, _Z, _P]),
-    "sg_segmax_workspace_bytes": (_Z, [_L, _L, _I]),
-    "sg_segmax_fwd": (c_int, [_P, _P, _P, _L, _L, _I, _P, _Z, _P]),
-    "sg_segmax_scatter": (c_int, [_P, _P, _P, _L, _L, _I, _P]),
-    "sg_segmax_gather": (c_int, [_P, _P, _P, _L, _L, _I, _P]),
-    "sg_scatter_rows_grouped": (c_int, [_P, _P, _P, _L, _I, _I, _P]),
-    "sg_rowdot": (c_int, [_P, _P, _P, _P, _L, _I, _I, _P]),
-    "sg_rowscale": (c_int, [_P, _P, _P, _L, _I, _I, _P]),
-    "sg_rowouter": (c_int, [_P, _P, _P, _L, _I, _I, _P]),
-    "sg_loss_workspace_bytes": (_Z, []),
-    "sg_loss_weighted_l1_fwd": (c_int, [_P, _P, _L, _F, _P, _P, _Z, _P]),
-    "sg_loss_weighted_l1_bwd": (c_int, [_P, _P, _P, _P, _L, _F, _P]),
-    "sg_loss_mean_split_fwd": (c_int, [_P, _L, _L, _F, _F, _P, _P, _P]),
-    "sg_loss_mean_split_bwd": (c_int, [_P, _P, _L, _L, _F, _F, _P]),
-    "sg_loss_bce_fwd": (c_int, [_P, _L, _F, _P, _P]),
-    "sg_loss_bce_bwd": (c_int, [_P, _P, _P, _L, _F, _P]),
-    "sg_loss_neg_mean_log_fwd": (c_int, [_P, _L, _P, _P]),
-    "sg_loss_neg_mean_log_bwd": (c_int, [_P, _P, _P, _L, _P]),
-    "sg_vae_reparam_fwd": (c_int, [_P, _P, _P, _P, _L, _P]),
-    "sg_vae_reparam_bwd": (c_int, [_P, _P, _P, _P, _L, _P]),
-    "sg_head_dot_fwd": (c_int, [_P, _P, _P, _P, _I, _L, _I, _F, _P]),
-    "sg_head_dot_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
-    "sg_conv3d_k4s2p1_wgrad_dy_image": (c_int, [_I, _I, _I, _I, _I, _I, _Z, _P, _P]),
-    "sg_act_bwd_rowsum_pack8": (c_int, [_P, _P, _P, _P, _P, _L, _I, _L, _I, _F, _P]),
-    "sg_conv3d_k4s2p1_wgrad_prepacked": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
-    "sg_loss_kld_fwd": (c_int, [_P, _P, _L, _P, _P, _Z, _P]),
-    "sg_loss_kld_bwd": (c_int, [_P, _P, _P, _P, _P, _L, _P]),
-    "sg_loss_meansq_fwd": (c_int, [_P, _P, _L, _I, _D, _P, _P, _Z, _P]),
-    "sg_loss_meansq_bwd": (c_int, [_P, _P, _P, _P, _L, _I, _D, _P]),
-    "sg_loss_deepsdf_fwd": (c_int, [_P, _P, _L, _P, _P, _L, _I, _D, _P, _P, _Z, _P]),
-    "sg_loss_deepsdf_bwd": (c_int, [_P, _P, _L, _P, _P, _L, _I, _D, _P, _P, _P, _P]),
-    "sg_loss_deepsdf_fused": (c_int, [_P, _P, _L, _P, _P, _L, _I, _D, _P, _P, _P, _P, _Z, _P, _P]),
-    "sg_count_sign_mismatch": (c_int, [_P, _P, _L, _P, _P, _Z, _P]),
-    "sg_gradient_penalty_fwd": (c_int, [_P, _L, _L, _F, _P, _P, _P]),
-    "sg_gradient_penalty_bwd": (c_int, [_P, _P, _P, _P, _L, _L, _F, _P]),
-    "sg_lerp_rows": (c_int, [_P, _P, _P, _P, _L, _L, _P]),
-    "sg_fade_blend": (c_int, [_P, _P, _P, _L, _I, _L, _F, _F, _P]),
-    "sg_channel0": (c_int, [_P, _P, _L, _I, _L, _F, _P]),
-    "sg_subsample2": (c_int, [_P, _P, _L, _I, _P]),
-    "sg_subsample2_adjoint": (c_int, [_P, _P, _L, _I, _P]),
-    "sg_act_bwd_dy": (c_int, [_P, _P, _P, _P, _L, _I, _P]),
-    "sg_scatter_max_workspace_bytes": (_Z, [_L, _I]),
-    "sg_scatter_max_fwd": (c_int, [_P, _P, _P, _P, _L, _L, _I, _P, _Z, _P]),
-    "sg_scatter_max_scatter": (c_int, [_P, _P, _P, _L, _L, _I, _P]),
-    "sg_scatter_max_gather": (c_int, [_P, _P, _P, _L, _L, _I, _P]),
-    "sg_mc_workspace_bytes": (_Z, [_L, _I, _I, _I, _I]),
-    "sg_mc_count": (c_int, [_P, _L, _I, _I, _I, _F, _I, _F, _P, _P, _P, _Z, _P]),
-    "sg_mc_emit": (c_int, [_P, _L, _I, _I, _I, _F, _I, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _L, _L, _P, _Z, _P]),
-    "sg_mesh_sample_workspace_bytes": (_Z, [_L, _L]),
-    "sg_mesh_sample": (c_int, [_P, _P, _P, _P, _L, _L, _P, _L, _P, _P, _P, _Z, _P]),
-    "sg_topo_label_workspace_bytes": (_Z, [_L, _L]),
-    "sg_topo_label": (c_int, [_P, _P, _P, _L, _L, _L, _P, _P, _P, _Z, _P]),
-    "sg_topo_keys": (c_int, [_P, _P, _P, _L, _L, _L, _P, _P, _L, _P, _P, _P]),
-    "sg_topo_stats_workspace_bytes": (_Z, [_L, _L]),
-    "sg_topo_stats": (c_int, [_P, _P, _P, _P, _L, _L, _L, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
-    "sg_topo_keep_workspace_bytes": (_Z, [_L, _L, _L]),
-    "sg_topo_keep_count": (c_int, [_P, _P, _P, _L, _L, _L, _P, _P, _L, _P, _P, _P, _P, _Z, _P]),
-    "sg_topo_keep_emit": (c_int, [_P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P, _L, _L, _P, _Z, _P]),
-    "sg_simplify_bounds": (c_int, [_P, _P, _L, _L, _P, _P, _P]),
-    "sg_simplify_keys": (c_int, [_P, _P, _L, _L, _P, _P, _P, _P, _P]),
-    "sg_simplify_count": (c_int, [_P, _P, _P, _L, _L, _L, _P, _P, _P]),
-    "sg_simplify_clusters_workspace_bytes": (_Z, [_L, _L]),
-    "sg_simplify_clusters": (c_int, [_P, _P, _P, _L, _L, _P, _P, _P, _P, _Z, _P]),
-    "sg_simplify_corners": (c_int, [_P, _P, _P, _L, _L, _L, _P, _P, _P]),
-    "sg_simplify_place": (c_int, [_P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P, _L, _P, _P, _I, _P, _P, _P]),
-    "sg_simplify_faces_workspace_bytes": (_Z, [_L, _L, _L]),
-    "sg_simplify_faces_count": (c_int, [_P, _P, _P, _L, _L, _L, _P, _P, _L, _P, _P, _P, _Z, _P]),
-    "sg_simplify_faces_emit": (c_int, [_P, _P, _P, _P, _P, _L, _L, _L, _P, _L, _P, _P, _P, _P, _L, _L, _P, _Z, _P]),
-    "sg_chamfer_matrix_workspace_bytes": (_Z, [_L, _L, _L, _L]),
-    "sg_chamfer_matrix": (c_int, [_P, _P, _L, _L, _L, _L, _P, _P, _P, _Z, _P]),
-    "sg_chamfer_nearest": (c_int, [_P, _P, _L, _L, _L, _P, _P, _P, _P, _P]),
-    "sg_occupancy_histogram": (c_int, [_P, _L, _L, _I, _P, _P]),
-    "sg_emd_match": (c_int, [_P, _P, _L, _L, _D, _P, _P, _P, _P, _P]),
-    "sg_emd_match_impl": (c_int, [_P, _P, _L, _L, _D, _P, _P, _P, _P, _I, _I, _P]),
-    "sg_emd_matrix_workspace_bytes": (_Z, [_L, _L, _L]),
-    "sg_emd_matrix": (c_int, [_P, _P, _L, _L, _L, _D, _I, _P, _P, _P, _Z, _P]),
-    "sg_meshsdf_distance_workspace_bytes": (_Z, [_L, _L, _L]),
-    "sg_meshsdf_distance": (c_int, [_P, _P, _L, _L, _P, _L, _P, _P, _P, _P, _Z, _P]),
-    "sg_meshsdf_distance_impl": (c_int, [_P, _P, _L, _L, _P, _L, _P, _P, _P, _P, _Z, _I, _P, _P]),
-    "sg_meshsdf_sign": (c_int, [_P, _L, _L, _P, _P, _I, _I, _F, _P, _P, _P, _P]),
-    "sg_tsne_affinities_workspace_bytes": (_Z, [_L]),
-    "sg_tsne_affinities": (c_int, [_P, _L, _L, _D, _D, _I, _P, _P, _P, _P, _Z, _P]),
-    "sg_tsne_gradient_workspace_bytes": (_Z, [_L]),
-    "sg_tsne_gradient": (c_int, [_P, _P, _L, _F, _P, _P, _P, _P, _Z, _P]),
-    "sg_tsne_update": (c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _P]),
-    "sg_tsne_step": (c_int, [_P, _P, _L, _F, _P, _P, _P, _F, _F, _F, _P, _P, _P, _Z, _P]),
-    "sg_raster_setup": (c_int, [_P, _P, _L, _L, _P, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P]),
-    "sg_raster_scan": (c_int, [_P, _L, _P, _P, _P, _P, _P]),
-    "sg_raster_fill": (c_int, [_P, _P, _P, _L, _L, _I, _I, _P, _P, _P, _L, _P]),
-    "sg_raster_visibility": (c_int, [_P, _P, _L, _I, _I, _P, _P, _L, _P, _L, _P, _P, _I, _P]),
-    "sg_raster_shade": (c_int, [_P, _P, _L, _P, _P, _P, _P, _I, _P, _P, _L, _I, _I, _P, _P]),
-    "sg_raster_resolve": (c_int, [_P, _L, _I, _I, _I, _P, _P]),
-    "sg_raymarch_rays": (c_int, [_P, _I, _L, _D, _P, _P, _P, _P, _P, _P]),
-    "sg_raymarch_steps": (c_int, [_P, _P, _P, _P, _P, _L, _P, _P, _L, _P, _P, _L, _L, _L, _L, _I, _F, _F, _F, _F, _F, _I, _P, _P]),
-    "sg_raymarch_finish": (c_int, [_P, _P, _L, _P, _P, _L, _L, _P]),
-    "sg_raymarch_workspace_bytes": (_Z, [_L, _L]),
-    "sg_raymarch_classify": (c_int, [_P, _P, _P, _L, _L, _I, _F, _P, _P, _P, _P, _Z, _P]),
-    "sg_raymarch_emit": (c_int, [_P, _P, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
-    "sg_raymarch_shade": (c_int, [_P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P]),
-    "sg_brick_compact_workspace_bytes": (_Z, [_L, _I, _I]),
-    "sg_brick_points": (c_int, [_P, _L, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "sg_brick_seed": (c_int, [_P, _P, _L, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P]),
-    "sg_brick_compact": (c_int, [_P, _P, _L, _I, _I, _P, _P, _P, _Z, _P]),
-    "sg_brick_scatter": (c_int, [_P, _P, _L, _P, _L, _I, _I, _P, _P]),
-    "sg_brick_grow": (c_int, [_P, _L, _P, _P, _P, _L, _I, _I, _F, _P, _P]),
-}
+# name -> (restype, argtypes) of every symbol include/shapegan_hip.h declares, read from the header itself (abi.py);
+# COMM_SIGNATURES: the entry points of libshapegan_comm.so
+SIGNATURES = {d.name: abi.ctypes_signature(d) for d in abi.DECLARATIONS if not abi.is_comm(d.name)}
+COMM_SIGNATURES = {d.name: abi.ctypes_signature(d) for d in abi.DECLARATIONS if abi.is_comm(d.name)}
 
 # libshapegan_comm.so (RCCL gradient exchange; loaded only by data-parallel runs that ask for it)
 COMM_PATH = os.path.join(_HERE, "libshapegan_comm.so")
-COMM_SIGNATURES = {
-    "sg_comm_last_error": (c_char_p, []),
-    "sg_comm_bind": (c_int, [c_char_p]),
-    "sg_comm_versions": (c_int, [_P, _P]),
-    "sg_allreduce_unique_id_bytes": (_Z, []),
-    "sg_allreduce_unique_id": (c_int, [_P, _Z]),
-    "sg_allreduce_init": (c_int, [_P, _I, _I, _P, _Z, _I]),
-    "sg_allreduce_info": (c_int, [_P, _P, _P, _P, _P]),
-    "sg_allreduce_launch": (c_int, [_P, _P, _L, _P]),
-    "sg_allreduce_wait": (c_int, [_P, _P]),
-    "sg_allreduce_destroy": (c_int, [_P]),
-}
 _comm = None
 
 
@@ -289,13 +84,7 @@ def check_comm(rc, what=""):
         raise RuntimeError("shapegan_comm %s failed (%d): %s" % (what, rc, msg.decode() if msg else "?"))
 
 
-# Entry points WITHOUT a twin: size queries and layout helpers are host code of libshapegan_hip.so (callable without a GPU; the
-# twin keeps its opaque buffers within those sizes), the *_impl variants force a particular HIP kernel (tests / tuning).
-NO_TWIN = {n for n in SIGNATURES if n.endswith("_workspace_bytes") or n.endswith("_workspace_bytes_for") or n.endswith("_impl")} | {
-    "sg_sdfgen_acts_floats", "sg_sdfgen_packed_norm_offset", "sg_sdfgen_bwd_blocks", "sg_pointnet_packed_floats",
-    "sg_abi_version", "sg_last_error", "sg_sdfnet_packed_floats", "sg_sdfnet_acts_floats", "sg_sdfnet_bwd_blocks", "sg_sdfnet_bwd_tile_start", "sg_sdf_batch_sort_max_shapes",
-    "sg_conv3d_k4s2p1_wgrad_act_eligible", "sg_convT3d_k4s2p1_to1_pre_eligible", "sg_conv3d_k4s2p1_wgrad_dy_image",
-    "sg_conv3d_k4s2p1_image_layout"}
+NO_TWIN = abi.NO_TWIN       # entry points without a twin
 CPU_PATH = os.path.join(_HERE, "libshapegan_cpu.so")
 
 _hip = None
@@ -315,7 +104,7 @@ def _load_hip():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
-        if lib.sg_abi_version() != 8:
+        if lib.sg_abi_version() != abi.ABI_VERSION:
             raise RuntimeError("libshapegan_hip.so ABI version mismatch")
         _hip = lib
     return _hip

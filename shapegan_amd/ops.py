@@ -1000,7 +1000,7 @@ class _PackCache(object):
         return None
 
 
-_PART_ROW = 14 * _H + 32      # SG_SDFNET_PARTIAL_ROW: floats per tile of the backward's partial sums
+_PART_ROW = L.abi.DEFINES["SG_SDFNET_PARTIAL_ROW"]      # 14 * _H + 32 floats per tile of the backward's partial sums
 
 _side_streams = {}
 _OVERLAP_MIN_POINTS = 65536      # side-stream overlap of short launches only in GPU-bound steps
@@ -1304,8 +1304,8 @@ class SDFNetShapes(Function):
 
 
 # ---- latent codes of unseen shapes: loss and latent-only gradient with the weights frozen (csrc/latent_fit.hip) -------------------
-_LATENT_TILE = 32             # SG_SDFNET_LATENT_TILE
-_LATENT_ROW = 2 * _H + 1      # SG_SDFNET_LATENT_PARTIAL_ROW
+_LATENT_TILE = L.abi.DEFINES["SG_SDFNET_LATENT_TILE"]
+_LATENT_ROW = L.abi.DEFINES["SG_SDFNET_LATENT_PARTIAL_ROW"]      # 2 * _H + 1
 _LATENT_MAX_SHAPES = 6144     # what sg_sdfnet_shape_bias_bwd takes in one call; more shapes go in chunks (shapes are independent)
 
 
@@ -1418,10 +1418,11 @@ class LatentFit(object):
 
 
 # ---- points onto a level set: value, point gradient and Newton steps with the weights frozen (csrc/sdfnet_project.hip) -------------
-_PROJECT_TILE = 32                 # SG_SDFNET_PROJECT_TILE
+_PROJECT_TILE = L.abi.DEFINES["SG_SDFNET_PROJECT_TILE"]
 _PROJECT_MAX_SHAPES = 6144         # shapes per launch, the chunks of LatentFit (_shape_chunks)
 _PROJECT_MAX_ITERATIONS = 64
-PROJECT_RULES = {"newton": 0, "unit": 1}      # SG_PROJECT_RULE_*: d / |g|^2, or the reference's d / |g| (model/sdf_net.py:146)
+_RULES = L.abi.core_defines("project_core.h")
+PROJECT_RULES = {r: _RULES["SG_PROJECT_RULE_" + r.upper()] for r in ("newton", "unit")}      # d / |g|^2, or the reference's d / |g| (model/sdf_net.py:146)
 
 
 def check_point_segments(points, nshapes, segment_offsets):
@@ -1578,7 +1579,7 @@ class _GenPackCache(object):
         return entry[1]
 
 
-_GEN_PART_ROW = _PART_ROW + 14 * _H      # SG_SDFGEN_PARTIAL_ROW
+_GEN_PART_ROW = L.abi.DEFINES["SG_SDFGEN_PARTIAL_ROW"]      # _PART_ROW + 14 * _H
 
 
 class SDFGenFused(Function):
@@ -2633,7 +2634,7 @@ def scatter_max(x, batch, dim_size=None):
 # --------------------------------------------------------------------------------------------------------------
 # K17: exact t-SNE (csrc/tsne.hip; shapegan_amd/traversal.py)
 # --------------------------------------------------------------------------------------------------------------
-TSNE_MAX_POINTS = 65536      # SG_TSNE_MAX_POINTS
+TSNE_MAX_POINTS = L.abi.DEFINES["SG_TSNE_MAX_POINTS"]
 
 
 def _tsne_state(name, t, N):

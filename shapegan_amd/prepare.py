@@ -26,8 +26,8 @@ from . import lib as L
 from .lib import check, ptr, stream
 from .rendering import raster
 
-MAX_SCANS = 64                # SG_MESHSDF_MAX_SCANS
-CHUNK = 256                   # SG_MESHSDF_CHUNK: triangle records per LDS stage of the distance kernel
+MAX_SCANS = L.abi.DEFINES["SG_MESHSDF_MAX_SCANS"]
+CHUNK = L.abi.DEFINES["SG_MESHSDF_CHUNK"]      # triangle records per LDS stage of the distance kernel
 
 
 class BadMeshException(Exception):

@@ -31,7 +31,7 @@ from . import lib as L
 from .lib import check, f32c, ptr, stream
 from .mesh import MeshBatch
 
-MAX_CELLS = 16384       # SG_SIMPLIFY_MAX_CELLS of csrc/simplify_core.h
+MAX_CELLS = L.abi.core_defines("simplify_core.h")["SG_SIMPLIFY_MAX_CELLS"]
 MAX_SHAPES = 1 << 20
 PLACEMENTS = {"quadric": 0, "mean": 1}
 _ONE = np.float32(1.0)

@@ -21,7 +21,7 @@ from . import lib as L
 from .lib import check, f32c, ptr, stream
 from .mesh import MeshBatch
 
-TILE = 256      # SG_TOPO_TILE of csrc/topology_core.h
+TILE = L.abi.core_defines("topology_core.h")["SG_TOPO_TILE"]
 DEFAULT_RULE = {"min_area_fraction": 0.01}
 _RULE_KEYS = ("largest", "min_area_fraction", "min_triangles", "drop_cavities")
 
