@@ -1144,6 +1144,63 @@ int sg_brick_scatter(const float* values, const int* bricks, long M, const unsig
 int sg_brick_grow(const int* bricks, long M, const float* grid, const int* state, const float* fill, long S, int R, int B, float level,
                   int* flag, hipStream_t stream);
 
+/* ---- K19: signed distances from oriented point clouds: k nearest neighbours, normals, the normal-vote sign -----------------------
+ * reference: mesh_to_sdf's sign_method = 'normal' (the package's default; demo_training.py:16, create_plot.py:636, and what
+ *            prepare_shapenet_dataset.py:33,129 selects with USE_DEPTH_BUFFER = False): the distance to the nearest sample of an
+ *            oriented cloud, the sign from a vote of the normals of the sample_count = 11 nearest samples.  K16 is the 'depth' method.
+ * Input: S ragged clouds, points [N][3] fp32 with cloud_offsets [S+1] int64, and S ragged query sets, queries [M][3] fp32 with
+ * query_offsets [S+1] int64 (device pointers; any run may be empty; a pointer whose array is empty may be NULL).  Every index in a
+ * result is LOCAL to its shape's cloud.  1 <= S <= 65535; offsets start at 0, do not decrease and end at N / M; every run holds at
+ * most 2^26 points (K13's limit); anything else is SG_ERR_ARG, on the GPU and in the twin alike.  The offsets decide every bound of
+ * the walk, so the entry points read them back before the launch (one small copy and a wait on `stream`: the calls cannot be
+ * captured in a graph).  No workspace: the only stores are to the result arrays, every element of which is written.
+ *
+ * sg_cloud_knn: idx [M][K] int32, d2 [M][K] fp32, 1 <= K <= SG_CLOUD_MAX_K.  For every query the K points of its shape's cloud that
+ *   are smallest in the order (d2, index), ascending; d2 = K13's value of the pair (csrc/pointcloud_core.h), bit for bit.  Slots
+ *   beyond the number of neighbours hold idx = -1, d2 = +inf.  A pair whose d2 is NaN or +inf is never a neighbour (non-finite
+ *   coordinates: no fault, every idx in [-1, size)).  exclude_self != 0: the query runs must EQUAL the cloud runs (else SG_ERR_ARG),
+ *   query i of a shape is its cloud point i, and the search skips the point with that INDEX — a duplicate of it at another index
+ *   is a neighbour at distance 0.  The result is defined by the order alone: the same bits on the GPU, in the twin, under any tiling
+ *   and wherever the shape stands in a batch.
+ *
+ * sg_cloud_normals: normals [N][3], variation [N] fp32 from idx [N][K] of a self-query with exclude_self.  All arithmetic is fp32,
+ *   stated once in csrc/cloud_core.h with explicit fmaf (contraction off).  The samples of a point are itself and then its valid
+ *   neighbours (0 <= idx < size) in slot order, n of them, each taken RELATIVE TO THE POINT: q_j = p_j - p_self (q_0 = 0), so the
+ *   result does not change under a translation that is exact in fp32.  Centroid c = (sum of the q_j in sample order) / (float) n;
+ *   with e_j = q_j - c the six sums xx, xy, xz, yy, yz, zz of the products, s = fmaf(e_a, e_b, s) in sample order.  The symmetric 3x3
+ *   is diagonalised by SG_CLOUD_JACOBI_SWEEPS cyclic Jacobi sweeps over the pairs (0,1), (0,2), (1,2) — a fixed count, no test for
+ *   convergence; a pair whose off-diagonal element is 0 is left alone:
+ *     theta = (a_qq - a_pp) / (2 a_pq);  t = copysign(1, theta) / (|theta| + sqrtf(fmaf(theta, theta, 1)));  c = 1 / sqrtf(fmaf(t, t, 1));
+ *     s = t c;  a_pp -= t a_pq;  a_qq += t a_pq;  a_pq = 0;  (x_p, x_q) <- (fmaf(c, x_p, -(s x_q)), fmaf(s, x_p, c x_q)) for the remaining
+ *     row r of a and for the three rows of the eigenvector matrix (identity at the start).
+ *   lambda = the diagonal; lambda_0 <= lambda_1 <= lambda_2.  normal = the column of the smallest (the LOWEST column on a tie),
+ *   divided by its length sqrtf(fmaf(z, z, fmaf(y, y, x x)));  variation = lambda_0 / ((lambda_0 + lambda_1) + lambda_2).
+ *   Orientation: view (x, y, z, w) fp32, [S][4], or [N][4] when view_per_point != 0: e = (x, y, z) - w p_self (a product, a
+ *   difference), the normal is negated when fmaf(n_z, e_z, fmaf(n_y, e_y, n_x e_x)) < 0.  w = 1: a scanner position; w = 0: the
+ *   direction toward an orthographic scanner (the d of K16's scans).  view = NULL ("unoriented"): the component of largest magnitude
+ *   (the lowest axis on a tie) is made positive.  Degenerate: n < 3, or not lambda_1 > 2^-20 lambda_2 (a line, a point, NaN):
+ *   normal = (0, 0, 0), variation = -1.  One lane per point; K as in sg_cloud_knn.
+ *
+ * sg_cloud_sdf: mesh_to_sdf's get_sdf(use_depth_buffer = False, sample_count = K) in one launch: sdf [M] fp32, nearest [M] int32
+ *   (may be NULL).  The walk of sg_cloud_knn without exclude_self; for each valid neighbour j, in slot order, with its normal n
+ *   (normals [N][3]): d = q - p_j, t_j = fmaf(d_z, n_z, fmaf(d_y, n_y, d_x n_x)); inside = 2 #{t_j < 0} > n_valid (a tie is not
+ *   inside; a normal (0, 0, 0) gives t_j = 0, a vote for outside); sdf = sqrtf(d2[0]), negated when inside; nearest = idx[0].  No
+ *   neighbour (an empty cloud, nothing finite): sdf = +inf, nearest = -1.  The same bits on the GPU and in the twin.
+ *
+ * Kernels (csrc/cloud.hip): one workgroup of SG_CLOUD_QUERY_TILE queries of ONE shape walks that shape's cloud, staged through LDS
+ * in chunks of SG_CLOUD_STAGE points; every lane keeps its sorted list in registers (forms for 8, 16 and 32 entries: the smallest
+ * that holds K runs, the first K entries are stored). */
+#define SG_CLOUD_MAX_K 32
+#define SG_CLOUD_QUERY_TILE 256
+#define SG_CLOUD_STAGE 1024
+#define SG_CLOUD_MAX_POINTS 67108864 /* 2^26 per run */
+int sg_cloud_knn(const float* points, const int64_t* cloud_offsets, const float* queries, const int64_t* query_offsets, long S, long N,
+                 long M, int K, int exclude_self, int* idx, float* d2, hipStream_t stream);
+int sg_cloud_normals(const float* points, const int64_t* cloud_offsets, long S, long N, const int* idx, int K, const float* view,
+                     int view_per_point, float* normals, float* variation, hipStream_t stream);
+int sg_cloud_sdf(const float* points, const float* normals, const int64_t* cloud_offsets, const float* queries,
+                 const int64_t* query_offsets, long S, long N, long M, int K, float* sdf, int* nearest, hipStream_t stream);
+
 /* ---- data-parallel gradient exchange: libshapegan_comm.so ----------------------------------------------
  * reference: nn.DataParallel's gradient reduce-add, train_hybrid_progressive_gan.py:62-68.  One process per GPU; one
  * ncclAllReduce(sum, fp32) of a slice of the flat gradient buffer per call, on the communicator's own stream, ordered after

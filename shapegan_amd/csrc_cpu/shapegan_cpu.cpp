@@ -3222,3 +3222,96 @@ int sg_sdfnet_project_cpu(const float* points, const int64_t* seg_off, long nsha
 
 }  // extern "C"
 #pragma GCC pop_options
+
+// ---- K19: signed distances from oriented point clouds (header: sg_cloud_*; csrc/cloud.hip) -------------------------------------------
+// By brute force: every query against every point of its shape's cloud, the K best kept in a small array in the order (d2, index) of
+// csrc/cloud_core.h; the normal of a neighbourhood and the vote of a normal are that file's, which the HIP kernels include.
+#pragma GCC push_options
+#pragma GCC optimize("fp-contract=off")
+#include "../csrc/cloud_core.h"
+
+// false when an offset table is not S runs of at most 2^26 points from 0 to total
+static bool cloud_runs_ok(const int64_t* off, long S, long total) {
+    if (off[0] != 0 || off[S] != total) return false;
+    for (long s = 0; s < S; ++s)
+        if (off[s + 1] < off[s] || off[s + 1] - off[s] > SG_CLOUD_MAX_POINTS) return false;
+    return true;
+}
+
+// the first K of the cloud's points in the order (d2, index) as seen from q, `self` left out; the unused slots hold (-1, +inf)
+static void cloud_list(const float* cloud, long P, const float* q, long self, int K, int* li, float* ld) {
+    for (int j = 0; j < K; ++j) li[j] = -1, ld[j] = INFINITY;
+    for (long p = 0; p < P; ++p) {
+        if (p == self) continue;
+        const float d = sg_pc_d2(q[0], q[1], q[2], cloud[p * 3], cloud[p * 3 + 1], cloud[p * 3 + 2]);
+        if (!(d < INFINITY)) continue;      // NaN and +inf are never neighbours
+        if (li[K - 1] >= 0 && !sg_cloud_before(d, (int)p, ld[K - 1], li[K - 1])) continue;
+        int j = K - 1;
+        for (; j > 0 && (li[j - 1] < 0 || sg_cloud_before(d, (int)p, ld[j - 1], li[j - 1])); --j) li[j] = li[j - 1], ld[j] = ld[j - 1];
+        li[j] = (int)p, ld[j] = d;
+    }
+}
+
+extern "C" {
+
+int sg_cloud_knn_cpu(const float* points, const int64_t* cloud_offsets, const float* queries, const int64_t* query_offsets, long S, long N,
+                     long M, int K, int exclude_self, int* idx, float* d2, hipStream_t_) {
+    CPU_CHECK(S >= 1 && S <= 65535 && N >= 0 && M >= 0 && K >= 1 && K <= SG_CLOUD_MAX_K && cloud_offsets && query_offsets);
+    CPU_CHECK((points || N == 0) && (queries || M == 0) && ((idx && d2) || M == 0));
+    CPU_CHECK(cloud_runs_ok(cloud_offsets, S, N) && cloud_runs_ok(query_offsets, S, M));
+    CPU_CHECK(!exclude_self || std::equal(cloud_offsets, cloud_offsets + S + 1, query_offsets));
+    for (long s = 0; s < S; ++s) {
+        const long c0 = cloud_offsets[s], P = cloud_offsets[s + 1] - c0, q0 = query_offsets[s], Q = query_offsets[s + 1] - q0;
+#pragma omp parallel for schedule(static)
+        for (long i = 0; i < Q; ++i)
+            cloud_list(points + c0 * 3, P, queries + (q0 + i) * 3, exclude_self ? i : -1, K, idx + (q0 + i) * K, d2 + (q0 + i) * K);
+    }
+    return SG_OK;
+}
+
+int sg_cloud_normals_cpu(const float* points, const int64_t* cloud_offsets, long S, long N, const int* idx, int K, const float* view,
+                         int view_per_point, float* normals, float* variation, hipStream_t_) {
+    CPU_CHECK(S >= 1 && S <= 65535 && N >= 0 && K >= 1 && K <= SG_CLOUD_MAX_K && cloud_offsets);
+    CPU_CHECK((points && idx && normals && variation) || N == 0);
+    CPU_CHECK(cloud_runs_ok(cloud_offsets, S, N));
+    for (long s = 0; s < S; ++s) {
+        const long c0 = cloud_offsets[s], P = cloud_offsets[s + 1] - c0;
+#pragma omp parallel for schedule(static)
+        for (long i = 0; i < P; ++i)
+            sg_cloud_normal(points + c0 * 3, P, i, idx + (c0 + i) * K, K, view ? view + (view_per_point ? c0 + i : s) * 4 : nullptr,
+                            normals + (c0 + i) * 3, variation + c0 + i);
+    }
+    return SG_OK;
+}
+
+int sg_cloud_sdf_cpu(const float* points, const float* normals, const int64_t* cloud_offsets, const float* queries,
+                     const int64_t* query_offsets, long S, long N, long M, int K, float* sdf, int* nearest, hipStream_t_) {
+    CPU_CHECK(S >= 1 && S <= 65535 && N >= 0 && M >= 0 && K >= 1 && K <= SG_CLOUD_MAX_K && cloud_offsets && query_offsets);
+    CPU_CHECK(((points && normals) || N == 0) && ((queries && sdf) || M == 0));
+    CPU_CHECK(cloud_runs_ok(cloud_offsets, S, N) && cloud_runs_ok(query_offsets, S, M));
+    for (long s = 0; s < S; ++s) {
+        const long c0 = cloud_offsets[s], P = cloud_offsets[s + 1] - c0, q0 = query_offsets[s], Q = query_offsets[s + 1] - q0;
+        const float* cloud = points + c0 * 3;
+        const float* cn = normals + c0 * 3;
+#pragma omp parallel for schedule(static)
+        for (long i = 0; i < Q; ++i) {
+            const float* q = queries + (q0 + i) * 3;
+            int li[SG_CLOUD_MAX_K];
+            float ld[SG_CLOUD_MAX_K];
+            cloud_list(cloud, P, q, -1, K, li, ld);
+            int valid = 0, negative = 0;
+            for (int j = 0; j < K; ++j)
+                if (li[j] >= 0) {
+                    const long g = (long)li[j] * 3;
+                    ++valid;
+                    negative += sg_cloud_vote(q[0], q[1], q[2], cloud[g], cloud[g + 1], cloud[g + 2], cn[g], cn[g + 1], cn[g + 2]) < 0.f ? 1 : 0;
+                }
+            sdf[q0 + i] = sg_cloud_signed(ld[0], valid, negative);
+            if (nearest) nearest[q0 + i] = li[0];
+        }
+    }
+    return SG_OK;
+}
+
+}  // extern "C"
+#pragma GCC pop_options

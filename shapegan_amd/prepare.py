@@ -6,7 +6,8 @@ Reference: prepare_shapenet_dataset.py:69-131 and prepare_data.py, which sit on 
 Here the same files come from three native pieces: K14's rasteriser draws the depth maps of K orthographic scans, sg_meshsdf_distance
 finds the exact distance from every query point to the triangles, sg_meshsdf_sign calls a point outside when a scan sees it
 (mesh_to_sdf's "depth" method, the one USE_DEPTH_BUFFER = True selects).  Two deliberate differences from mesh_to_sdf: the
-magnitude is the distance to the triangles, not to a scanned point cloud, and the scans are orthographic, not perspective.
+magnitude is the distance to the triangles, not to a scanned point cloud, and the scans are orthographic, not perspective.  mesh_to_sdf's other method, 'normal' (USE_DEPTH_BUFFER = False), needs no triangles:
+shapegan_amd/cloudsdf.py has it for point clouds, and CloudSDF.from_scans for the scan points of a SurfaceScans.
 
 GPU tensors run the HIP kernels, CPU tensors the twin.  Random numbers are drawn with a CPU `torch.Generator` and moved to the device:
 one seed gives the same query points on either.  File layout, dtypes and the bad-mesh markers are the reference's, so

@@ -10,6 +10,10 @@ training codes).  fit_latent_codes runs it for a batch of shapes at once — eve
 csrc/latent_fit.hip (SDFNet.latent_loss_and_grad), with Adam through sg_adam_step; reconstruct_meshes turns codes into a MeshBatch.
 
     python -m shapegan_amd.reconstruct --net models/sdf_net.to --models DIR --out codes.to [--meshes OUTDIR] [--chamfer]
+    python -m shapegan_amd.reconstruct --net models/sdf_net.to --clouds DIR --out codes.to       # point clouds: .npy, .xyz, .ply
+    python -m shapegan_amd.reconstruct --net models/sdf_net.to --models DIR --partial 5 --out codes.to --chamfer     # shape completion
+
+--clouds and --partial fit to the SDF of an oriented point cloud (shapegan_amd.cloudsdf, mesh_to_sdf's 'normal' sign) instead of a mesh's.
 """
 import argparse
 import os
@@ -115,7 +119,16 @@ def main(argv=None):
     from .model.sdf_net import SDFNet
     ap = argparse.ArgumentParser(description="Fit SDFNet latent codes to the meshes of a directory.")
     ap.add_argument("--net", required=True, help="state_dict of a trained SDFNet (models/sdf_net.to)")
-    ap.add_argument("--models", required=True, help="directory searched for .obj files")
+    ap.add_argument("--models", default=None, help="directory searched for .obj files")
+    ap.add_argument("--clouds", default=None, help="directory searched for point clouds (.npy [P,3] or [P,6], .xyz, .ply) instead of --models")
+    ap.add_argument("--partial", type=int, default=None, metavar="V",
+                    help="with --models: fit to the cloud that the first V scans see instead of the mesh (shape completion); the cloud is a random "
+                         "subset of at most --points of the texels those scans drew (seeded by --seed)")
+    ap.add_argument("--sample-count", type=int, default=11, help="cloud fits: the nearest samples whose normals vote on the sign")
+    ap.add_argument("--k-normals", type=int, default=16, help="cloud fits: the neighbours a normal is estimated from")
+    ap.add_argument("--view", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
+                    help="--clouds without normals: the scanner position the estimated normals face, in the coordinates of the cloud FILES (a sensor at "
+                         "its own origin: 0 0 0); the normals are estimated before the clouds are centred and scaled to the unit sphere")
     ap.add_argument("--out", required=True, help="where the codes [S,L] are torch.save'd")
     ap.add_argument("--meshes", default=None, help="directory for one reconstructed .obj per model")
     ap.add_argument("--chamfer", action="store_true", help="print the Chamfer distance between input and reconstruction")
@@ -137,22 +150,46 @@ def main(argv=None):
     ap.add_argument("--chamfer-points", type=int, default=2048)
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
+    if (args.models is None) == (args.clouds is None):
+        ap.error("exactly one of --models and --clouds is required")
+    if args.partial is not None and (args.models is None or args.partial < 1):
+        ap.error("--partial V goes with --models and needs V >= 1")
+    if args.clouds is not None and args.chamfer:
+        ap.error("--chamfer scores against the mesh of --models")
 
     dev = torch.device(args.device)
     state = torch.load(args.net, map_location="cpu")
     net = SDFNet(latent_code_size=state["layers1.0.weight"].shape[1] - 3, device=args.device)
     net.load_state_dict(state)
     L.bump_param_epoch()
-    files = prepare.get_model_files(args.models)
-    if not files:
-        raise SystemExit("no .obj files under %s" % args.models)
-    meshes = []
-    for path in files:
-        v, f = prepare.load_obj(path)
-        meshes.append((prepare.scale_to_unit_sphere(v), f))
     g = torch.Generator().manual_seed(args.seed)
-    scans = prepare.SurfaceScans(meshes, 1.0, args.scan_count, args.scan_resolution, device=dev)
-    points, sdf, ok = scans.sample_sdf_near_surface(args.points, generator=g)
+    if args.clouds is not None:
+        from . import cloudsdf
+        files = cloudsdf.get_cloud_files(args.clouds)
+        if not files:
+            raise SystemExit("no point clouds under %s" % args.clouds)
+        meshes = None
+        try:
+            source = cloudsdf.CloudSDF.from_files(files, view=args.view, k_normals=args.k_normals, device=dev)
+        except ValueError as e:
+            raise SystemExit("%s: %s" % (args.clouds, e))
+        points, sdf, ok = source.sample_sdf_near_surface(args.points, generator=g, sample_count=args.sample_count)
+    else:
+        files = prepare.get_model_files(args.models)
+        if not files:
+            raise SystemExit("no .obj files under %s" % args.models)
+        meshes = []
+        for path in files:
+            v, f = prepare.load_obj(path)
+            meshes.append((prepare.scale_to_unit_sphere(v), f))
+        scans = prepare.SurfaceScans(meshes, 1.0, args.scan_count, args.scan_resolution, device=dev)
+        if args.partial is not None:
+            from . import cloudsdf
+            source = cloudsdf.CloudSDF.from_scans(scans, keep=range(min(args.partial, args.scan_count)), k_normals=args.k_normals,
+                                                  max_points=args.points, generator=g)
+            points, sdf, ok = source.sample_sdf_near_surface(args.points, generator=g, sample_count=args.sample_count)
+        else:
+            points, sdf, ok = scans.sample_sdf_near_surface(args.points, generator=g)
     codes, loss = fit_latent_codes(net, points, sdf, iterations=args.iterations, lr=args.lr, sigma=args.sigma,
                                    points_per_step=args.points_per_step or None, seed=args.seed)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
@@ -175,7 +212,7 @@ def main(argv=None):
         d = evaluation.chamfer_distance(truth, recon).cpu()
         chamfer = [None if int(empty[i]) else float(d[i]) for i in range(len(files))]
     for i, path in enumerate(files):
-        line = "%s: loss %.6f%s" % (path, float(loss[i]), "" if bool(ok[i]) else " (bad mesh: too little inside)")
+        line = "%s: loss %.6f%s" % (path, float(loss[i]), "" if bool(ok[i]) else " (bad %s: too little inside)" % ("mesh" if args.clouds is None and args.partial is None else "cloud"))
         if args.chamfer:
             line += ", chamfer %s" % ("n/a (empty reconstruction)" if chamfer[i] is None else "%.6f" % chamfer[i])
         print(line)
