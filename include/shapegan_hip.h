@@ -164,6 +164,23 @@ size_t sg_gemm_workspace_bytes(int M, int N);
 int sg_gemm(const float* A, long sai, long sak, const float* B, long sbk, long sbj, float* C, long sci, long scj,
             const float* bias_i, const float* bias_j, int bias_j_shift, int M, int N, int K, int act, float slope,
             void* workspace, size_t workspace_bytes, hipStream_t stream);
+/* Which kernel sg_gemm launches for a call, and how: the value sg_gemm itself launches from (host code only, no GPU needed;
+ * additions to ABI 8, backward compatible).  A, B, workspace: the pointers of the call (only their alignment / being null is read).
+ * plan[0..7] = { kind (SG_GEMM_KIND_*), tm, tn (the 16-k skeleton's 32 x 32 MFMA tiles per wave: a workgroup tile of 64 tm x 64 tn;
+ * 0 for the other kinds), nsplit (partial images in the workspace; 1: no K split), kchunk (k range of a split), finalize
+ * (SG_GEMM_FINALIZE_*), grid (workgroups of the product kernel), layout (2 * (A is k-major) + (B is k-major)) }. */
+#define SG_GEMM_KIND_SKELETON 0
+#define SG_GEMM_KIND_GEMM128 1
+#define SG_GEMM_KIND_GEMM128_SPLIT 2
+#define SG_GEMM_KIND_PERSISTENT 3
+#define SG_GEMM_FINALIZE_NONE 0
+#define SG_GEMM_FINALIZE_FLAT 1
+#define SG_GEMM_FINALIZE_DEEP 2
+int sg_gemm_plan(const void* A, long sai, long sak, const void* B, long sbk, long sbj, long sci, long scj, int has_bias_i, int M, int N,
+                 int K, const void* workspace, size_t workspace_bytes, long* plan);
+/* The same for sg_gemm_nt (batch = 1) and sg_gemm_nt_batched / _lnrelu: plan[0..4] = { direct (1: one launch straight into C, no
+ * workspace), nsplit, kchunk, grid, workspace bytes the call insists on }. */
+int sg_gemm_nt_plan(int batch, int M, int N, long K, long* plan);
 /* C[M,N] = A[M,K] B[N,K]^T, K contiguous in both operands and K >> M, N: the SDFNet weight gradients dW_l = dZ_l H_{l-1}^T over
  * the points of a batch (autograd of model/sdf_net.py:56-61).  Deterministic split-K; rows of C have stride ldc. */
 size_t sg_gemm_nt_workspace_bytes(int M, int N, long K);

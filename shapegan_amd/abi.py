@@ -139,4 +139,4 @@ NO_TWIN = {d.name for d in DECLARATIONS if not is_comm(d.name) and (d.name.endsw
     "sg_sdfgen_acts_floats", "sg_sdfgen_packed_norm_offset", "sg_sdfgen_bwd_blocks", "sg_pointnet_packed_floats",
     "sg_abi_version", "sg_last_error", "sg_sdfnet_packed_floats", "sg_sdfnet_acts_floats", "sg_sdfnet_bwd_blocks", "sg_sdfnet_bwd_tile_start", "sg_sdf_batch_sort_max_shapes",
     "sg_conv3d_k4s2p1_wgrad_act_eligible", "sg_convT3d_k4s2p1_to1_pre_eligible", "sg_conv3d_k4s2p1_wgrad_dy_image",
-    "sg_conv3d_k4s2p1_image_layout"}
+    "sg_conv3d_k4s2p1_image_layout", "sg_gemm_plan", "sg_gemm_nt_plan"}

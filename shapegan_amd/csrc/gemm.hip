@@ -387,14 +387,27 @@ __global__ void __launch_bounds__(256) gemm_nt_finalize_kernel(const float* __re
     }
 }
 
-static void gemm_nt_plan(int M, int N, long K, int& nsplit, long& kchunk, int batch = 1) {
+// Everything gemm_nt_launch decides, as a pure function of the shape (host code: sg_gemm_nt_plan reports it, the launcher reads it)
+struct GemmNtPlan {
+    int nsplit;
+    long kchunk;
+    bool direct;      // one launch straight into C: no partials, no finalize, no workspace
+    long grid;        // workgroups of gemm_nt_bigk_kernel
+    size_t ws_bytes;  // partial images the launch needs (0 when direct)
+};
+static GemmNtPlan gemm_nt_plan(int M, int N, long K, int batch = 1) {
     const long tiles = (long)sg_cdiv(M, 128) * sg_cdiv(N, 128) * batch;
     long s = 512 / tiles > 0 ? 512 / tiles : 1;   // at most 512 workgroups: one round at 2 per CU, no straggler round
     const long maxs = K / (8 * kNtKC) > 0 ? K / (8 * kNtKC) : 1;   // >= 8 stages per workgroup
     if (s > maxs) s = maxs;
     if (s > 256) s = 256;
-    kchunk = ((K + s - 1) / s + kNtKC - 1) / kNtKC * kNtKC;
-    nsplit = (int)((K + kchunk - 1) / kchunk);
+    GemmNtPlan p;
+    p.kchunk = ((K + s - 1) / s + kNtKC - 1) / kNtKC * kNtKC;
+    p.nsplit = (int)((K + p.kchunk - 1) / p.kchunk);
+    p.direct = p.nsplit == 1 && batch == 1;
+    p.grid = (long)((batch * p.nsplit + 7) / 8 * 8) * sg_cdiv(N, 128) * sg_cdiv(M, 128);
+    p.ws_bytes = p.direct ? 0 : (size_t)batch * p.nsplit * M * N * sizeof(float);
+    return p;
 }
 
 // ================================================================================================================
@@ -816,47 +829,99 @@ struct Gemm128Partial {
     __device__ void store(const Col& c, int i, int j, float v) const { ws[c.off + (long)i * N] = v; }
 };
 
-// Returns 1 if the product was launched here, 0 if the shape / layout is left to the skeleton.
-static int gemm128_try(const float* A, long sai, long sak, const float* B, long sbk, long sbj, const GemmEpi& epi, int M, int N,
-                       int K, float* ws, size_t ws_bytes, hipStream_t stream) {
+// Everything sg_gemm decides before it launches, as a pure function of shape, strides, alignment, workspace size and epilogue
+// addressing (host code: sg_gemm_plan reports it, sg_gemm launches from it).
+struct GemmPlan {
+    int kind;         // SG_GEMM_KIND_*
+    bool ak, bk;      // operand layouts: k-major (element (row, k) at p[row * ld + k]) or row-major
+    int tm, tn;       // skeleton: 32 x 32 MFMA tiles per wave (the workgroup tile is 64 tm x 64 tn)
+    int nsplit;       // partial images (1: the kernel writes C itself)
+    long kchunk;      // k range of one split
+    int finalize;     // SG_GEMM_FINALIZE_*
+    long grid;        // workgroups of the product kernel
+};
+
+// gemm128 / persistent part of the plan: false if the shape / layout is left to the skeleton
+static bool gemm128_plan(GemmPlan& p, const void* A, long sai, long sak, const void* B, long sbk, long sbj, long sci, long scj,
+                         bool has_bias_i, int M, int N, int K, bool has_ws, size_t ws_bytes) {
     constexpr bool off = SG_GEMM128 == 0;
     const bool ak = sak == 1 && sai != 1, bk = sbk == 1 && sbj != 1;      // (a degenerate dimension keeps the skeleton)
-    if (off || (!ak && sai != 1) || (!bk && sbj != 1) || (!ak && bk)) return 0;
+    if (off || (!ak && sai != 1) || (!bk && sbj != 1) || (!ak && bk)) return false;
     const long lda = ak ? sai : sak, ldb = bk ? sbj : sbk;
-    if (M < 128 || N < 128 || K < 64 || (long)M * N < (1L << 16)) return 0;
-    if ((lda & 3) || (ldb & 3) || (((uintptr_t)A) & 15) || (((uintptr_t)B) & 15)) return 0;
-    if ((!ak && (M & 3)) || (!bk && (N & 3))) return 0;
+    if (M < 128 || N < 128 || K < 64 || (long)M * N < (1L << 16)) return false;
+    if ((lda & 3) || (ldb & 3) || (((uintptr_t)A) & 15) || (((uintptr_t)B) & 15)) return false;
+    if ((!ak && (M & 3)) || (!bk && (N & 3))) return false;
     // 32-bit byte offsets inside a workgroup's window: 128 rows (k-major) or one K chunk of rows (row-major) of an operand
     const long tiles = (long)sg_cdiv(M, 128) * sg_cdiv(N, 128);
     long s = tiles >= 256 ? 1 : (512 + tiles - 1) / tiles;
     const long maxs = K / (8 * kNtKC) > 0 ? K / (8 * kNtKC) : 1;
     if (s > maxs) s = maxs;
     if (s > 128) s = 128;
-    if (s > 1 && (!ws || ws_bytes < (size_t)s * M * N * sizeof(float))) s = ws ? (long)(ws_bytes / ((size_t)M * N * sizeof(float))) : 1;
+    if (s > 1 && (!has_ws || ws_bytes < (size_t)s * M * N * sizeof(float))) s = has_ws ? (long)(ws_bytes / ((size_t)M * N * sizeof(float))) : 1;
     if (s < 1) s = 1;
-    if (tiles * s < 128) return 0;                                          // too small to fill the chip either way
-    Gemm128Args g;
-    g.A = A;
-    g.B = B;
-    g.lda = lda;
-    g.ldb = ldb;
-    g.M = M;
-    g.N = N;
-    g.K = K;
-    g.kchunk = ((K + s - 1) / s + kNtKC - 1) / kNtKC * kNtKC;
-    g.nsplit = (int)((K + g.kchunk - 1) / g.kchunk);
-    const long win_a = ak ? 128 * lda + g.kchunk : g.kchunk * lda + 128, win_b = bk ? 128 * ldb + g.kchunk : g.kchunk * ldb + 128;
-    if (win_a * 4 >= (long)kBufRange || win_b * 4 >= (long)kBufRange) return 0;
-    const size_t lds = (size_t)2 * 2 * kNtOp * sizeof(float);
+    if (tiles * s < 128) return false;                                      // too small to fill the chip either way
+    p.ak = ak;
+    p.bk = bk;
+    p.tm = p.tn = 0;
+    p.kchunk = ((K + s - 1) / s + kNtKC - 1) / kNtKC * kNtKC;
+    p.nsplit = (int)((K + p.kchunk - 1) / p.kchunk);
+    const long win_a = ak ? 128 * lda + p.kchunk : p.kchunk * lda + 128, win_b = bk ? 128 * ldb + p.kchunk : p.kchunk * ldb + 128;
+    if (win_a * 4 >= (long)kBufRange || win_b * 4 >= (long)kBufRange) return false;
     // a product without a K split and with more tiles than resident workgroups runs persistently (-DSG_GEMM128=2 builds: one workgroup per tile)
     constexpr bool persist_off = SG_GEMM128 == 2;
     // (its epilogue writes rows of C through one 32-bit-offset window per tile that ends with row M - 1: unit column stride, rows
     // that do not overlap (sci >= N: the window's end is what clips the rows beyond M), no per-row bias, 128 rows of C below 2 GiB;
     // its operand windows span the whole K range)
-    const bool persistent = !persist_off && tiles > 512 && ((K + kNtKC - 1) / kNtKC) % 2 == 0 && epi.scj == 1 && epi.sci >= N && !epi.bias_i && 128 * epi.sci * 4 < (long)kBufRange &&
+    const bool persistent = !persist_off && tiles > 512 && ((K + kNtKC - 1) / kNtKC) % 2 == 0 && scj == 1 && sci >= N && !has_bias_i && 128 * sci * 4 < (long)kBufRange &&
                             (ak ? 128 * lda + K : (long)K * lda + 128) * 4 < (long)kBufRange &&
                             (bk ? 128 * ldb + K : (long)K * ldb + 128) * 4 < (long)kBufRange;
-    const unsigned wgs = g.nsplit > 1 ? (unsigned)((g.nsplit + 7) / 8 * 8 * tiles) : (unsigned)tiles;
+    if (p.nsplit > 1) {
+        p.kind = SG_GEMM_KIND_GEMM128_SPLIT;
+        p.grid = (long)((p.nsplit + 7) / 8 * 8) * tiles;
+        p.finalize = splitk_finalize_is_deep(p.nsplit, M, N) ? SG_GEMM_FINALIZE_DEEP : SG_GEMM_FINALIZE_FLAT;
+    } else {
+        p.kind = persistent ? SG_GEMM_KIND_PERSISTENT : SG_GEMM_KIND_GEMM128;
+        p.grid = persistent && tiles > 512 ? 512 : tiles;
+        p.finalize = SG_GEMM_FINALIZE_NONE;
+    }
+    return true;
+}
+
+static GemmPlan gemm_plan(const void* A, long sai, long sak, const void* B, long sbk, long sbj, long sci, long scj, bool has_bias_i,
+                          int M, int N, int K, bool has_ws, size_t ws_bytes) {
+    GemmPlan p;
+    if (gemm128_plan(p, A, sai, sak, B, sbk, sbj, sci, scj, has_bias_i, M, N, K, has_ws, ws_bytes)) return p;
+    const TilePlan t = plan_tiles_ws(M, N, K, has_ws, ws_bytes);
+    p.kind = SG_GEMM_KIND_SKELETON;
+    p.ak = sak == 1;      // prefer the k-contiguous form when a dimension is degenerate (both strides legal)
+    p.bk = sbk == 1;
+    p.tm = t.tm;
+    p.tn = t.tn;
+    p.nsplit = t.splitk;
+    p.kchunk = tile_kchunk(K, t.splitk);
+    const dim3 g = tile_grid(M, N, t);
+    p.grid = (long)g.x * g.y * g.z;
+    p.finalize = t.splitk == 1 ? SG_GEMM_FINALIZE_NONE : splitk_finalize_is_deep(t.splitk, M, N) ? SG_GEMM_FINALIZE_DEEP : SG_GEMM_FINALIZE_FLAT;
+    return p;
+}
+
+// launches a gemm128 / persistent plan
+static void gemm128_launch(const GemmPlan& p, const float* A, long sai, long sak, const float* B, long sbk, long sbj, const GemmEpi& epi,
+                           int M, int N, int K, float* ws, hipStream_t stream) {
+    const bool ak = p.ak, bk = p.bk;
+    Gemm128Args g;
+    g.A = A;
+    g.B = B;
+    g.lda = ak ? sai : sak;
+    g.ldb = bk ? sbj : sbk;
+    g.M = M;
+    g.N = N;
+    g.K = K;
+    g.kchunk = p.kchunk;
+    g.nsplit = p.nsplit;
+    const bool persistent = p.kind == SG_GEMM_KIND_PERSISTENT;
+    const unsigned wgs = (unsigned)p.grid;
+    const size_t lds = (size_t)2 * 2 * kNtOp * sizeof(float);
 #define SG_G128(AK_, BK_)                                                                                                         \
     do {                                                                                                                         \
         static SgPerDeviceOnce once_d, once_p;                                                                                  \
@@ -867,7 +932,7 @@ static int gemm128_try(const float* A, long sai, long sak, const float* B, long 
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
                 once_pp.end();                                                                                                   \
             }                                                                                                                    \
-            hipLaunchKernelGGL((gemm128p_kernel<AK_, BK_>), dim3(tiles < 512 ? (unsigned)tiles : 512u), dim3(256), lds, stream, g, epi); \
+            hipLaunchKernelGGL((gemm128p_kernel<AK_, BK_>), dim3(wgs), dim3(256), lds, stream, g, epi);                             \
         } else if (g.nsplit == 1) {                                                                                              \
             if (once_d.begin()) {                                                                                                \
                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm128_kernel<AK_, BK_, Gemm128Direct>),                \
@@ -889,17 +954,7 @@ static int gemm128_try(const float* A, long sai, long sak, const float* B, long 
     else if (ak && !bk) SG_G128(true, false);
     else SG_G128(false, false);
 #undef SG_G128
-    if (g.nsplit > 1) {
-        if (g.nsplit >= 32 && (long)M * N <= (1L << 18)) {
-            hipLaunchKernelGGL((splitk_finalize_deep_kernel<GemmEpi>), dim3((unsigned)(((long)M * N + 63) / 64)), dim3(256), 0, stream,
-                               (const float*)ws, epi, M, N, g.nsplit);
-        } else {
-            const long fb = (long)M * ((N + 1023) >> 10);
-            hipLaunchKernelGGL((splitk_finalize_kernel<GemmEpi>), dim3((unsigned)fb), dim3(256), 0, stream, (const float*)ws, epi, M, N,
-                               g.nsplit);
-        }
-    }
-    return 1;
+    if (g.nsplit > 1) launch_splitk_finalize((const float*)ws, epi, M, N, g.nsplit, stream);
 }
 
 }  // namespace sg
@@ -919,23 +974,52 @@ int sg_gemm(const float* A, long sai, long sak, const float* B, long sbk, long s
     SG_CHECK_ARG(sbk == 1 || sbj == 1);
     GemmEpi epi{C, sci, scj, bias_i, bias_j, bias_j_shift, act, slope};
     float* ws = (float*)workspace;
-    if (gemm128_try(A, sai, sak, B, sbk, sbj, epi, M, N, K, ws, workspace_bytes, stream) == 1) {
+    const GemmPlan p = gemm_plan(A, sai, sak, B, sbk, sbj, sci, scj, bias_i != nullptr, M, N, K, ws != nullptr, workspace_bytes);
+    if (p.kind != SG_GEMM_KIND_SKELETON) {
+        gemm128_launch(p, A, sai, sak, B, sbk, sbj, epi, M, N, K, ws, stream);
         SG_CHECK_LAUNCH();
         return SG_OK;
     }
-    // prefer the k-contiguous form when a dimension is degenerate (both strides legal)
-    const bool a_kfast = (sak == 1);
-    const bool b_kfast = (sbk == 1);
-    if (a_kfast && b_kfast) {
-        launch_tile_gemm(MatRowMajor{A, sai, 0}, MatRowMajor{B, sbj, 0}, epi, M, N, K, ws, workspace_bytes, stream);
-    } else if (a_kfast && !b_kfast) {
-        launch_tile_gemm(MatRowMajor{A, sai, 0}, MatColMajor{B, sbk, 0}, epi, M, N, K, ws, workspace_bytes, stream);
-    } else if (!a_kfast && b_kfast) {
-        launch_tile_gemm(MatColMajor{A, sak, 0}, MatRowMajor{B, sbj, 0}, epi, M, N, K, ws, workspace_bytes, stream);
+    const TilePlan t{p.tm, p.tn, p.nsplit};
+    if (p.ak && p.bk) {
+        launch_tile_gemm_planned(MatRowMajor{A, sai, 0}, MatRowMajor{B, sbj, 0}, epi, M, N, K, t, ws, stream);
+    } else if (p.ak && !p.bk) {
+        launch_tile_gemm_planned(MatRowMajor{A, sai, 0}, MatColMajor{B, sbk, 0}, epi, M, N, K, t, ws, stream);
+    } else if (!p.ak && p.bk) {
+        launch_tile_gemm_planned(MatColMajor{A, sak, 0}, MatRowMajor{B, sbj, 0}, epi, M, N, K, t, ws, stream);
     } else {
-        launch_tile_gemm(MatColMajor{A, sak, 0}, MatColMajor{B, sbk, 0}, epi, M, N, K, ws, workspace_bytes, stream);
+        launch_tile_gemm_planned(MatColMajor{A, sak, 0}, MatColMajor{B, sbk, 0}, epi, M, N, K, t, ws, stream);
     }
     SG_CHECK_LAUNCH();
+    return SG_OK;
+}
+
+/* host code only: the plan sg_gemm launches from (see the header) */
+int sg_gemm_plan(const void* A, long sai, long sak, const void* B, long sbk, long sbj, long sci, long scj, int has_bias_i, int M, int N,
+                 int K, const void* workspace, size_t workspace_bytes, long* plan) {
+    SG_CHECK_ARG(plan && M > 0 && N > 0 && K > 0);
+    SG_CHECK_ARG(sai == 1 || sak == 1);
+    SG_CHECK_ARG(sbk == 1 || sbj == 1);
+    const GemmPlan p = gemm_plan(A, sai, sak, B, sbk, sbj, sci, scj, has_bias_i != 0, M, N, K, workspace != nullptr, workspace_bytes);
+    plan[0] = p.kind;
+    plan[1] = p.tm;
+    plan[2] = p.tn;
+    plan[3] = p.nsplit;
+    plan[4] = p.kchunk;
+    plan[5] = p.finalize;
+    plan[6] = p.grid;
+    plan[7] = (p.ak ? 2 : 0) + (p.bk ? 1 : 0);
+    return SG_OK;
+}
+
+int sg_gemm_nt_plan(int batch, int M, int N, long K, long* plan) {
+    SG_CHECK_ARG(plan && batch > 0 && batch <= kNtMaxBatch && M > 0 && N > 0 && K > 0);
+    const GemmNtPlan p = gemm_nt_plan(M, N, K, batch);
+    plan[0] = p.direct ? 1 : 0;
+    plan[1] = p.nsplit;
+    plan[2] = p.kchunk;
+    plan[3] = p.grid;
+    plan[4] = (long)p.ws_bytes;
     return SG_OK;
 }
 
@@ -983,12 +1067,10 @@ static int gemm_nt_launch(const float* A, const long* a_off, long lda, const flo
                           const long* c_off, const long* ldc, int batch, int M, int N, long K, void* workspace,
                           size_t workspace_bytes, hipStream_t stream, const char* who, const float* gamma = nullptr,
                           const float* beta = nullptr, const long* g_off = nullptr) {
-    int nsplit;
-    long kchunk;
-    gemm_nt_plan(M, N, K, nsplit, kchunk, batch);
-    const bool direct = nsplit == 1 && batch == 1;
-    if (!direct && (!workspace || workspace_bytes < (size_t)batch * nsplit * M * N * sizeof(float)))
-        SG_FAIL(SG_ERR_WORKSPACE, "%s: workspace too small", who);
+    const GemmNtPlan plan = gemm_nt_plan(M, N, K, batch);
+    const int nsplit = plan.nsplit;
+    const bool direct = plan.direct;
+    if (!direct && (!workspace || workspace_bytes < plan.ws_bytes)) SG_FAIL(SG_ERR_WORKSPACE, "%s: workspace too small", who);
     GemmNtArgs a;
     a.A = A;
     a.B = B;
@@ -997,7 +1079,7 @@ static int gemm_nt_launch(const float* A, const long* a_off, long lda, const flo
     a.M = M;
     a.N = N;
     a.K = K;
-    a.kchunk = kchunk;
+    a.kchunk = plan.kchunk;
     a.nsplit = nsplit;
     for (int b = 0; b < kNtMaxBatch; ++b) {
         a.a_off[b] = b < batch ? a_off[b] : 0;
@@ -1018,7 +1100,7 @@ static int gemm_nt_launch(const float* A, const long* a_off, long lda, const flo
         attr_once.end();
     }
     a.ngroups = batch * nsplit;
-    const unsigned wgs = (unsigned)((a.ngroups + 7) / 8 * 8 * sg_cdiv(N, 128) * sg_cdiv(M, 128));
+    const unsigned wgs = (unsigned)plan.grid;
     if (gamma)
         hipLaunchKernelGGL(gemm_nt_bigk_kernel<true>, dim3(wgs), dim3(256), lds, stream, a);
     else
@@ -1036,12 +1118,7 @@ static int gemm_nt_launch(const float* A, const long* a_off, long lda, const flo
     return SG_OK;
 }
 
-size_t sg_gemm_nt_workspace_bytes(int M, int N, long K) {
-    int nsplit;
-    long kchunk;
-    gemm_nt_plan(M, N, K, nsplit, kchunk);
-    return nsplit > 1 ? (size_t)nsplit * M * N * sizeof(float) : 0;
-}
+size_t sg_gemm_nt_workspace_bytes(int M, int N, long K) { return gemm_nt_plan(M, N, K).ws_bytes; }
 
 int sg_gemm_nt(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, long K, void* workspace,
                size_t workspace_bytes, hipStream_t stream) {
@@ -1054,10 +1131,7 @@ int sg_gemm_nt(const float* A, long lda, const float* B, long ldb, float* C, lon
 }
 
 size_t sg_gemm_nt_batched_workspace_bytes(int batch, int M, int N, long K) {
-    int nsplit;
-    long kchunk;
-    gemm_nt_plan(M, N, K, nsplit, kchunk, batch);
-    return (size_t)batch * nsplit * M * N * sizeof(float);
+    return (size_t)batch * gemm_nt_plan(M, N, K, batch).nsplit * M * N * sizeof(float);
 }
 
 int sg_gemm_nt_batched(const float* A, const long* a_off, long lda, const float* B, const long* b_off, long ldb, float* C,

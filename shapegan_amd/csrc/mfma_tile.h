@@ -343,36 +343,53 @@ static inline TilePlan plan_tiles(int M, int N, int K, long ws_floats_avail, int
     return best;
 }
 
+// The launch arithmetic of a planned product: read by the launcher below and by the plan query (sg_gemm_plan), nowhere else.
+static inline int tile_kchunk(int K, int splitk) { return splitk == 1 ? K : sg_cdiv(sg_cdiv(K, splitk), kBK) * kBK; }
+static inline dim3 tile_grid(int M, int N, const TilePlan& p) { return dim3(sg_cdiv(N, 64 * p.tn), sg_cdiv(M, 64 * p.tm), p.splitk); }
+// many partials of a small matrix go to splitk_finalize_deep_kernel, everything else to splitk_finalize_kernel
+static inline bool splitk_finalize_is_deep(int splits, int M, int N) { return splits >= 32 && (long)M * N <= (1L << 18); }
+static inline unsigned splitk_finalize_blocks(int splits, int M, int N) {
+    return splitk_finalize_is_deep(splits, M, N) ? (unsigned)(((long)M * N + 63) / 64) : (unsigned)((long)M * ((N + 1023) >> 10));
+}
+template <class EPI>
+static void launch_splitk_finalize(const float* ws, EPI epi, int M, int N, int splits, hipStream_t st) {
+    const unsigned fb = splitk_finalize_blocks(splits, M, N);
+    if (splitk_finalize_is_deep(splits, M, N))
+        hipLaunchKernelGGL((splitk_finalize_deep_kernel<EPI>), dim3(fb), dim3(256), 0, st, ws, epi, M, N, splits);
+    else
+        hipLaunchKernelGGL((splitk_finalize_kernel<EPI>), dim3(fb), dim3(256), 0, st, ws, epi, M, N, splits);
+}
+
 template <int TM, int TN, class LA, class LB, class EPI>
 static int launch_tile_gemm_t(LA la, LB lb, EPI epi, int M, int N, int K, int splitk, float* ws, hipStream_t st) {
-    dim3 grid(sg_cdiv(N, 64 * TN), sg_cdiv(M, 64 * TM), splitk);
+    const dim3 grid = tile_grid(M, N, TilePlan{TM, TN, splitk});
     if (splitk == 1) {
-        hipLaunchKernelGGL((tile_gemm_kernel<TM, TN, LA, LB, EPI>), grid, dim3(256), 0, st, la, lb, epi, M, N, K, K);
+        hipLaunchKernelGGL((tile_gemm_kernel<TM, TN, LA, LB, EPI>), grid, dim3(256), 0, st, la, lb, epi, M, N, K, tile_kchunk(K, 1));
     } else {
-        int kchunk = sg_cdiv(sg_cdiv(K, splitk), kBK) * kBK;
         EpiWorkspace wepi{ws, M, N};
         hipLaunchKernelGGL((tile_gemm_kernel<TM, TN, LA, LB, EpiWorkspace>), grid, dim3(256), 0, st, la, lb, wepi, M, N,
-                           K, kchunk);
-        if (splitk >= 32 && (long)M * N <= (1L << 18)) {
-            hipLaunchKernelGGL((splitk_finalize_deep_kernel<EPI>), dim3((unsigned)(((long)M * N + 63) / 64)), dim3(256), 0, st,
-                               (const float*)ws, epi, M, N, splitk);
-        } else {
-            const long fb = (long)M * ((N + 1023) >> 10);
-            hipLaunchKernelGGL((splitk_finalize_kernel<EPI>), dim3((unsigned)fb), dim3(256), 0, st, (const float*)ws, epi,
-                               M, N, splitk);
-        }
+                           K, tile_kchunk(K, splitk));
+        launch_splitk_finalize((const float*)ws, epi, M, N, splitk, st);
     }
     return 0;
 }
 
-// ws may be null (then no split-K). ws_bytes is the size of the caller-owned workspace.
+// the tile plan the workspace allows (ws may be null: then no split-K; ws_bytes is the size of the caller-owned workspace)
+static inline TilePlan plan_tiles_ws(int M, int N, int K, bool has_ws, size_t ws_bytes) {
+    return plan_tiles(M, N, K, has_ws ? (long)(ws_bytes / sizeof(float)) : 0);
+}
+
 template <class LA, class LB, class EPI>
-static int launch_tile_gemm(LA la, LB lb, EPI epi, int M, int N, int K, float* ws, size_t ws_bytes, hipStream_t st) {
-    const TilePlan p = plan_tiles(M, N, K, ws ? (long)(ws_bytes / sizeof(float)) : 0);
+static int launch_tile_gemm_planned(LA la, LB lb, EPI epi, int M, int N, int K, const TilePlan& p, float* ws, hipStream_t st) {
     if (p.tm == 2 && p.tn == 2) return launch_tile_gemm_t<2, 2>(la, lb, epi, M, N, K, p.splitk, ws, st);
     if (p.tm == 2 && p.tn == 1) return launch_tile_gemm_t<2, 1>(la, lb, epi, M, N, K, p.splitk, ws, st);
     if (p.tm == 1 && p.tn == 2) return launch_tile_gemm_t<1, 2>(la, lb, epi, M, N, K, p.splitk, ws, st);
     return launch_tile_gemm_t<1, 1>(la, lb, epi, M, N, K, p.splitk, ws, st);
+}
+
+template <class LA, class LB, class EPI>
+static int launch_tile_gemm(LA la, LB lb, EPI epi, int M, int N, int K, float* ws, size_t ws_bytes, hipStream_t st) {
+    return launch_tile_gemm_planned(la, lb, epi, M, N, K, plan_tiles_ws(M, N, K, ws != nullptr, ws_bytes), ws, st);
 }
 
 }  // namespace sg

@@ -105,6 +105,8 @@ ROWS = {
     "sg_last_error": (c_char_p, []),
     "sg_gemm": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _I, _I, _I, _I, _I, _F, _P, _Z, _P]),
     "sg_gemm_workspace_bytes": (_Z, [_I, _I]),
+    "sg_gemm_plan": (c_int, [_P, _L, _L, _P, _L, _L, _L, _L, _I, _I, _I, _I, _P, _Z, _P]),
+    "sg_gemm_nt_plan": (c_int, [_I, _I, _I, _L, _P]),
     "sg_loss_meansq_fwd": (c_int, [_P, _P, _L, _I, _D, _P, _P, _Z, _P]),
     "sg_conv3d_k4s2p1_image_layout": (c_longlong, [_I, _P, _Z]),
     "sg_sdfnet_bwd_blocks": (c_long, [_L]),

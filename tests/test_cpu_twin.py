@@ -14,6 +14,7 @@ import torch.nn as nn
 import shapegan_amd.lib as L
 import autograd_cases as AG
 import conv_patterns as GRIDS
+import gemm_forms as GEMM
 import sdfnet_forms as FORMS
 import test_gpu_modules as M
 import test_gpu_ops as OPS
@@ -49,7 +50,7 @@ def test_twin_exports_every_entry_point():
             "sg_abi_version", "sg_last_error", "sg_sdfnet_packed_floats", "sg_sdfnet_acts_floats", "sg_sdfnet_bwd_blocks", "sg_sdfnet_bwd_tile_start", "sg_sdf_batch_sort_max_shapes",
             "sg_sdfgen_acts_floats", "sg_sdfgen_packed_norm_offset", "sg_sdfgen_bwd_blocks", "sg_pointnet_packed_floats",
             "sg_conv3d_k4s2p1_wgrad_act_eligible", "sg_convT3d_k4s2p1_to1_pre_eligible", "sg_conv3d_k4s2p1_wgrad_dy_image",
-            "sg_conv3d_k4s2p1_image_layout")
+            "sg_conv3d_k4s2p1_image_layout", "sg_gemm_plan", "sg_gemm_nt_plan")
 
 
 def test_dispatch_is_by_tensor_device_only(on_cpu):
@@ -144,6 +145,39 @@ def test_linear(on_cpu, M_, N_, K_):
 
 def test_gemm_double_backward(on_cpu):
     OPS.test_gemm_double_backward()
+
+
+# the bodies of tests/test_gpu_gemm_forms.py (tests/gemm_forms.py): the GEMM family against float64, operands inside NaN buffers.  The
+# twin has no dispatch: of the sg_gemm table it runs the cases its plain loops finish quickly (every layout, epilogue and finalize
+# branch has one among them); the plans the cases claim are checked by tests/test_gemm_dispatch.py.
+@pytest.mark.parametrize("case_id", GEMM.GEMM_TWIN_IDS)
+def test_gemm_forms(on_cpu, case_id):
+    GEMM.body_gemm(case_id)
+
+
+@pytest.mark.parametrize("case_id", [i for i in GEMM.NONFINITE_IDS if i in GEMM.GEMM_TWIN_IDS])
+def test_gemm_forms_nan_and_inf(on_cpu, case_id):
+    GEMM.body_gemm_nonfinite(case_id)
+
+
+@pytest.mark.parametrize("case_id", [c.id for c in GEMM.NT_CASES])
+def test_gemm_nt_forms(on_cpu, case_id):
+    GEMM.body_gemm_nt(case_id)
+
+
+def test_gemm_nt_forms_nan_and_inf(on_cpu):
+    GEMM.body_gemm_nt_nonfinite()
+
+
+def test_gemm_family_reductions(on_cpu):
+    for case in GEMM.ROWSUM_CASES:
+        GEMM.body_rowsum(*case)
+    for case in GEMM.ROWSUM_MULTI_CASES:
+        GEMM.body_rowsum_multi(*case)
+    for case in GEMM.SEGSUM_CASES:
+        GEMM.body_segsum(*case)
+    for case in GEMM.COLSUM_CASES:
+        GEMM.body_colsum(*case)
 
 
 @pytest.mark.parametrize("N,C,S", [(4, 8, 64), (4, 256, 1), (3, 7, 27)])

@@ -28,6 +28,7 @@ import torch.nn.functional as F
 
 from poison import poisoned, run_poisoned
 import conv_patterns as GRIDS
+import gemm_forms as GEMM
 import evaluation_reference as ER
 import test_evaluation as EV
 import test_gpu_losses as LOSS
@@ -99,6 +100,10 @@ BODIES = [
     (OPS.test_linear_fwd_bwd, (16388, 384, 320)), (OPS.test_linear_fwd_bwd, (40004, 128, 100)),
     (OPS.test_gemm128_persistent_all_layouts, (70004, 256, 100)),
     (OPS.test_gemm_nt_bigk, (70, 130, 1000, 1003)), (OPS.test_gemm_nt_bigk, (256, 256, 31, 40)),
+    # the GEMM family against float64 (tests/test_gpu_gemm_forms.py): one case per kernel kind, and the reductions
+    *[(GEMM.body_gemm, (i,)) for i in GEMM.POISON_IDS], *[(GEMM.body_gemm_nt, (i,)) for i in GEMM.NT_POISON_IDS],
+    (GEMM.body_rowsum, GEMM.ROWSUM_CASES[0]), (GEMM.body_rowsum_multi, GEMM.ROWSUM_MULTI_CASES[1]),
+    (GEMM.body_segsum, GEMM.SEGSUM_CASES[1]), (GEMM.body_colsum, GEMM.COLSUM_CASES[3]),
     (OPS.test_colsum_tall, ()), (OPS.test_mean_reduction, ()), (OPS.test_gather_scatter_rows_bit_exact, ()),
     (OPS.test_batchnorm_train_fwd_bwd, (3, 7, 27)), (OPS.test_batchnorm_train_fwd_bwd, (4, 256, 1)),
     (OPS.test_batchnorm_train_fwd_bwd, (4, 24, 4096)),

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import conv_patterns as GRIDS
+import gemm_forms as GEMM
 import poison
 from poison import poisoned, run_poisoned
 from test_cpu_twin import on_cpu  # noqa: F401  (fixture)
@@ -121,6 +122,10 @@ BODIES = [
     *GRIDS.DISPATCH_BODIES,          # (the conv family on grids of three different extents: tests/test_gpu_conv_grids.py)
     (OPS.test_linear_fwd_bwd, (64, 128, 256)), (OPS.test_linear_fwd_bwd, (4, 128, 256)), (OPS.test_linear_fwd_bwd, (5, 7, 3)),
     (OPS.test_gemm_double_backward, ()),
+    # (the GEMM family against float64: tests/test_gpu_gemm_forms.py)
+    *[(GEMM.body_gemm, (i,)) for i in GEMM.POISON_TWIN_IDS], *[(GEMM.body_gemm_nt, (i,)) for i in GEMM.NT_POISON_IDS],
+    (GEMM.body_rowsum, GEMM.ROWSUM_CASES[0]), (GEMM.body_rowsum_multi, GEMM.ROWSUM_MULTI_CASES[1]),
+    (GEMM.body_segsum, GEMM.SEGSUM_CASES[1]), (GEMM.body_colsum, GEMM.COLSUM_CASES[3]),
     (OPS.test_batchnorm_train_fwd_bwd, (4, 8, 64)), (OPS.test_batchnorm_train_fwd_bwd, (4, 256, 1)),
     (OPS.test_batchnorm_train_fwd_bwd, (3, 7, 27)),
     (OPS.test_activations, ()), (OPS.test_mean_reduction, ()), (OPS.test_gather_scatter_rows_bit_exact, ()),
