@@ -480,11 +480,7 @@ class HybridGANOracle(ClassicGANOracle):
 def pointnet_forward(P, pos, dist):
     """PointNet.forward, point_sdf_net.py:33-47 (dense path, batch=None)."""
     dist = dist.unsqueeze(-1) if dist.size(-1) != 1 else dist
-    x = torch.cat([pos, dist], dim=-1)
-    for i in (0, 2, 4, 6):
-        x = F.linear(x, P["nn1.%d.weight" % i], P["nn1.%d.bias" % i])
-        if i < 6:
-            x = F.relu(x)
+    x = pointnet_features(P, torch.cat([pos, dist], dim=-1))
     x = x.max(dim=-2)[0]
     for i in (0, 2, 4):
         x = F.linear(x, P["nn2.%d.weight" % i], P["nn2.%d.bias" % i])
@@ -493,9 +489,18 @@ def pointnet_forward(P, pos, dist):
     return x
 
 
-def sdf_generator_forward(P, pos, z, num_layers=8):
-    """SDFGenerator.forward, point_sdf_net.py:83-119 (norm=True, dropout 0)."""
-    x = pos
+def pointnet_features(P, x):
+    """nn1 of PointNet.forward on x = cat([pos, dist]) [..., P, 4] -> [..., P, 512]: the per-point features the max runs over."""
+    for i in (0, 2, 4, 6):
+        x = F.linear(x, P["nn1.%d.weight" % i], P["nn1.%d.bias" % i])
+        if i < 6:
+            x = F.relu(x)
+    return x
+
+
+def _sdf_generator_layers(P, pos, z, num_layers, eps):
+    """SDFGenerator.forward -> (output, the ReLU inputs of the num_layers - 1 normed layers)."""
+    x, pre = pos, []
     for i in range(num_layers):
         if i == num_layers // 2:
             x = torch.cat([x, pos], dim=-1)
@@ -506,8 +511,22 @@ def sdf_generator_forward(P, pos, z, num_layers=8):
             x = F.linear(z, P["z_lin2.weight"], P["z_lin2.bias"]).unsqueeze(1) + x
         if i < num_layers - 1:
             w = P["norms.%d.weight" % i]
-            x = F.relu(F.layer_norm(x, (w.shape[0],), w, P["norms.%d.bias" % i], 1e-5))
-    return x
+            pre.append(F.layer_norm(x, (w.shape[0],), w, P["norms.%d.bias" % i], eps))
+            x = F.relu(pre[-1])
+    return x, pre
+
+
+def sdf_generator_forward(P, pos, z, num_layers=8, eps=1e-5):
+    """SDFGenerator.forward, point_sdf_net.py:83-119 (norm=True, dropout 0); eps: that of every LayerNorm."""
+    return _sdf_generator_layers(P, pos, z, num_layers, eps)[0]
+
+
+def sdf_generator_min_preactivation(P, pos, z, eps=1e-5, num_layers=8):
+    """min over the normed layers and their units of |ReLU input| per point, [B, P] (see sdfnet_min_preactivation: a point
+    whose smallest |ReLU input| is within fp32 rounding of 0 sits on a kink)."""
+    with torch.no_grad():
+        pre = _sdf_generator_layers(P, pos, z, num_layers, eps)[1]
+        return torch.stack([x.abs().min(dim=-1).values for x in pre]).min(dim=0).values
 
 
 class PointGANOracle(object):

@@ -985,7 +985,9 @@ static inline float ln_relu(const float* x, const float* g, const float* b, floa
 }
 int sg_sdfgen_fwd_cpu(const float* points, const float* packed, const float* zb1, const float* zb5, long points_per_shape,
                       const int* shape_index, float eps, float* out, float* acts, long ldn, long N, void*) {
-    CPU_CHECK(points && packed && zb1 && zb5 && out && N > 0 && eps > 0.f && (shape_index || points_per_shape > 0));
+    CPU_CHECK(points && packed && zb1 && zb5 && out && N > 0 && eps > 0.f);
+    // (the HIP kernel's tiles must not straddle shapes without a shape index: the twin refuses the same calls)
+    CPU_CHECK(shape_index || (points_per_shape > 0 && (points_per_shape % 128 == 0 || points_per_shape >= N)));
     CPU_CHECK(!acts || ldn >= N);
     const CpuSdf v = sdf_view(packed, 3);
     const float *G = packed + kGenG, *Be = packed + kGenBe;

@@ -144,7 +144,11 @@ class SDFGenerator(nn.Module):
         self._pack = ops._GenPackCache()
 
     def _fused(self, pos):
-        """The one-launch form covers the script's configuration; every other one runs layer by layer."""
+        """The one-launch form covers the script's configuration; every other one runs layer by layer.  So does a call whose
+        positions require grad: the fused backward has no position-gradient path (sg_sdfgen_bwd writes no dx), the layer-by-layer
+        operators return that gradient."""
+        if torch.is_grad_enabled() and pos.requires_grad:
+            return False
         return (self.hidden_channels == 256 and self.num_layers == 8
                 and all(n.elementwise_affine and n.eps == self.norms[0].eps for n in self.norms))
 

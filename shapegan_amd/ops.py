@@ -1596,6 +1596,11 @@ class SDFGenFused(Function):
         N = pos.shape[0]
         if N != S * pps or zb1.shape != (S, _H) or zb5.shape != (S, _H):
             raise RuntimeError("SDFGenFused: need pos for all %d x %d samples and [S, 256] rows" % (S, pps))
+        # LayerNorm ignores what is common to the 256 channels of a row, and the kernels start their accumulators from these rows:
+        # a row whose mean is far above its spread (a large bias) would cost every product added to it its low bits.  The rows go
+        # to the kernel without their channel mean.  Their gradients are untouched: dZ1 / dZ5 sum to zero over the channels.
+        zb1 = zb1 - zb1.mean(dim=1, keepdim=True)
+        zb5 = zb5 - zb5.mean(dim=1, keepdim=True)
         lib = _lib()
         dev = pos.device
         packed = cache.get(params)

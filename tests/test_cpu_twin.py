@@ -15,6 +15,7 @@ import shapegan_amd.lib as L
 import autograd_cases as AG
 import conv_patterns as GRIDS
 import gemm_forms as GEMM
+import pointgan_forms as PG
 import sdfnet_forms as FORMS
 import test_gpu_modules as M
 import test_gpu_ops as OPS
@@ -264,6 +265,58 @@ def test_sdfnet_grid_values_of_several_shapes(on_cpu):
 def test_sdfnet_points_per_shape_refusal(on_cpu):
     """The twin refuses what the HIP library refuses: a caller that only the HIP library would stop shows in this tier."""
     FORMS.body_points_per_shape_refusal()
+
+
+# the bodies of tests/test_gpu_pointgan_forms.py (tests/pointgan_forms.py): the point-GAN kernels in every calling form against float64
+@pytest.mark.parametrize("S,pps,sid", PG.SHAPES)
+def test_pointgan_generator_shapes(on_cpu, S, pps, sid):
+    PG.body_shapes(S, pps, sid)
+
+
+@pytest.mark.parametrize("where", sorted(PG.ONE_HOT_POSITIONS))
+def test_pointgan_generator_one_hot(on_cpu, where):
+    PG.body_one_hot(where)
+
+
+@pytest.mark.parametrize("need_z,need_lins,need_norms", PG.SUBSETS)
+def test_pointgan_generator_which_grads(on_cpu, need_z, need_lins, need_norms):
+    PG.body_which_grads(need_z, need_lins, need_norms)
+
+
+def test_pointgan_generator_forward_without_grad(on_cpu):
+    PG.body_no_grad_forward()
+
+
+def test_pointgan_generator_positions_require_grad(on_cpu):
+    PG.body_positions_require_grad()
+
+
+def test_pointgan_generator_offset_rows(on_cpu):
+    PG.body_offset_rows()
+
+
+def test_pointgan_generator_eps(on_cpu):
+    PG.body_eps(1e-3)
+
+
+def test_pointgan_generator_raw_abi_ldn(on_cpu):
+    """The twin refuses what the HIP library refuses."""
+    PG.body_raw_abi_ldn()
+
+
+@pytest.mark.parametrize("B,P,twin_rows", PG.SELECT_CASES)
+def test_pointgan_pointnet_select(on_cpu, B, P, twin_rows):
+    PG.body_select(B, P, twin_rows)
+
+
+@pytest.mark.parametrize("P", PG.FORWARD_POINTS)
+def test_pointgan_pointnet_forward_forms(on_cpu, P):
+    PG.body_forward_forms(P)
+
+
+@pytest.mark.parametrize("P", PG.PENALTY_POINTS)
+def test_pointgan_pointnet_gradient_penalty(on_cpu, P):
+    PG.body_gradient_penalty(P)
 
 
 @pytest.mark.parametrize("S,pc,N", [(64, 200, 20000), (5, 40, 700), (300, 7, 1000), (4097, 3, 9000)])
