@@ -510,43 +510,47 @@ using namespace sg;
 
 extern "C" {
 
-// A/B switch for the edge-layer kernels of conv3d_edge.hip (SG_NO_EDGE=1 restores the previous kernels)
-static bool edge_enabled(int which = 7) {   // SG_NO_EDGE = bit mask: 1 forward, 2 input gradient, 4 weight gradient
-    constexpr int off = SG_NO_EDGE;
-    return (off & which) == 0;
+// The size queries ask the plans what a kernel family needs for a shape (workspace_need, with every byte allowed) and add what
+// the gather kernels of this file need.  The geometry of a query: the O^3 grid of the stride-2 side, tensors of exactly Cin / Cout
+// channels.
+constexpr size_t kAnyWorkspace = ~(size_t)0;
+static bool query_geom(ConvGeom& g, int Cin, int Cout, int OD, int OH, int OW) {
+    return OD > 0 && OH > 0 && OW > 0 && make_geom(g, 2 * OD, 2 * OH, 2 * OW, Cin, Cout) == 0;
 }
+static size_t max3(size_t a, size_t b, size_t c = 0) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
 
+// gather kernel: the per-parity weight image;  LDS-halo kernel: its weight image (neither depends on the batch or the grid)
+static size_t dgrad_gather_workspace_bytes(int Cout, int Cin) { return (size_t)8 * Cout * 8 * Cin * sizeof(float); }
 size_t sg_conv3d_k4s2p1_dgrad_workspace_bytes(int Cout, int Cin) {
-    const size_t a = (size_t)8 * Cout * 8 * Cin * sizeof(float), b = halo_dgrad_workspace_bytes(Cin, Cout);
-    return a > b ? a : b;
+    return max3(dgrad_gather_workspace_bytes(Cout, Cin), halo_dgrad_workspace_bytes(Cin, Cout));
 }
 
 size_t sg_conv3d_k4s2p1_dgrad_workspace_bytes_for(int batch, int Cin, int Cout, int OD, int OH, int OW) {
-    const size_t a = sg_conv3d_k4s2p1_dgrad_workspace_bytes(Cout, Cin);
-    const size_t b = (Cin == 1 && Cout <= 64) ? edge_dgrad_workspace_bytes(batch, OD, OH, OW) : 0;
-    return a > b ? a : b;
+    ConvGeom g;
+    const size_t edge = query_geom(g, Cin, Cout, OD, OH, OW) ? edge_dgrad_plan(batch, Cin, Cout, g, kAnyWorkspace).workspace_need : 0;
+    return max3(sg_conv3d_k4s2p1_dgrad_workspace_bytes(Cout, Cin), edge);
 }
 
 size_t sg_conv3d_k4s2p1_wgrad_workspace_bytes(int batch, int Cin, int Cout, int OD, int OH, int OW) {
     // gather kernel: up to 16 split-K partials of the [Cout, Cin*64] weight gradient; LDS-halo kernel: packed dy + partials
-    const size_t a = (size_t)16 * Cout * Cin * 64 * sizeof(float);
-    const size_t b = (Cin >= 2 && Cout >= 32) ? halo_wgrad_workspace_bytes(batch, Cin, Cout, OD, OH, OW) : 0;   // halo_wgrad_try's own gate
-    const size_t c = (Cin == 1 && Cout <= 64) ? edge_wgrad_workspace_bytes(batch, OD, OH, OW) : 0;
-    const size_t ab = a > b ? a : b;
-    return ab > c ? ab : c;
+    const size_t gather = (size_t)16 * Cout * Cin * 64 * sizeof(float);
+    ConvGeom g;
+    if (!query_geom(g, Cin, Cout, OD, OH, OW)) return gather;
+    return max3(gather, halo_wgrad_plan(batch, Cin, Cout, g, kAnyWorkspace, true).workspace_need,
+                edge_wgrad_plan(batch, Cin, Cout, g, kAnyWorkspace, 0).workspace_need);
 }
 
 size_t sg_conv3d_k4s2p1_fwd_workspace_bytes(int batch, int Cin, int Cout, int OD, int OH, int OW) {
     // (a) the LDS-halo kernel's packed weight image, (b) split-K partials of the gather kernel, used only when
-    // batch*O^3 x Cout gives fewer than 512 tiles of 64x64 (<= 8 partials)
+    // batch*O^3 x Cout gives fewer than 512 tiles of 64x64 (<= 8 partials).  The one-channel forward needs no workspace.
     const size_t per = (size_t)batch * Cout * OD * OH * OW;
     const size_t tiles = ((size_t)batch * OD * OH * OW + 63) / 64 * ((Cout + 63) / 64);
     const size_t splitk = tiles >= 512 ? 0 : per * 8 * sizeof(float);
     const size_t pack = halo_fwd_workspace_bytes(Cin, Cout);
-    const size_t edge = (Cin == 1 && Cout <= 64) ? edge_fwd_workspace_bytes(batch, OD, OH, OW) : 0;
-    // (4^3 outputs at small batches: the halo kernel's image AND its channel-split partials — at most 8 — side by side)
-    const size_t sp = (OD == 4 && OH == 4 && OW == 4) ? pack + splitk : (splitk > pack ? splitk : pack);
-    return sp > edge ? sp : edge;
+    // 4^3 outputs at small batches: the halo kernel keeps its channel-split partials BEHIND the image (HaloFwdPlan::partial_offset);
+    // at most as many as the gather kernel's split-K, so image + splitk holds whatever halo_fwd_plan chooses
+    static_assert(kHaloFwd4MaxSplit == 8, "the 4^3 forward's partials must fit the gather kernel's 8 split-K partials");
+    return (OD == 4 && OH == 4 && OW == 4) ? pack + splitk : (splitk > pack ? splitk : pack);
 }
 
 static int check_sizes(const ConvGeom& g, int batch, const char* who) {
@@ -567,29 +571,25 @@ static int fwd_call(const float* x, const float* w, const float* bias, float* y,
     if (make_geom(g, ID, IH, IW, Cx, Cout)) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_fwd: spatial dims must be even and >= 2");
     if (check_sizes(g, batch, "sg_conv3d_k4s2p1_fwd")) return SG_ERR_ARG;
     const long npos = (long)batch * g.O3();
-    if (Cin == 1 && edge_enabled(1) &&
-        edge_fwd_try(x, w, bias, y, batch, Cin, Cin_total, g, Cout, act, slope, workspace, workspace_bytes, stream) == 1) {
+    const EdgeFwdPlan ep = edge_fwd_plan(batch, Cin, Cout, g, act, slope);
+    if (ep.served) {
+        edge_fwd_launch(ep, x, w, bias, y, batch, Cin_total, Cout, g, act, slope, stream);
         SG_CHECK_LAUNCH();
         return SG_OK;
     }
-    {
-        const int rc = halo_fwd_try(x, w, bias, y, batch, Cin, Cin_total, g, Cout, act, slope, workspace, workspace_bytes,
-                                    stream, 0, 0, packed_already);
-        if (rc < 0) return rc;
-        if (rc == 1) {
-            SG_CHECK_LAUNCH();
-            return SG_OK;
-        }
-        if (rc > 16) {      // the 4^3 halo kernel with its input channels split over rc - 16 workgroups: partial sums behind the image
-            const int csplit = rc - 16;
+    const HaloFwdPlan hp = halo_fwd_plan(batch, Cin, Cout, g, workspace ? workspace_bytes : 0);
+    if (hp.served) {
+        if (!packed_already) halo_fwd_pack(hp, w, Cin, Cin_total, Cout, workspace, stream);
+        halo_fwd_launch(hp, x, bias, y, batch, Cin, Cout, g, act, slope, workspace, stream);
+        if (hp.csplit > 1) {      // the 4^3 halo kernel with its input channels split over csplit workgroups: partial sums behind the image
             FwdEpi epi{y, bias, g.O3(), Cout, FastDiv((uint32_t)g.O3()), act, slope};
-            const float* partial = reinterpret_cast<const float*>(static_cast<const char*>(workspace) + halo_fwd_workspace_bytes(Cin, Cout));
+            const float* partial = workspace_at<float>(workspace, hp.partial_offset);
             const long fb = (long)Cout * ((npos + 1023) >> 10);
             hipLaunchKernelGGL((splitk_finalize_kernel<FwdEpi>), dim3((unsigned)fb), dim3(256), 0, stream, partial, epi, Cout, (int)npos,
-                               csplit);
-            SG_CHECK_LAUNCH();
-            return SG_OK;
+                               hp.csplit);
         }
+        SG_CHECK_LAUNCH();
+        return SG_OK;
     }
     MatRowMajor la;
     la.p = w;
@@ -635,9 +635,10 @@ int sg_conv3d_k4s2p1_fwd_impl(const float* x, const float* w, const float* bias,
     if (make_geom(g, ID, IH, IW, Cx, Cout)) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_fwd_impl: bad spatial dims");
     if (check_sizes(g, batch, "sg_conv3d_k4s2p1_fwd_impl")) return SG_ERR_ARG;
     if (impl == 1) {
-        const int rc = halo_fwd_try(x, w, bias, y, batch, Cin, Cin_total, g, Cout, act, slope, workspace, workspace_bytes,
-                                    stream, 1, debug);
-        if (rc != 1) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_fwd_impl: shape not eligible for the LDS-halo kernel");
+        const HaloFwdPlan hp = halo_fwd_plan(batch, Cin, Cout, g, workspace ? workspace_bytes : 0, halo_fwd_form_decode(debug));
+        if (!hp.served) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_fwd_impl: shape not eligible for the LDS-halo kernel");
+        halo_fwd_pack(hp, w, Cin, Cin_total, Cout, workspace, stream);
+        halo_fwd_launch(hp, x, bias, y, batch, Cin, Cout, g, act, slope, workspace, stream);
         SG_CHECK_LAUNCH();
         return SG_OK;
     }
@@ -666,8 +667,9 @@ static int dgrad_call(const float* dy, const float* w, const float* bias, float*
     if (make_geom(g, ID, IH, IW, Cx, Cout)) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_dgrad: spatial dims must be even and >= 2");
     if (check_sizes(g, batch, "sg_conv3d_k4s2p1_dgrad")) return SG_ERR_ARG;
     const long npos = (long)batch * g.O3();
-    if (Cin == 1 && edge_enabled(2) &&
-        edge_dgrad_try(dy, w, bias, dx, batch, Cin, Cin_total, g, Cout, act, slope, workspace, workspace_bytes, stream) == 1) {
+    const EdgeDgradPlan ep = edge_dgrad_plan(batch, Cin, Cout, g, workspace ? workspace_bytes : 0);
+    if (ep.served) {
+        edge_dgrad_launch(ep, dy, w, bias, dx, batch, Cin_total, Cout, g, act, slope, workspace, stream);
         SG_CHECK_LAUNCH();
         return SG_OK;
     }
@@ -692,16 +694,14 @@ static int dgrad_call(const float* dy, const float* w, const float* bias, float*
         SG_CHECK_LAUNCH();
         return SG_OK;
     }
-    {
-        const int rc = halo_dgrad_try(dy, w, bias, dx, batch, Cin, Cin_total, g, Cout, act, slope, workspace,
-                                      workspace_bytes, stream, 0, packed_already);
-        if (rc < 0) return rc;
-        if (rc == 1) {
-            SG_CHECK_LAUNCH();
-            return SG_OK;
-        }
+    const HaloDgradPlan hp = halo_dgrad_plan(batch, Cin, Cout, g, workspace ? workspace_bytes : 0);
+    if (hp.served) {
+        if (!packed_already) halo_dgrad_pack(hp, w, Cin, Cin_total, Cout, workspace, stream);
+        halo_dgrad_launch(hp, dy, bias, dx, batch, Cin, Cout, g, act, slope, workspace, stream);
+        SG_CHECK_LAUNCH();
+        return SG_OK;
     }
-    const size_t need = (size_t)8 * Cout * 8 * Cin * sizeof(float);
+    const size_t need = dgrad_gather_workspace_bytes(Cout, Cin);
     if (!workspace || workspace_bytes < need)
         SG_FAIL(SG_ERR_WORKSPACE, "sg_conv3d_k4s2p1_dgrad: workspace too small (%zu < %zu)", workspace_bytes, need);
     float* wt = (float*)workspace;
@@ -757,6 +757,19 @@ int sg_conv3d_k4s2p1_dgrad_keep(const float* dy, const float* w, const float* bi
                       weights_unchanged != 0);
 }
 
+// The weight image a call (kind 0: sg_conv3d_k4s2p1_fwd_keep, 1: sg_conv3d_k4s2p1_dgrad_keep) keeps in its workspace, from the plan that
+// call itself makes; false: not served by a kernel with a kept image
+static bool kept_image_of_call(int kind, int batch, int Cin, int Cout, const ConvGeom& g, size_t workspace_bytes, ImageJob* image) {
+    if (kind == 0) {
+        const HaloFwdPlan p = halo_fwd_plan(batch, Cin, Cout, g, workspace_bytes);
+        *image = p.image;
+        return p.served;
+    }
+    const HaloDgradPlan p = halo_dgrad_plan(batch, Cin, Cout, g, workspace_bytes);
+    *image = p.image;
+    return p.served;
+}
+
 // The weight images of up to 8 forthcoming calls in ONE launch.  Call i is described by kinds[i] (0: sg_conv3d_k4s2p1_fwd_keep, 1:
 // sg_conv3d_k4s2p1_dgrad_keep) and dims[8 i ..] = {batch, Cin, Cin_total, Cx, Cout, ID, IH, IW} exactly as it will be made, with the
 // workspace it will be given.  served[i] = 1: the image is in place, make the call with weights_unchanged = 1;  0: that call is
@@ -766,7 +779,6 @@ int sg_conv3d_k4s2p1_pack_images(int n, const int* kinds, const float* const* we
                                  const size_t* workspace_bytes, const int* dims, int* served, hipStream_t stream) {
     SG_CHECK_ARG(n > 0 && n <= 8 && kinds && weights && workspaces && workspace_bytes && dims && served);
     PackJobs jobs;
-    static const float dummy = 0.f;       // operand pointers are only stored in collect mode, never dereferenced
     for (int i = 0; i < n; ++i) {
         const int* d = dims + 8 * i;
         const int batch = d[0], Cin = d[1], Cin_total = d[2], Cx = d[3], Cout = d[4];
@@ -775,16 +787,9 @@ int sg_conv3d_k4s2p1_pack_images(int n, const int* kinds, const float* const* we
         ConvGeom g;
         if (make_geom(g, d[5], d[6], d[7], Cx, Cout)) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_pack_images: bad spatial dims");
         if (check_sizes(g, batch, "sg_conv3d_k4s2p1_pack_images")) return SG_ERR_ARG;
-        if (Cin == 1) continue;          // the one-channel kernels read the weights in place
-        int rc;
-        if (kinds[i] == 0)
-            rc = halo_fwd_try(&dummy, weights[i], nullptr, const_cast<float*>(&dummy), batch, Cin, Cin_total, g, Cout, SG_ACT_NONE, 0.f,
-                              workspaces[i], workspace_bytes[i], stream, 0, 0, false, &jobs);
-        else
-            rc = halo_dgrad_try(&dummy, weights[i], nullptr, const_cast<float*>(&dummy), batch, Cin, Cin_total, g, Cout, SG_ACT_NONE, 0.f,
-                                workspaces[i], workspace_bytes[i], stream, 0, false, &jobs);
-        if (rc < 0) return rc;
-        served[i] = rc == 1;
+        ImageJob image;
+        if (!kept_image_of_call(kinds[i], batch, Cin, Cout, g, workspaces[i] ? workspace_bytes[i] : 0, &image)) continue;
+        served[i] = jobs.add(image, weights[i], workspaces[i], Cout, Cin_total, Cin);
     }
     halo_pack_jobs_launch(jobs, stream);
     SG_CHECK_LAUNCH();
@@ -804,17 +809,10 @@ long long sg_conv3d_k4s2p1_image_layout(int kind, const int* dims, size_t worksp
     ConvGeom g;
     if (make_geom(g, dims[5], dims[6], dims[7], Cx, Cout)) return 0;
     if ((long)batch * g.O3() >= (1L << 31) || (long)batch * g.I3() >= (1L << 31)) return 0;
-    PackJobs jobs;
-    static const float dummy = 0.f;               // operand pointers are only stored in collect mode, never dereferenced
-    char* const base = reinterpret_cast<char*>(uintptr_t(1) << 20);
-    const int rc = kind == 0 ? halo_fwd_try(&dummy, &dummy, nullptr, const_cast<float*>(&dummy), batch, Cin, Cin_total, g, Cout, SG_ACT_NONE,
-                                            0.f, base, workspace_bytes, nullptr, 0, 0, false, &jobs)
-                             : halo_dgrad_try(&dummy, &dummy, nullptr, const_cast<float*>(&dummy), batch, Cin, Cin_total, g, Cout,
-                                              SG_ACT_NONE, 0.f, base, workspace_bytes, nullptr, 0, false, &jobs);
-    if (rc != 1 || jobs.n != 1) return 0;
-    const PackJob& j = jobs.job[0];
+    ImageJob j;
+    if (!kept_image_of_call(kind, batch, Cin, Cout, g, workspace_bytes, &j)) return 0;
     unsigned long long h = 1469598103934665603ull;                       // FNV-1a over the fields that define the image
-    const long long f[7] = {j.kind + 1, j.Cout, j.Cin_total, j.Cin, j.nt, (long long)(reinterpret_cast<char*>(j.wp) - base), 0x5347};
+    const long long f[7] = {j.kind + 1, Cout, Cin_total, Cin, j.nt, (long long)j.offset, 0x5347};
     for (long long v : f)
         for (int b = 0; b < 8; ++b) {
             h ^= (unsigned long long)(v >> (8 * b)) & 0xffull;
@@ -828,15 +826,19 @@ long long sg_conv3d_k4s2p1_image_layout(int kind, const int* dims, size_t worksp
 int sg_conv3d_k4s2p1_dgrad_impl(const float* dy, const float* w, const float* bias, float* dx, int batch, int Cin,
                                 int Cin_total, int Cx, int Cout, int ID, int IH, int IW, int act, float slope,
                                 void* workspace, size_t workspace_bytes, int impl, hipStream_t stream) {
-    SG_CHECK_ARG(dy && w && dx && batch > 0 && Cin > 0 && Cin <= Cin_total && Cin <= Cx && Cout > 0 && (impl & 1) &&
-                 ((impl & ~64) == 1 || (impl & ~64) == 3 || (impl & ~64) == 9 || (impl & ~64) == 17 || (impl & ~64) == 33));
+    // impl 1: forced, 3: one parity per workgroup, 1 + 4 ppw: ppw = 2, 4 or 8 parities; + 64: the depth-skip form of the 4^3 64-row
+    // kernel (4^3 grids only)
+    HaloDgradForm form;
+    SG_CHECK_ARG(dy && w && dx && batch > 0 && Cin > 0 && Cin <= Cin_total && Cin <= Cx && Cout > 0 &&
+                 halo_dgrad_form_decode(impl, &form) && form.forced &&
+                 (form.ppw == 0 || (!form.one_parity && (form.ppw == 2 || form.ppw == 4 || form.ppw == 8))));
     ConvGeom g;
     if (make_geom(g, ID, IH, IW, Cx, Cout)) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_dgrad_impl: bad spatial dims");
     if (check_sizes(g, batch, "sg_conv3d_k4s2p1_dgrad_impl")) return SG_ERR_ARG;
-    const int rc = halo_dgrad_try(dy, w, bias, dx, batch, Cin, Cin_total, g, Cout, act, slope, workspace, workspace_bytes,
-                                  stream, impl);   // 1: forced, 3: one parity per workgroup, 1 + 4 ppw: ppw parities;
-                                                   // + 64: the depth-skip form of the 4^3 64-row kernel (4^3 grids only)
-    if (rc != 1) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_dgrad_impl: shape not eligible for the LDS-halo kernel");
+    const HaloDgradPlan hp = halo_dgrad_plan(batch, Cin, Cout, g, workspace ? workspace_bytes : 0, form);
+    if (!hp.served) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_dgrad_impl: shape not eligible for the LDS-halo kernel");
+    halo_dgrad_pack(hp, w, Cin, Cin_total, Cout, workspace, stream);
+    halo_dgrad_launch(hp, dy, bias, dx, batch, Cin, Cout, g, act, slope, workspace, stream);
     SG_CHECK_LAUNCH();
     return SG_OK;
 }
@@ -849,8 +851,10 @@ int sg_conv3d_k4s2p1_wgrad_impl(const float* dy, const float* x, float* dw, int 
     ConvGeom g;
     if (make_geom(g, ID, IH, IW, Cx, Cout)) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_wgrad_impl: bad spatial dims");
     if (check_sizes(g, batch, "sg_conv3d_k4s2p1_wgrad_impl")) return SG_ERR_ARG;
-    const int rc = halo_wgrad_try(dy, x, dw, batch, Cin, Cin_total, g, Cout, workspace, workspace_bytes, stream, 1);
-    if (rc != 1) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_wgrad_impl: shape not eligible for the LDS-halo kernel");
+    const HaloWgradPlan hp = halo_wgrad_plan(batch, Cin, Cout, g, workspace ? workspace_bytes : 0, true);
+    if (!hp.served) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_wgrad_impl: shape not eligible for the LDS-halo kernel");
+    halo_wgrad_pack(hp, dy, Cout, g, workspace, stream);
+    halo_wgrad_launch(hp, x, dw, Cin, Cin_total, Cout, g, workspace, stream);
     SG_CHECK_LAUNCH();
     return SG_OK;
 }
@@ -869,8 +873,11 @@ int sg_conv3d_k4s2p1_wgrad_dy_image(int batch, int Cin, int Cout, int OD, int OH
     if (batch <= 0 || Cin <= 0 || Cout <= 0 || !mt_total || !nslice) return 0;
     ConvGeom g;
     if (make_geom(g, 2 * OD, 2 * OH, 2 * OW, Cin, Cout)) return 0;
-    if (Cin == 1 && Cout <= 64) return 0;      // the one-channel kernels
-    return halo_wgrad_dy_image_plan(batch, Cin, Cout, g, workspace_bytes, mt_total, nslice);
+    const HaloWgradPlan hp = halo_wgrad_plan(batch, Cin, Cout, g, workspace_bytes, false);
+    if (!hp.producer_image) return 0;
+    *mt_total = hp.dy_image.nt;
+    *nslice = hp.nslice;
+    return 1;
 }
 int sg_act_bwd_rowsum_pack8(const float* y, const float* dy, float* dz, float* rowsum, void* dz_image, long N, int C, long nslice,
                             int act, float slope, hipStream_t stream) {
@@ -887,23 +894,19 @@ int sg_conv3d_k4s2p1_wgrad_prepacked(const float* dy, const float* x, float* dw,
     ConvGeom g;
     if (make_geom(g, ID, IH, IW, Cx, Cout)) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_wgrad_prepacked: bad spatial dims");
     if (check_sizes(g, batch, "sg_conv3d_k4s2p1_wgrad_prepacked")) return SG_ERR_ARG;
-    int mt;
-    long ns;
-    if (!halo_wgrad_dy_image_plan(batch, Cin, Cout, g, workspace_bytes, &mt, &ns))
+    const HaloWgradPlan hp = halo_wgrad_plan(batch, Cin, Cout, g, workspace ? workspace_bytes : 0, false);
+    if (!hp.producer_image)
         SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_wgrad_prepacked: this call is not served with a producer-written image");
-    if (halo_wgrad_try(dy, x, dw, batch, Cin, Cin_total, g, Cout, workspace, workspace_bytes, stream, 0, true) != 1)
-        SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_wgrad_prepacked: not served");
+    halo_wgrad_launch(hp, x, dw, Cin, Cin_total, Cout, g, workspace, stream);
     SG_CHECK_LAUNCH();
     return SG_OK;
 }
 
 int sg_conv3d_k4s2p1_wgrad_act_eligible(int batch, int Cin, int Cout, int OD, int OH, int OW, int act) {
-    // the same refusal conditions as edge_wgrad_try: 32-bit buffer ranges of the one-channel grid (read in place; the
-    // resource starts (IH + 1) rows + 1 element before it) and of dy / y
-    const size_t x_bytes = ((size_t)batch * 8 * OD * OH * OW + (size_t)(2 * OH + 1) * 2 * OW + 4) * 4;
-    const size_t dy_bytes = (size_t)batch * Cout * OD * OH * OW * 4;
-    return Cin == 1 && Cout <= 64 && OW % 16 == 0 && (long)batch * OD * OH * OW >= 65536 && (act == SG_ACT_LEAKY || act == SG_ACT_RELU) &&
-           x_bytes < (size_t)kBufRange && dy_bytes < (size_t)kBufRange && edge_enabled(4);
+    // the fused plan of the call on tensors of exactly one / Cout channels, with every byte of workspace allowed
+    ConvGeom g;
+    return batch > 0 && act != SG_ACT_NONE && query_geom(g, 1, Cout, OD, OH, OW) &&
+           edge_wgrad_plan(batch, Cin, Cout, g, kAnyWorkspace, act).served;
 }
 int sg_conv3d_k4s2p1_wgrad_act(const float* dy, const float* y, const float* x, float* dw, float* db, int batch, int Cin,
                                int Cin_total, int Cx, int Cout, int ID, int IH, int IW, int act, float slope, void* workspace,
@@ -912,10 +915,10 @@ int sg_conv3d_k4s2p1_wgrad_act(const float* dy, const float* y, const float* x, 
     ConvGeom g;
     if (make_geom(g, ID, IH, IW, Cx, Cout)) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_wgrad_act: spatial dims must be even and >= 2");
     if (check_sizes(g, batch, "sg_conv3d_k4s2p1_wgrad_act")) return SG_ERR_ARG;
-    if (!sg_conv3d_k4s2p1_wgrad_act_eligible(batch, Cin, Cout, g.OD, g.OH, g.OW, act) ||
-        edge_wgrad_try(dy, x, dw, batch, Cin, Cin_total, g, Cout, workspace, workspace ? workspace_bytes : 0, stream, 0, y, act, slope,
-                       db) != 1)
+    const EdgeWgradPlan ep = edge_wgrad_plan(batch, Cin, Cout, g, workspace ? workspace_bytes : 0, act);
+    if (act == SG_ACT_NONE || !ep.served)
         SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_wgrad_act: shape not served (see sg_conv3d_k4s2p1_wgrad_act_eligible) or workspace too small");
+    edge_wgrad_launch(ep, dy, y, x, dw, db, batch, Cin_total, Cout, g, slope, workspace, stream);
     SG_CHECK_LAUNCH();
     return SG_OK;
 }
@@ -928,19 +931,18 @@ int sg_conv3d_k4s2p1_wgrad(const float* dy, const float* x, float* dw, int batch
     if (make_geom(g, ID, IH, IW, Cx, Cout)) SG_FAIL(SG_ERR_ARG, "sg_conv3d_k4s2p1_wgrad: spatial dims must be even and >= 2");
     if (check_sizes(g, batch, "sg_conv3d_k4s2p1_wgrad")) return SG_ERR_ARG;
     const long npos = (long)batch * g.O3();
-    if (Cin == 1 && edge_enabled(4) &&
-        edge_wgrad_try(dy, x, dw, batch, Cin, Cin_total, g, Cout, workspace, workspace ? workspace_bytes : 0, stream) == 1) {
+    const EdgeWgradPlan ep = edge_wgrad_plan(batch, Cin, Cout, g, workspace ? workspace_bytes : 0, 0);
+    if (ep.served) {
+        edge_wgrad_launch(ep, dy, nullptr, x, dw, nullptr, batch, Cin_total, Cout, g, 0.f, workspace, stream);
         SG_CHECK_LAUNCH();
         return SG_OK;
     }
-    {
-        const int rc = halo_wgrad_try(dy, x, dw, batch, Cin, Cin_total, g, Cout, workspace, workspace ? workspace_bytes : 0,
-                                      stream, 0);
-        if (rc < 0) return rc;
-        if (rc == 1) {
-            SG_CHECK_LAUNCH();
-            return SG_OK;
-        }
+    const HaloWgradPlan hp = halo_wgrad_plan(batch, Cin, Cout, g, workspace ? workspace_bytes : 0, false);
+    if (hp.served) {
+        halo_wgrad_pack(hp, dy, Cout, g, workspace, stream);
+        halo_wgrad_launch(hp, x, dw, Cin, Cin_total, Cout, g, workspace, stream);
+        SG_CHECK_LAUNCH();
+        return SG_OK;
     }
     WgradDyLoader la;
     la.dy = dy;
@@ -969,8 +971,9 @@ int sg_convT3d_k4s2p1_fwd(const float* x, const float* w, const float* bias, flo
 // (a BatchNorm3d + LeakyReLU between the producing layer and this one, model/gan.py:18-21, folded into the loads of
 // convT_c1_stream_kernel): x [batch, C, I^3] -> y [batch, 1, (2I)^3].  Served for C <= 64 and planes of at most 256 positions.
 int sg_convT3d_k4s2p1_to1_pre_eligible(int batch, int C, int ID, int IH, int IW) {
-    return batch > 0 && C > 0 && C <= 64 && ID > 0 && IH > 0 && IW > 0 && IH * IW <= 256 &&
-           (size_t)C * ID * IH * IW * 4 < (size_t)kBufRange && (long)batch * 8 * ID * IH * IW < (1L << 31);
+    ConvGeom g;      // (of the equivalent Conv3d(1 -> C) input gradient: its stride-2 side is the I^3 grid of x)
+    return batch > 0 && C > 0 && query_geom(g, 1, C, ID, IH, IW) && (long)batch * g.I3() < (1L << 31) &&
+           edge_dgrad_walk_plan(0, batch, 1, C, g).served;
 }
 static int convT_to1_pre(const float* x, const float* w, const float* bias, float* y, const float* in_scale,
                          const float* in_shift, int in_act, float in_slope, int batch, int C, int ID, int IH, int IW,
@@ -984,9 +987,10 @@ static int convT_to1_pre(const float* x, const float* w, const float* bias, floa
     if (make_geom(g, 2 * ID, 2 * IH, 2 * IW, 1, C)) SG_FAIL(SG_ERR_ARG, "sg_convT3d_k4s2p1_to1_pre: bad spatial dims");
     if (form == 3 || form == 4)
         SG_FAIL(SG_ERR_ARG, "sg_convT3d_k4s2p1_to1_pre_impl: forms 3 and 4 (both h parities per workgroup) were retired");
-    if (edge_dgrad_stream_try(x, w, bias, y, batch, 1, 1, g, C, act, slope, stream, in_scale, in_shift, in_act, in_slope,
-                              samples_per_group, y_group_stride, form) != 1)
-        SG_FAIL(SG_ERR_ARG, "sg_convT3d_k4s2p1_to1_pre: not served");
+    const EdgeDgradPlan ep = edge_dgrad_walk_plan(form, batch, 1, C, g);
+    if (!ep.served) SG_FAIL(SG_ERR_ARG, "sg_convT3d_k4s2p1_to1_pre: not served");
+    edge_dgrad_launch(ep, x, w, bias, y, batch, 1, C, g, act, slope, nullptr, stream, in_scale, in_shift, in_act, in_slope,
+                      samples_per_group, y_group_stride);
     SG_CHECK_LAUNCH();
     return SG_OK;
 }

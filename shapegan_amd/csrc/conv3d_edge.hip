@@ -1499,25 +1499,43 @@ __global__ void __launch_bounds__(512, 1) convT_c1_all_kernel(ConvTStreamArgs a)
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-size_t edge_fwd_workspace_bytes(int, int, int, int) { return 0; }   // the forward reads the grid in place
-size_t edge_wgrad_workspace_bytes(int, int, int, int) { return (size_t)512 * kEdgePartial * sizeof(float); }   // partial tiles
-size_t edge_dgrad_workspace_bytes(int batch, int OD, int OH, int OW) { return (size_t)batch * 64 * OD * OH * OW * sizeof(float); }
+// The one-channel kernels address x (plus the (IH + 1) rows + 1 element the resource starts before it) and y / dy with 32-bit
+// buffer offsets: both inside the 2 GiB window
+static bool edge_buffers_in_range(int batch, const ConvGeom& g) {
+    return ((size_t)batch * g.Cx * g.I3() + (size_t)(g.IH + 1) * g.IW + 4) * 4 < (size_t)kBufRange &&
+           (size_t)batch * g.Cy * g.O3() * 4 < (size_t)kBufRange;
+}
 
-// Conv3d(1 -> Cout <= 64) forward.  Returns 1 if handled, 0 if not eligible.  Needs no workspace (the grid is read in place).
-int edge_fwd_try(const float* x, const float* w, const float* bias, float* y, int batch, int Cin, int Cin_total,
-                 const ConvGeom& g, int Cout, int act, float slope, void* workspace, size_t workspace_bytes,
-                 hipStream_t stream, int force) {
-    (void)workspace;
-    (void)workspace_bytes;
+// Conv3d(1 -> Cout <= 64) forward.  Needs no workspace (the grid is read in place).
+EdgeFwdPlan edge_fwd_plan(int batch, int Cin, int Cout, const ConvGeom& g, int act, float slope) {
+    EdgeFwdPlan p = EdgeFwdPlan();
     const long O3 = g.O3();
-    if (Cin != 1 || Cout > 64 || O3 % 32 != 0) return 0;
-    if (!force && (long)batch * O3 < 65536) return 0;   // small problems: the generic kernel's launch is as good
-    // 32-bit buffer offsets: x (plus the (IH + 1) rows the resource starts before it) and y inside the 2 GiB window
-    if (((size_t)batch * g.Cx * g.I3() + (size_t)(g.IH + 1) * g.IW + 4) * 4 >= (size_t)kBufRange ||
-        (size_t)batch * g.Cy * O3 * 4 >= (size_t)kBufRange)
-        return 0;
+    if (Cin != 1 || Cout > 64 || O3 % 32 != 0) return p;
+    if ((long)batch * O3 < 65536) return p;   // small problems: the generic kernel's launch is as good
+    if (!edge_buffers_in_range(batch, g)) return p;
+    p.served = true;
+    p.block = 256;
+    p.nt = Cout > 32 ? 2 : 1;
     // LeakyReLU runs as max(t, slope t): only for slopes in [0, 1]; anything else takes the generic epilogue
-    const int actk = act == SG_ACT_NONE ? 0 : ((act == SG_ACT_LEAKY && slope >= 0.f && slope <= 1.f) ? 1 : 2);
+    p.actk = act == SG_ACT_NONE ? 0 : ((act == SG_ACT_LEAKY && slope >= 0.f && slope <= 1.f) ? 1 : 2);
+    // round 5: the LDS-staged form for 32- / 64-wide grids (the critic's first layer, the progressive discriminator's 64^3 stage)
+    p.bh = g.IW == 32 ? 16 : 8;
+    if ((g.IW == 32 || g.IW == 64) && g.OH % p.bh == 0) {
+        const int units = batch * g.OD * (g.OH / p.bh);
+        const int lwgs = units < 512 ? units : 512;
+        p.kernel = EdgeFwdKernel::lds_staged;
+        p.units_per_wg = (units + lwgs - 1) / lwgs;
+        p.grid = dim3((units + p.units_per_wg - 1) / p.units_per_wg);
+        return p;
+    }
+    const int wgs = (int)(batch * (O3 / 32) + 3) / 4;
+    p.kernel = EdgeFwdKernel::gather;
+    p.grid = dim3(wgs > 512 ? 512 : wgs);
+    return p;
+}
+
+static EdgeFwdArgs edge_fwd_args(const float* x, const float* w, const float* bias, float* y, int batch, int Cin_total, int Cout,
+                                 const ConvGeom& g, int act, float slope) {
     EdgeFwdArgs a;
     a.x = x;
     a.w = w;
@@ -1532,79 +1550,98 @@ int edge_fwd_try(const float* x, const float* w, const float* bias, float* y, in
     a.Cy = g.Cy;
     a.Cin_total = Cin_total;
     a.x_sample = (long)g.Cx * g.I3();
-    a.tiles_per_sample = (int)(O3 / 32);
+    a.tiles_per_sample = (int)(g.O3() / 32);
     a.total_tiles = batch * a.tiles_per_sample;
     a.dtps = FastDiv((uint32_t)a.tiles_per_sample);
     a.dOW = FastDiv((uint32_t)g.OW);
     a.dOH = FastDiv((uint32_t)g.OH);
     a.act = act;
     a.slope = slope;
-    // round 5: the LDS-staged form for 32- / 64-wide grids (the critic's first layer, the progressive discriminator's 64^3 stage)
-    {
-        const int bh = g.IW == 32 ? 16 : 8;
-        if (SG_FWD_C1_LDS && (g.IW == 32 || g.IW == 64) && g.OH % bh == 0) {
-            EdgeFwdLdsArgs l;
-            l.x = x;
-            l.w = w;
-            l.bias = bias;
-            l.y = y;
-            l.OD = g.OD;
-            l.OH = g.OH;
-            l.IH = g.IH;
-            l.Cout = Cout;
-            l.Cy = g.Cy;
-            l.Cin_total = Cin_total;
-            l.x_sample = (long)g.Cx * g.I3();
-            l.blocks_per_plane = g.OH / bh;
-            l.units = batch * g.OD * l.blocks_per_plane;
-            int lwgs = l.units < 512 ? l.units : 512;
-            l.units_per_wg = (l.units + lwgs - 1) / lwgs;
-            lwgs = (l.units + l.units_per_wg - 1) / l.units_per_wg;
-            l.dbpp = FastDiv((uint32_t)l.blocks_per_plane);
-            l.dOD = FastDiv((uint32_t)g.OD);
-            l.act = act;
-            l.slope = slope;
-#define SG_FWD_L(NT_, ACT_, IW_) hipLaunchKernelGGL((conv_fwd_c1_lds_kernel<NT_, ACT_, IW_>), dim3(lwgs), dim3(256), 0, stream, l)
-#define SG_FWD_LA(NT_, IW_) do { if (actk == 0) SG_FWD_L(NT_, 0, IW_); else if (actk == 1) SG_FWD_L(NT_, 1, IW_); else SG_FWD_L(NT_, 2, IW_); } while (0)
-            if (g.IW == 32) { if (Cout > 32) SG_FWD_LA(2, 32); else SG_FWD_LA(1, 32); }
-            else            { if (Cout > 32) SG_FWD_LA(2, 64); else SG_FWD_LA(1, 64); }
-#undef SG_FWD_LA
-#undef SG_FWD_L
-            return 1;
-        }
-    }
-    int wgs = (a.total_tiles + 3) / 4;
-    if (wgs > 512) wgs = 512;
-#define SG_FWD_C1(NT_, ACT_) hipLaunchKernelGGL((conv_fwd_c1_kernel<NT_, ACT_>), dim3(wgs), dim3(256), 0, stream, a)
-    if (Cout > 32) {
-        if (actk == 0) SG_FWD_C1(2, 0); else if (actk == 1) SG_FWD_C1(2, 1); else SG_FWD_C1(2, 2);
-    } else {
-        if (actk == 0) SG_FWD_C1(1, 0); else if (actk == 1) SG_FWD_C1(1, 1); else SG_FWD_C1(1, 2);
-    }
-#undef SG_FWD_C1
-    return 1;
+    return a;
+}
+static EdgeFwdLdsArgs edge_fwd_lds_args(const EdgeFwdPlan& p, const float* x, const float* w, const float* bias, float* y, int batch,
+                                        int Cin_total, int Cout, const ConvGeom& g, int act, float slope) {
+    EdgeFwdLdsArgs l;
+    l.x = x;
+    l.w = w;
+    l.bias = bias;
+    l.y = y;
+    l.OD = g.OD;
+    l.OH = g.OH;
+    l.IH = g.IH;
+    l.Cout = Cout;
+    l.Cy = g.Cy;
+    l.Cin_total = Cin_total;
+    l.x_sample = (long)g.Cx * g.I3();
+    l.blocks_per_plane = g.OH / p.bh;
+    l.units = batch * g.OD * l.blocks_per_plane;
+    l.units_per_wg = p.units_per_wg;
+    l.dbpp = FastDiv((uint32_t)l.blocks_per_plane);
+    l.dOD = FastDiv((uint32_t)g.OD);
+    l.act = act;
+    l.slope = slope;
+    return l;
+}
+
+// The instantiations for a plan's (nt, actk) and the grid width, as convT_walk_kernel below
+typedef void (*EdgeFwdLdsFn)(EdgeFwdLdsArgs);
+typedef void (*EdgeFwdFn)(EdgeFwdArgs);
+template <int NT, int IWT>
+static EdgeFwdLdsFn edge_fwd_lds_kernel_act(int actk) {
+    if (actk == 0) return conv_fwd_c1_lds_kernel<NT, 0, IWT>;
+    if (actk == 1) return conv_fwd_c1_lds_kernel<NT, 1, IWT>;
+    return conv_fwd_c1_lds_kernel<NT, 2, IWT>;
+}
+static EdgeFwdLdsFn edge_fwd_lds_kernel(int IW, int nt, int actk) {
+    if (IW == 32) return nt == 2 ? edge_fwd_lds_kernel_act<2, 32>(actk) : edge_fwd_lds_kernel_act<1, 32>(actk);
+    return nt == 2 ? edge_fwd_lds_kernel_act<2, 64>(actk) : edge_fwd_lds_kernel_act<1, 64>(actk);
+}
+template <int NT>
+static EdgeFwdFn edge_fwd_kernel_act(int actk) {
+    if (actk == 0) return conv_fwd_c1_kernel<NT, 0>;
+    if (actk == 1) return conv_fwd_c1_kernel<NT, 1>;
+    return conv_fwd_c1_kernel<NT, 2>;
+}
+
+void edge_fwd_launch(const EdgeFwdPlan& p, const float* x, const float* w, const float* bias, float* y, int batch, int Cin_total,
+                     int Cout, const ConvGeom& g, int act, float slope, hipStream_t stream) {
+    if (p.kernel == EdgeFwdKernel::lds_staged)
+        hipLaunchKernelGGL(edge_fwd_lds_kernel(g.IW, p.nt, p.actk), p.grid, dim3(p.block), p.lds, stream,
+                           edge_fwd_lds_args(p, x, w, bias, y, batch, Cin_total, Cout, g, act, slope));
+    else
+        hipLaunchKernelGGL(p.nt == 2 ? edge_fwd_kernel_act<2>(p.actk) : edge_fwd_kernel_act<1>(p.actk), p.grid, dim3(p.block), p.lds,
+                           stream, edge_fwd_args(x, w, bias, y, batch, Cin_total, Cout, g, act, slope));
 }
 
 // Conv3d(1 -> Cout <= 64) weight gradient (channel 0 of dw; the caller zeroes the rest when Cin_total > 1).
-// y != NULL: fused activation backward (act = SG_ACT_LEAKY / SG_ACT_RELU), db receives the bias gradient
-int edge_wgrad_try(const float* dy, const float* x, float* dw, int batch, int Cin, int Cin_total, const ConvGeom& g, int Cout,
-                   void* workspace, size_t workspace_bytes, hipStream_t stream, int force, const float* y, int act, float slope,
-                   float* db) {
-    const long O3 = g.O3();
-    if (Cin != 1 || Cout > 64 || g.OW % 16 != 0) return 0;
-    if (y && ((act != SG_ACT_LEAKY && act != SG_ACT_RELU) || !db)) return 0;
-    if (!force && (long)batch * O3 < 65536) return 0;
-    if (!workspace || workspace_bytes < edge_wgrad_workspace_bytes(batch, g.OD, g.OH, g.OW)) return 0;
-    if (((size_t)batch * g.Cx * g.I3() + (size_t)(g.IH + 1) * g.IW + 4) * 4 >= (size_t)kBufRange ||
-        (size_t)batch * g.Cy * O3 * 4 >= (size_t)kBufRange)
-        return 0;
-    float* partial = (float*)workspace;
+// fuse_act != 0: fused activation backward (SG_ACT_LEAKY / SG_ACT_RELU) from the layer's activated output y; db receives the bias
+// gradient.  workspace_need (the partial tiles) is set for every Cin == 1, Cout <= 64 shape, served or not.
+EdgeWgradPlan edge_wgrad_plan(int batch, int Cin, int Cout, const ConvGeom& g, size_t workspace_bytes, int fuse_act) {
+    EdgeWgradPlan p = EdgeWgradPlan();
+    if (Cin != 1 || Cout > 64) return p;
+    p.workspace_need = (size_t)512 * kEdgePartial * sizeof(float);
+    if (g.OW % 16 != 0) return p;
+    if (fuse_act != 0 && fuse_act != SG_ACT_LEAKY && fuse_act != SG_ACT_RELU) return p;
+    if ((long)batch * g.O3() < 65536) return p;
+    if (workspace_bytes < p.workspace_need) return p;
+    if (!edge_buffers_in_range(batch, g)) return p;
+    const int wgs = (int)(batch * (g.O3() / 32) + 3) / 4;
+    p.served = true;
+    p.grid = dim3(wgs > 512 ? 512 : wgs);
+    p.block = 256;
+    p.nt = Cout > 32 ? 2 : 1;
+    p.fuse = fuse_act;
+    return p;
+}
+
+static EdgeWgradArgs edge_wgrad_args(const float* dy, const float* y, const float* x, int batch, int Cout, const ConvGeom& g,
+                                     float slope, void* workspace) {
     EdgeWgradArgs a;
     a.dy = dy;
     a.y = y;
     a.slope = slope;
     a.x = x;
-    a.partial = partial;
+    a.partial = (float*)workspace;
     a.OD = g.OD;
     a.OH = g.OH;
     a.OW = g.OW;
@@ -1613,29 +1650,30 @@ int edge_wgrad_try(const float* dy, const float* x, float* dw, int batch, int Ci
     a.Cout = Cout;
     a.Cy = g.Cy;
     a.x_sample = (long)g.Cx * g.I3();
-    a.passes_per_sample = (int)(O3 / 32);
+    a.passes_per_sample = (int)(g.O3() / 32);
     a.total_passes = batch * a.passes_per_sample;
     a.dpps = FastDiv((uint32_t)a.passes_per_sample);
     a.dOW16 = FastDiv((uint32_t)(g.OW / 16));
     a.dOH = FastDiv((uint32_t)g.OH);
-    int wgs = (a.total_passes + 3) / 4;
-    if (wgs > 512) wgs = 512;
-    const int fuse = y ? act : 0;
-#define SG_LAUNCH_WGRAD_C1(MT, F) hipLaunchKernelGGL((conv_wgrad_c1_kernel<MT, F>), dim3(wgs), dim3(256), 0, stream, a)
-    if (Cout > 32) {
-        if (fuse == SG_ACT_LEAKY) SG_LAUNCH_WGRAD_C1(2, SG_ACT_LEAKY);
-        else if (fuse == SG_ACT_RELU) SG_LAUNCH_WGRAD_C1(2, SG_ACT_RELU);
-        else SG_LAUNCH_WGRAD_C1(2, 0);
-    } else {
-        if (fuse == SG_ACT_LEAKY) SG_LAUNCH_WGRAD_C1(1, SG_ACT_LEAKY);
-        else if (fuse == SG_ACT_RELU) SG_LAUNCH_WGRAD_C1(1, SG_ACT_RELU);
-        else SG_LAUNCH_WGRAD_C1(1, 0);
-    }
-#undef SG_LAUNCH_WGRAD_C1
-    hipLaunchKernelGGL(wgrad_c1_finalize_kernel, dim3(fuse ? 260 : 256), dim3(256), 0, stream, (const float*)partial, dw, wgs, Cout,
-                       Cin_total, db);
-    return 1;
+    return a;
 }
+
+typedef void (*EdgeWgradFn)(EdgeWgradArgs);
+template <int MT>
+static EdgeWgradFn edge_wgrad_kernel_fuse(int fuse) {
+    if (fuse == SG_ACT_LEAKY) return conv_wgrad_c1_kernel<MT, SG_ACT_LEAKY>;
+    if (fuse == SG_ACT_RELU) return conv_wgrad_c1_kernel<MT, SG_ACT_RELU>;
+    return conv_wgrad_c1_kernel<MT, 0>;
+}
+
+void edge_wgrad_launch(const EdgeWgradPlan& p, const float* dy, const float* y, const float* x, float* dw, float* db, int batch,
+                       int Cin_total, int Cout, const ConvGeom& g, float slope, void* workspace, hipStream_t stream) {
+    hipLaunchKernelGGL(p.nt == 2 ? edge_wgrad_kernel_fuse<2>(p.fuse) : edge_wgrad_kernel_fuse<1>(p.fuse), p.grid, dim3(p.block), p.lds,
+                       stream, edge_wgrad_args(dy, p.fuse ? y : nullptr, x, batch, Cout, g, slope, workspace));
+    hipLaunchKernelGGL(wgrad_c1_finalize_kernel, dim3(p.fuse ? 260 : 256), dim3(256), 0, stream, (const float*)workspace, dw, (int)p.grid.x,
+                       Cout, Cin_total, db);
+}
+
 
 // ---- the plane-walk ConvTranspose3d(C -> 1) kernels on the host ------------------------------------------------------------------
 // What the launcher needs to know of a kernel: its instantiations, the tap rows it keeps per LDS buffer, and whether that is more
@@ -1666,9 +1704,7 @@ static ConvTWalkFn convT_walk_kernel(bool full, bool pre, int act) {
 }
 
 template <class K>
-static void convT_walk_launch(const ConvTStreamArgs& f, bool pre, unsigned wgs, hipStream_t stream) {
-    const int nblocks = (f.P2 + 31) / 32;
-    const size_t lds = (size_t)2 * K::kTapRows * (nblocks * 32 + 4) * sizeof(float);      // [2 buffers][tap rows][stride]
+static void convT_walk_launch(const EdgeDgradPlan& p, const ConvTStreamArgs& f, bool pre, hipStream_t stream) {
     if (K::kLdsAttr) {
         static SgPerDeviceOnce once;
         if (once.begin()) {      // the attribute, once per device, for every instantiation that may be launched
@@ -1681,7 +1717,7 @@ static void convT_walk_launch(const ConvTStreamArgs& f, bool pre, unsigned wgs, 
             once.end();
         }
     }
-    hipLaunchKernelGGL(convT_walk_kernel<K>(f.Cout == 64 && f.P2 == 256, pre, f.act), dim3(wgs), dim3(512), lds, stream, f);
+    hipLaunchKernelGGL(convT_walk_kernel<K>(f.Cout == 64 && f.P2 == 256, pre, f.act), p.grid, dim3(p.block), p.lds, stream, f);
 }
 
 // Kernel and plane walks per sample of a `form` of sg_convT3d_k4s2p1_to1_pre_impl.  Tests and tuning select a form through the
@@ -1714,18 +1750,62 @@ static ConvTPlan convT_plan(int form, int batch, int OD) {
     return {false, form == 2 && OD >= 4 && OD % 2 == 0 ? 2 : 1};
 }
 
-// Conv3d(1 -> Cout <= 64) input gradient = ConvTranspose3d(Cout -> 1) forward through the plane-streaming kernel; optionally with
-// the input transform act_in(dy * in_scale[c] + in_shift[c]) folded into the loads (in_act: none / LeakyReLU / ReLU).
-int edge_dgrad_stream_try(const float* dy, const float* w, const float* bias, float* dx, int batch, int Cin, int Cin_total,
-                          const ConvGeom& g, int Cout, int act, float slope, hipStream_t stream, const float* in_scale,
-                          const float* in_shift, int in_act, float in_slope, int samples_per_group, long out_group_stride, int form) {
+// Conv3d(1 -> Cout <= 64) input gradient = ConvTranspose3d(Cout -> 1) forward through the plane-walk kernels (round 4).
+EdgeDgradPlan edge_dgrad_walk_plan(int form, int batch, int Cin, int Cout, const ConvGeom& g) {
+    EdgeDgradPlan p = EdgeDgradPlan();
+    if (Cin != 1 || Cout > 64 || g.OH * g.OW > 256 || (size_t)g.Cy * g.O3() * 4 >= (size_t)kBufRange) return p;
+    if (form == 3 || form == 4) return p;      // retired forms
+    const ConvTPlan walk = convT_plan(form, batch, g.OD);
+    const unsigned padded = (unsigned)((batch + 7) / 8 * 8);      // (whole rounds of the eight XCDs)
+    const int tap_rows = walk.all_taps ? ConvTAllTaps::kTapRows : ConvTOnePair::kTapRows;
+    p.served = true;
+    p.kernel = walk.all_taps ? EdgeDgradKernel::walk_all_taps : EdgeDgradKernel::walk_one_pair;
+    p.grid = dim3(walk.all_taps ? padded * walk.splits : padded * 4 * walk.splits);
+    p.block = 512;
+    p.lds = (size_t)2 * tap_rows * ((g.OH * g.OW + 31) / 32 * 32 + 4) * sizeof(float);      // [2 buffers][tap rows][stride]
+    p.splits = walk.splits;
+    return p;
+}
+
+// The plane-walk kernels run four workgroups per sample for the whole depth of the grid: below ~48 samples they leave CUs idle and
+// the one-workgroup-per-plane kernel is faster — 17.8 vs 22.6 us at 32 samples, 32.0 vs 22.7 at 64, 114 vs 92 at 256
+constexpr int kConvTWalkMinBatch = 48;
+
+// Conv3d(1 -> Cout <= 64) input gradient = ConvTranspose3d(Cout -> 1) forward: dx [batch][Cx][I3] (channel 0 written).
+// workspace_need (the tap planes of the last resort) is set for every Cin == 1, Cout <= 64 shape, whichever kernel serves it.
+EdgeDgradPlan edge_dgrad_plan(int batch, int Cin, int Cout, const ConvGeom& g, size_t workspace_bytes) {
+    EdgeDgradPlan p = EdgeDgradPlan();
     const long O3 = g.O3();
-    if (Cin != 1 || Cout > 64 || g.OH * g.OW > 256 || (size_t)g.Cy * O3 * 4 >= (size_t)kBufRange) return 0;
-    const bool pre = in_scale != nullptr;
-    if (pre && (!in_shift || (in_act != SG_ACT_NONE && in_act != SG_ACT_LEAKY && in_act != SG_ACT_RELU) ||
-                (in_act == SG_ACT_LEAKY && (in_slope < 0.f || in_slope > 1.f))))
-        return 0;
-    if (form == 3 || form == 4) return 0;      // retired forms
+    if (Cin != 1 || Cout > 64) return p;
+    if (g.OH * g.OW <= 256 && (long)batch * O3 >= 512) {
+        if (batch >= kConvTWalkMinBatch) p = edge_dgrad_walk_plan(0, batch, Cin, Cout, g);
+        // per-plane kernel: a whole (OH x OW) plane of the four tap groups fits in LDS
+        if (!p.served && (size_t)g.Cy * O3 * 4 < (size_t)kBufRange) {
+            p.served = true;
+            p.kernel = EdgeDgradKernel::plane_fused;
+            p.grid = dim3((unsigned)((batch + 7) / 8 * 8 * g.OD));
+            p.block = 512;
+            p.lds = (size_t)(2 * kFusedGroup + 64 * kFusedWStride) * sizeof(float);
+        }
+    }
+    p.workspace_need = (size_t)batch * 64 * O3 * sizeof(float);
+    if (p.served) return p;
+    if (O3 % 32 != 0) return p;
+    if ((long)batch * O3 < 65536) return p;
+    if (workspace_bytes < p.workspace_need) return p;
+    if ((size_t)batch * 64 * O3 * 4 >= (size_t)kBufRange || (size_t)batch * g.Cy * O3 * 4 >= (size_t)kBufRange) return p;
+    const int wgs = (int)(batch * (O3 / 32) + 3) / 4;
+    p.served = true;
+    p.kernel = EdgeDgradKernel::tap_planes;      // tapplane_gemm_kernel, then col2im_c1_kernel
+    p.grid = dim3(wgs > 1024 ? 1024 : wgs);
+    p.block = 256;
+    return p;
+}
+
+static ConvTStreamArgs convT_stream_args(const EdgeDgradPlan& p, const float* dy, const float* w, const float* bias, float* dx,
+                                         int batch, int Cin_total, int Cout, const ConvGeom& g, int act, float slope,
+                                         const float* in_scale, const float* in_shift, int in_act, float in_slope,
+                                         int samples_per_group, long out_group_stride) {
     ConvTStreamArgs f;
     f.dy = dy;
     f.w = w;
@@ -1747,67 +1827,31 @@ int edge_dgrad_stream_try(const float* dy, const float* w, const float* bias, fl
     f.slope = slope;
     f.spg = samples_per_group > 0 ? samples_per_group : batch;
     f.out_group_stride = samples_per_group > 0 ? out_group_stride : (long)batch * f.dx_sample;
-    const ConvTPlan plan = convT_plan(form, batch, g.OD);
-    f.splits = plan.splits;
-    const unsigned padded = (unsigned)((batch + 7) / 8 * 8);      // (whole rounds of the eight XCDs)
-    if (plan.all_taps) convT_walk_launch<ConvTAllTaps>(f, pre, padded * plan.splits, stream);
-    else convT_walk_launch<ConvTOnePair>(f, pre, padded * 4 * plan.splits, stream);
-    return 1;
+    f.splits = p.splits;
+    return f;
 }
-
-// Conv3d(1 -> Cout <= 64) input gradient = ConvTranspose3d(Cout -> 1) forward: dx [batch][Cx][I3] (channel 0 written).
-int edge_dgrad_try(const float* dy, const float* w, const float* bias, float* dx, int batch, int Cin, int Cin_total,
-                   const ConvGeom& g, int Cout, int act, float slope, void* workspace, size_t workspace_bytes,
-                   hipStream_t stream, int force) {
-    const long O3 = g.O3();
-    if (Cin != 1 || Cout > 64) return 0;
-    // plane-streaming kernel (round 4); -DSG_NO_EDGE=16 builds restore the per-plane fused kernel below (A/B)
-    constexpr bool stream_off = (SG_NO_EDGE & 16) != 0;
-    // (the streaming kernel runs four workgroups per sample for the whole depth of the grid: below ~48 samples it leaves CUs
-    // idle and the one-workgroup-per-plane kernel is faster — 17.8 vs 22.6 us at 32 samples, 32.0 vs 22.7 at 64, 114 vs 92 at 256)
-    constexpr int stream_min_batch = SG_CONVT_MIN_BATCH;
-    if (!stream_off && g.OH * g.OW <= 256 && (force || (long)batch * O3 >= 512) && batch >= stream_min_batch &&
-        edge_dgrad_stream_try(dy, w, bias, dx, batch, Cin, Cin_total, g, Cout, act, slope, stream, nullptr, nullptr, 0, 0.f, 0, 0) == 1)
-        return 1;
-    // fused kernel: a whole (OH x OW) plane of the four tap groups fits in LDS
-    constexpr bool fused_off = (SG_NO_EDGE & 8) != 0;
-    if (!fused_off && g.OH * g.OW <= 256 && (size_t)g.Cy * O3 * 4 < (size_t)kBufRange && (force || (long)batch * O3 >= 512)) {
-        ConvTFusedArgs f;
-        f.dy = dy;
-        f.w = w;
-        f.bias = bias;
-        f.dx = dx;
-        f.Cout = Cout;
-        f.Cy = g.Cy;
-        f.Cin_total = Cin_total;
-        f.OD = g.OD;
-        f.OH = g.OH;
-        f.OW = g.OW;
-        f.P2 = g.OH * g.OW;
-        f.dx_sample = (long)g.Cx * g.I3();
-        f.batch = batch;
-        f.act = act;
-        f.slope = slope;
-        const size_t lds = (size_t)(2 * kFusedGroup + 64 * kFusedWStride) * sizeof(float);
-        static SgPerDeviceOnce attr_once;   // > 48 KB of dynamic LDS needs the attribute once per DEVICE
-        if (attr_once.begin()) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(convT_c1_fused_kernel<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(convT_c1_fused_kernel<false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_once.end();
-        }
-        const unsigned wgs = (unsigned)((batch + 7) / 8 * 8 * g.OD);
-        if (Cout == 64)
-            hipLaunchKernelGGL((convT_c1_fused_kernel<true>), dim3(wgs), dim3(512), lds, stream, f);
-        else
-            hipLaunchKernelGGL((convT_c1_fused_kernel<false>), dim3(wgs), dim3(512), lds, stream, f);
-        return 1;
-    }
-    if (O3 % 32 != 0) return 0;
-    if (!force && (long)batch * O3 < 65536) return 0;
-    if (!workspace || workspace_bytes < edge_dgrad_workspace_bytes(batch, g.OD, g.OH, g.OW)) return 0;
-    if ((size_t)batch * 64 * O3 * 4 >= (size_t)kBufRange || (size_t)batch * g.Cy * O3 * 4 >= (size_t)kBufRange) return 0;
+static ConvTFusedArgs convT_fused_args(const float* dy, const float* w, const float* bias, float* dx, int batch, int Cin_total,
+                                       int Cout, const ConvGeom& g, int act, float slope) {
+    ConvTFusedArgs f;
+    f.dy = dy;
+    f.w = w;
+    f.bias = bias;
+    f.dx = dx;
+    f.Cout = Cout;
+    f.Cy = g.Cy;
+    f.Cin_total = Cin_total;
+    f.OD = g.OD;
+    f.OH = g.OH;
+    f.OW = g.OW;
+    f.P2 = g.OH * g.OW;
+    f.dx_sample = (long)g.Cx * g.I3();
+    f.batch = batch;
+    f.act = act;
+    f.slope = slope;
+    return f;
+}
+static TapPlaneArgs tap_plane_args(const float* dy, const float* w, int batch, int Cin_total, int Cout, const ConvGeom& g,
+                                   void* workspace) {
     TapPlaneArgs a;
     a.dy = dy;
     a.w = w;
@@ -1815,22 +1859,56 @@ int edge_dgrad_try(const float* dy, const float* w, const float* bias, float* dx
     a.Cout = Cout;
     a.Cy = g.Cy;
     a.Cin_total = Cin_total;
-    a.O3 = (unsigned)O3;
-    a.tiles_per_sample = (int)(O3 / 32);
+    a.O3 = (unsigned)g.O3();
+    a.tiles_per_sample = (int)(g.O3() / 32);
     a.total_tiles = batch * a.tiles_per_sample;
     a.dtps = FastDiv((uint32_t)a.tiles_per_sample);
-    int wgs = (a.total_tiles + 3) / 4;
-    if (wgs > 1024) wgs = 1024;
-    if (Cout <= 16)
-        hipLaunchKernelGGL((tapplane_gemm_kernel<8>), dim3(wgs), dim3(256), 0, stream, a);
-    else if (Cout <= 32)
-        hipLaunchKernelGGL((tapplane_gemm_kernel<16>), dim3(wgs), dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL((tapplane_gemm_kernel<32>), dim3(wgs), dim3(256), 0, stream, a);
-    const int total = (int)((long)batch * O3);
-    hipLaunchKernelGGL(col2im_c1_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, (const float*)workspace, bias, dx, g,
-                       (long)g.Cx * g.I3(), total, act, slope);
-    return 1;
+    return a;
 }
+
+void edge_dgrad_launch(const EdgeDgradPlan& p, const float* dy, const float* w, const float* bias, float* dx, int batch, int Cin_total,
+                       int Cout, const ConvGeom& g, int act, float slope, void* workspace, hipStream_t stream, const float* in_scale,
+                       const float* in_shift, int in_act, float in_slope, int samples_per_group, long out_group_stride) {
+    switch (p.kernel) {
+    case EdgeDgradKernel::walk_all_taps:
+    case EdgeDgradKernel::walk_one_pair: {
+        const ConvTStreamArgs f = convT_stream_args(p, dy, w, bias, dx, batch, Cin_total, Cout, g, act, slope, in_scale, in_shift, in_act,
+                                                    in_slope, samples_per_group, out_group_stride);
+        if (p.kernel == EdgeDgradKernel::walk_all_taps) convT_walk_launch<ConvTAllTaps>(p, f, in_scale != nullptr, stream);
+        else convT_walk_launch<ConvTOnePair>(p, f, in_scale != nullptr, stream);
+        break;
+    }
+    case EdgeDgradKernel::plane_fused: {
+        static SgPerDeviceOnce attr_once;   // > 48 KB of dynamic LDS needs the attribute once per DEVICE
+        if (attr_once.begin()) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(convT_c1_fused_kernel<true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(convT_c1_fused_kernel<false>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+            attr_once.end();
+        }
+        const ConvTFusedArgs f = convT_fused_args(dy, w, bias, dx, batch, Cin_total, Cout, g, act, slope);
+        if (Cout == 64)
+            hipLaunchKernelGGL((convT_c1_fused_kernel<true>), p.grid, dim3(p.block), p.lds, stream, f);
+        else
+            hipLaunchKernelGGL((convT_c1_fused_kernel<false>), p.grid, dim3(p.block), p.lds, stream, f);
+        break;
+    }
+    case EdgeDgradKernel::tap_planes: {
+        const TapPlaneArgs a = tap_plane_args(dy, w, batch, Cin_total, Cout, g, workspace);
+        if (Cout <= 16)
+            hipLaunchKernelGGL((tapplane_gemm_kernel<8>), p.grid, dim3(p.block), 0, stream, a);
+        else if (Cout <= 32)
+            hipLaunchKernelGGL((tapplane_gemm_kernel<16>), p.grid, dim3(p.block), 0, stream, a);
+        else
+            hipLaunchKernelGGL((tapplane_gemm_kernel<32>), p.grid, dim3(p.block), 0, stream, a);
+        const int total = (int)((long)batch * g.O3());
+        hipLaunchKernelGGL(col2im_c1_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, (const float*)workspace, bias, dx, g,
+                           (long)g.Cx * g.I3(), total, act, slope);
+        break;
+    }
+    }
+}
+
 
 }  // namespace sg

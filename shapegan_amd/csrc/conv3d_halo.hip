@@ -616,100 +616,76 @@ __global__ void __launch_bounds__(512) conv_fwd_halo4_dskip_kernel(HaloFwdArgs a
 
 size_t halo_fwd_workspace_bytes(int Cin, int Cout) { return (size_t)((Cout + 127) / 128) * 128 * Cin * 64 * sizeof(float); }
 
-// Which form serves an 8^3 -> 4^3 forward (pure host logic).  Forced calls (tests, A/B): debug bit 8 asks for the depth-skip form,
-// without it they get conv_fwd_halo4_kernel.  The dispatch takes the depth-skip form wherever the input channels are not split over
-// workgroups (csplit > 1: small batches) — measured faster at 64 and 128 samples.
-bool halo_fwd4_dskip_chosen(int csplit, int force, int debug) {
-    if (debug & 256) return csplit == 1;
-    return !force && csplit == 1;
+HaloFwdForm halo_fwd_form_decode(int debug) {
+    HaloFwdForm f;
+    f.forced = true;
+    f.variant = (debug >> 4) & 3;
+    f.keep_lds = (debug & 64) != 0;
+    f.keep_rows128 = (debug & 128) != 0;
+    f.dskip = (debug & 256) != 0;
+    return f;
 }
 
-int halo_fwd_try(const float* x, const float* w, const float* bias, float* y, int batch, int Cin, int Cin_total,
-                 const ConvGeom& g, int Cout, int act, float slope, void* workspace, size_t workspace_bytes,
-                 hipStream_t stream, int force, int debug, bool packed_already, PackJobs* collect) {
-    // 4^3 outputs: the whole-sample box kernel (8-channel stages, 64-row tiles)
-    if (g.OD == 4 && g.OH == 4 && g.OW == 4) {
-        if (Cin % k4CC != 0 || Cin < 2 * k4CC || Cout < 32) return 0;
-        if (!workspace || workspace_bytes < halo_fwd_workspace_bytes(Cin, Cout)) return 0;
-        if ((long)g.Cx * 512 * 4 >= (long)kBufRange || (long)Cin * 8 * 1024 >= (long)kBufRange || batch > 65535 * 16) return 0;
-        const int mtiles = sg_cdiv(Cout, 64);
-        // (one round of workgroups costs ~130 us at 128 -> 256 channels whatever its size; the split-K gather kernel is faster
-        // below ~160 of them: 113 vs 132 us at 32 samples, 195 vs 129 us at 48 — scripts/small_batch_ab2.py, round 4)
-        // Below that, the input channels are split over 2 - 8 workgroups per (sample, row tile) that write partial sums (finished by
-        // the caller with the gather kernel's split-K finalize: return code 16 + csplit): 256 workgroups of 4+ stages each
-        int csplit = 1;
-        if (!force && (long)batch * mtiles < 160) {
-            while (csplit < 8 && (long)batch * mtiles * csplit < 256 && (Cin / (2 * csplit)) % k4CC == 0 && Cin / (2 * csplit) >= 2 * k4CC)
-                csplit *= 2;
-            if (csplit == 1) return 0;
-            if (workspace_bytes < halo_fwd_workspace_bytes(Cin, Cout) + (size_t)csplit * Cout * batch * 64 * sizeof(float)) return 0;
-        }
-        // depth-skip form (conv_fwd_halo4_dskip_kernel) or conv_fwd_halo4_kernel: they read different weight images (job kinds 2, 0)
-        const bool dskip = halo_fwd4_dskip_chosen(csplit, force, debug);
-        if ((debug & 256) && !dskip) return 0;
-        float4* wp = (float4*)workspace;
-        const int ntile = mtiles * 2;
-        const long total = (long)ntile * Cin * 8 * 64;
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        if (collect) return collect->add(dskip ? 2 : 0, w, wp, Cout, Cin_total, Cin, ntile);
-        if (!packed_already)
-            hipLaunchKernelGGL(pack_fwd_weights_kernel, dim3(blocks), dim3(256), 0, stream, w, wp, Cout, Cin_total, Cin, ntile,
-                               dskip ? 1 : 0);
-        HaloFwdArgs a;
-        a.x = x;
-        a.wp = wp;
-        a.bias = bias;
-        a.y = y;
-        a.g = g;
-        a.Cin = Cin;
-        a.Cout = Cout;
-        a.nth = a.ntw = 1;
-        a.dntw = a.dnth = a.dOD = FastDiv(1);
-        a.act = act;
-        a.slope = slope;
-        a.csplit = csplit;
-        a.partial = reinterpret_cast<float*>(static_cast<char*>(workspace) + halo_fwd_workspace_bytes(Cin, Cout));
-        a.npos = (long)batch * 64;
-        const size_t lds4 = (size_t)2 * k4BUF * sizeof(float);   // 66.5 KB: above the default dynamic-LDS limit
-        static SgPerDeviceOnce attr_once;   // > 48 KB of dynamic LDS needs the attribute once per DEVICE
-        if (attr_once.begin()) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_halo4_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
-            attr_once.end();
-        }
-        if (dskip) {
-            const size_t lds4s = (size_t)2 * k4sBUF * sizeof(float);   // 75 KB
-            static SgPerDeviceOnce attr_once_s;
-            if (attr_once_s.begin()) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_halo4_dskip_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4s);
-                attr_once_s.end();
-            }
-            hipLaunchKernelGGL(conv_fwd_halo4_dskip_kernel, dim3((unsigned)batch, mtiles), dim3(512), lds4s, stream, a);
-            return 1;
-        }
-        hipLaunchKernelGGL(conv_fwd_halo4_kernel, dim3((unsigned)batch, mtiles, csplit), dim3(512), lds4, stream, a);
-        return csplit > 1 ? 16 + csplit : 1;
+// 4^3 outputs: the whole-sample box kernel (8-channel stages, 64-row tiles)
+static HaloFwdPlan halo_fwd4_plan(int batch, int Cin, int Cout, const ConvGeom& g, size_t workspace_bytes, const HaloFwdForm& form) {
+    HaloFwdPlan p = HaloFwdPlan();
+    const size_t image_bytes = halo_fwd_workspace_bytes(Cin, Cout);
+    if (Cin % k4CC != 0 || Cin < 2 * k4CC || Cout < 32) return p;
+    if (workspace_bytes < image_bytes) return p;
+    if ((long)g.Cx * 512 * 4 >= (long)kBufRange || (long)Cin * 8 * 1024 >= (long)kBufRange || batch > 65535 * 16) return p;
+    const int mtiles = sg_cdiv(Cout, 64);
+    // (one round of workgroups costs ~130 us at 128 -> 256 channels whatever its size; the split-K gather kernel is faster
+    // below ~160 of them: 113 vs 132 us at 32 samples, 195 vs 129 us at 48 — scripts/small_batch_ab2.py, round 4)
+    // Below that, the input channels are split over 2 - 8 workgroups per (sample, row tile) that write partial sums behind the image
+    // (finished by the caller with the gather kernel's split-K finalize): 256 workgroups of 4+ stages each
+    int csplit = 1;
+    if (!form.forced && (long)batch * mtiles < 160) {
+        while (csplit < kHaloFwd4MaxSplit && (long)batch * mtiles * csplit < 256 && (Cin / (2 * csplit)) % k4CC == 0 &&
+               Cin / (2 * csplit) >= 2 * k4CC)
+            csplit *= 2;
+        if (csplit == 1) return p;
+        if (workspace_bytes < image_bytes + (size_t)csplit * Cout * batch * 64 * sizeof(float)) return p;
     }
-    if (debug & 256) return 0;   // the depth-skip form exists for 4^3 outputs only
+    // Depth-skip form (conv_fwd_halo4_dskip_kernel) or conv_fwd_halo4_kernel: they read different weight images (job kinds 2, 0).
+    // Forced calls (tests, A/B) get the depth-skip form only where they ask for it.  The dispatch takes it wherever the input channels
+    // are not split over workgroups (csplit > 1: small batches) — measured faster at 64 and 128 samples.
+    const bool dskip = (form.dskip || !form.forced) && csplit == 1;
+    if (form.dskip && !dskip) return p;
+    p.served = true;
+    p.kernel = dskip ? HaloFwdKernel::halo4_dskip : HaloFwdKernel::halo4;
+    p.grid = dskip ? dim3((unsigned)batch, mtiles) : dim3((unsigned)batch, mtiles, csplit);
+    p.block = 512;
+    p.lds = dskip ? (size_t)2 * k4sBUF * sizeof(float)      // 75 KB
+                  : (size_t)2 * k4BUF * sizeof(float);      // 66.5 KB: both above the default dynamic-LDS limit
+    p.image = ImageJob{dskip ? 2 : 0, mtiles * 2, 0};
+    p.nth = p.ntw = 1;
+    p.csplit = csplit;
+    p.partial_offset = image_bytes;
+    p.workspace_need = image_bytes + (csplit > 1 ? (size_t)csplit * Cout * batch * 64 * sizeof(float) : 0);
+    return p;
+}
+
+HaloFwdPlan halo_fwd_plan(int batch, int Cin, int Cout, const ConvGeom& g, size_t workspace_bytes, HaloFwdForm form) {
+    if (g.OD == 4 && g.OH == 4 && g.OW == 4) return halo_fwd4_plan(batch, Cin, Cout, g, workspace_bytes, form);
+    HaloFwdPlan p = HaloFwdPlan();
+    if (form.dskip) return p;   // the depth-skip form exists for 4^3 outputs only
     // eligible: 8x8 position tiles exist, whole stages of 4 channels, enough output channels to fill 64-row MFMA tiles
-    if (g.OW % 8 != 0 || g.OH % 8 != 0 || Cin % kCC != 0 || Cin < 8 || Cout < 32) return 0;
-    if ((long)g.Cx * g.ID * g.IH * g.IW * 4 >= (long)kBufRange || (long)Cin * 8 * 1024 >= (long)kBufRange) return 0;
-    if (!workspace || workspace_bytes < halo_fwd_workspace_bytes(Cin, Cout)) return 0;
-    if ((long)batch * g.Cx * g.ID * g.IH * g.IW >= (1L << 31)) return 0;
+    if (g.OW % 8 != 0 || g.OH % 8 != 0 || Cin % kCC != 0 || Cin < 8 || Cout < 32) return p;
+    if ((long)g.Cx * g.ID * g.IH * g.IW * 4 >= (long)kBufRange || (long)Cin * 8 * 1024 >= (long)kBufRange) return p;
+    if (workspace_bytes < halo_fwd_workspace_bytes(Cin, Cout)) return p;
+    if ((long)batch * g.Cx * g.ID * g.IH * g.IW >= (1L << 31)) return p;
     // configuration: 128 output channels per workgroup as 8 waves x 1 tile (variant 0, more waves per SIMD to hide the
     // copy / weight-load latency) or 4 waves x 2 tiles (variant 1); 64 channels as 4 waves x 1 tile
     // measured (scripts/halo_bench.py of rounds 1-3: git history): 4 waves x 2 tiles wins below ~1024 workgroups, 8 waves x 1 tile above
-    int variant = (debug >> 4) & 3;
-    int rows = (Cout > 64 && ((debug >> 4) & 3) != 3) ? 128 : 64;   // variant 3: 64-row tiles, twice the workgroups
+    int variant = form.variant;
+    int rows = (Cout > 64 && variant != 3) ? 128 : 64;   // variant 3: 64-row tiles, twice the workgroups
     const int ntw = g.OW / 8, nth = g.OH / 8;
     const long tiles = (long)batch * g.OD * nth * ntw;
     // Small grids (round 4, scripts/small_batch_ab2.py; the critics of the hybrid GANs see 16 - 32 samples): a round of <= 256
     // workgroups costs the same whatever its size (64 -> 128 channels at 16^3: ~125 us with 128-row tiles, ~70 us with 64-row
     // tiles), so with 128-row tiles at most half a round (W <= 128) or just over one (256 < W <= 384) the 64-row tiles are chosen:
     // 16 samples 125 -> 71 us (the gather kernel: 104), 40 samples 238 -> 186 us.  Same weight image (row tiles of 32).
-    if (rows == 128 && variant == 0 && !(debug & 128)) {
+    if (rows == 128 && variant == 0 && !form.keep_rows128) {
         const long w128 = tiles * sg_cdiv(Cout, 128);
         if (w128 <= 128 || (w128 > 256 && w128 <= 384)) rows = 64;
     }
@@ -717,48 +693,94 @@ int halo_fwd_try(const float* x, const float* w, const float* bias, float* y, in
     // auto-dispatch only where it wins (A/B on MI355X): from three quarters of a round of workgroups on; below that the
     // split-K gather kernel is faster (8 samples at 64 -> 128 channels, 16^3: 63 vs 70 us; 12 samples: 103 vs 70 us; with 128-row
     // tiles, 20 samples = 160 workgroups: 126 vs 156 us)
-    if (!force && tiles * mtiles < (rows == 128 ? 144 : 192)) return 0;
-    if (tiles >= (1L << 31)) return 0;
+    if (!form.forced && tiles * mtiles < (rows == 128 ? 144 : 192)) return p;
+    if (tiles >= (1L << 31)) return p;
     if (variant == 0) variant = 2;   // 1 = 4 waves x (32 rows x 64 positions), 2 = 8 waves x (32 x 32): measured 143-146 vs 139-143 TF
-    size_t lds = (size_t)2 * kCC * kHS * sizeof(float);
+    p.lds = (size_t)2 * kCC * kHS * sizeof(float);
     // Registers and LDS would admit 3 workgroups per CU; with fewer than ~4 rounds of workgroups that leaves a mostly
-    // idle last round (1024 workgroups: 768 + 256), so ask for enough LDS to cap the CU at 2 (debug bit 6: don't)
-    if (tiles * mtiles < 256 * 3 * 4 && !(debug & 64) && lds < 56 * 1024) lds = 56 * 1024;
+    // idle last round (1024 workgroups: 768 + 256), so ask for enough LDS to cap the CU at 2 (form.keep_lds: don't)
+    if (tiles * mtiles < 256 * 3 * 4 && !form.keep_lds && p.lds < 56 * 1024) p.lds = 56 * 1024;
+    p.served = true;
+    p.kernel = rows == 64 ? HaloFwdKernel::rows64 : (variant == 2 ? HaloFwdKernel::rows128_w8 : HaloFwdKernel::rows128_w4);
+    p.grid = dim3((unsigned)tiles, mtiles);
+    p.block = p.kernel == HaloFwdKernel::rows128_w8 ? 512 : 256;
+    p.image = ImageJob{0, mtiles * rows / 32, 0};  // every row tile a workgroup may touch exists (zero rows beyond Cout)
+    p.nth = nth;
+    p.ntw = ntw;
+    p.csplit = 1;
+    p.partial_offset = p.workspace_need = halo_fwd_workspace_bytes(Cin, Cout);
+    return p;
+}
 
-    float4* wp = (float4*)workspace;
-    {
-        const int ntile = mtiles * rows / 32;  // every row tile a workgroup may touch exists (zero rows beyond Cout)
-        const long total = (long)ntile * Cin * 8 * 64;
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        if (collect) return collect->add(0, w, wp, Cout, Cin_total, Cin, ntile);
-        if (!packed_already)
-            hipLaunchKernelGGL(pack_fwd_weights_kernel, dim3(blocks), dim3(256), 0, stream, w, wp, Cout, Cin_total, Cin, ntile, 0);
-    }
+void halo_fwd_pack(const HaloFwdPlan& p, const float* w, int Cin, int Cin_total, int Cout, void* workspace, hipStream_t stream) {
+    const long total = (long)p.image.nt * Cin * 8 * 64;
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(pack_fwd_weights_kernel, dim3(blocks), dim3(256), 0, stream, w, workspace_at<float4>(workspace, p.image.offset), Cout,
+                       Cin_total, Cin, p.image.nt, p.image.kind >> 1);
+}
+
+static HaloFwdArgs halo_fwd_args(const HaloFwdPlan& p, const float* x, const float* bias, float* y, int batch, int Cin, int Cout,
+                                 const ConvGeom& g, int act, float slope, void* workspace) {
+    const bool box4 = p.kernel == HaloFwdKernel::halo4 || p.kernel == HaloFwdKernel::halo4_dskip;
     HaloFwdArgs a;
     a.x = x;
-    a.wp = wp;
+    a.wp = workspace_at<float4>(workspace, p.image.offset);
     a.bias = bias;
     a.y = y;
     a.g = g;
     a.Cin = Cin;
     a.Cout = Cout;
-    a.nth = nth;
-    a.ntw = ntw;
-    a.dntw = FastDiv(ntw);
-    a.dnth = FastDiv(nth);
-    a.dOD = FastDiv(g.OD);
+    a.nth = p.nth;
+    a.ntw = p.ntw;
+    a.dntw = FastDiv(p.ntw);
+    a.dnth = FastDiv(p.nth);
+    a.dOD = FastDiv(box4 ? 1 : g.OD);
     a.act = act;
     a.slope = slope;
-    dim3 grid((unsigned)tiles, mtiles);
-    if (rows == 128 && variant == 2)
-        hipLaunchKernelGGL((conv_fwd_halo_kernel<1, 8>), grid, dim3(512), lds, stream, a);
-    else if (rows == 128)
-        hipLaunchKernelGGL((conv_fwd_halo_kernel<2, 4>), grid, dim3(256), lds, stream, a);
-    else
-        hipLaunchKernelGGL((conv_fwd_halo_kernel<1, 4>), grid, dim3(256), lds, stream, a);
-    return 1;
+    a.csplit = p.csplit;
+    a.partial = workspace_at<float>(workspace, p.partial_offset);
+    a.npos = (long)batch * g.O3();
+    return a;
 }
+
+void halo_fwd_launch(const HaloFwdPlan& p, const float* x, const float* bias, float* y, int batch, int Cin, int Cout, const ConvGeom& g,
+                     int act, float slope, void* workspace, hipStream_t stream) {
+    const HaloFwdArgs a = halo_fwd_args(p, x, bias, y, batch, Cin, Cout, g, act, slope, workspace);
+    if (p.kernel == HaloFwdKernel::halo4 || p.kernel == HaloFwdKernel::halo4_dskip) {
+        static SgPerDeviceOnce attr_once;   // > 48 KB of dynamic LDS needs the attribute once per DEVICE
+        if (attr_once.begin()) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_halo4_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)2 * k4BUF * sizeof(float)));
+            attr_once.end();
+        }
+    }
+    switch (p.kernel) {
+    case HaloFwdKernel::halo4_dskip: {
+        static SgPerDeviceOnce attr_once_s;
+        if (attr_once_s.begin()) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_halo4_dskip_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+            attr_once_s.end();
+        }
+        hipLaunchKernelGGL(conv_fwd_halo4_dskip_kernel, p.grid, dim3(p.block), p.lds, stream, a);
+        break;
+    }
+    case HaloFwdKernel::halo4:
+        hipLaunchKernelGGL(conv_fwd_halo4_kernel, p.grid, dim3(p.block), p.lds, stream, a);
+        break;
+    case HaloFwdKernel::rows128_w8:
+        hipLaunchKernelGGL((conv_fwd_halo_kernel<1, 8>), p.grid, dim3(p.block), p.lds, stream, a);
+        break;
+    case HaloFwdKernel::rows128_w4:
+        hipLaunchKernelGGL((conv_fwd_halo_kernel<2, 4>), p.grid, dim3(p.block), p.lds, stream, a);
+        break;
+    case HaloFwdKernel::rows64:
+        hipLaunchKernelGGL((conv_fwd_halo_kernel<1, 4>), p.grid, dim3(p.block), p.lds, stream, a);
+        break;
+    }
+}
+
 
 
 // ================================================================================================================
@@ -831,9 +853,9 @@ __global__ void __launch_bounds__(256) pack_dgrad_frag_kernel(const float* __res
 
 // ---- several weight images in ONE launch ------------------------------------------------------------------------------------
 // A critic update packs four images of two weights (forward and input-gradient form each), one launch of 5 - 7 us apiece: 0.19 ms
-// of the 16.8 ms WGAN step in thirty launches.  sg_conv3d_k4s2p1_pack_images (conv3d.hip) runs halo_fwd_try / halo_dgrad_try in
-// COLLECT mode — they plan exactly as for a real call and hand their packing job to the collector instead of launching it — and
-// this kernel does all collected jobs at once (grid y = job); the convolutions that follow are told their image is in place.
+// of the 16.8 ms WGAN step in thirty launches.  sg_conv3d_k4s2p1_pack_images (conv3d.hip) takes the image jobs of
+// halo_fwd_plan / halo_dgrad_plan — the plans the calls themselves will make — and this kernel does all of them at once
+// (grid y = job); the convolutions that follow are told their image is in place.
 // Job kinds: 0 / 2 forward image mode 0 / 1, 1 / 3 input-gradient image mode 0 / 1.
 __global__ void __launch_bounds__(256) pack_images_kernel(PackJobs jobs) {
     const PackJob& j = jobs.job[blockIdx.y];
@@ -1371,90 +1393,119 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) c
 
 size_t halo_dgrad_workspace_bytes(int Cin, int Cout) { return (size_t)8 * ((Cin + 63) / 64) * 64 * Cout * 8 * sizeof(float); }
 
-// Which form serves a 4^3 -> 8^3 input gradient with 64-row workgroups (pure host logic).  Forced calls (tests, A/B): force bit 6
-// asks for the depth-skip form, without it they get conv_dgrad_halo_kernel<1>.  The dispatch takes the depth-skip form for every
-// 64-row 4^3 call — measured faster at 64, 128 and 256 samples.  Other grids and the 32-row workgroups
-// have no depth-skip form.
-bool halo_dgrad_dskip_chosen(bool mode1, bool r32, int force) {
-    if (!mode1 || r32) return false;
-    return !force || (force & 64);
+bool halo_dgrad_form_decode(int impl, HaloDgradForm* form) {
+    form->forced = (impl & 1) != 0;
+    form->one_parity = (impl & 2) != 0;
+    form->ppw = (impl >> 2) & 15;
+    form->rows64_dskip = (impl & 64) != 0;
+    return (impl & ~127) == 0;
 }
 
-int halo_dgrad_try(const float* dy, const float* w, const float* bias, float* dx, int batch, int Cin, int Cin_total,
-                   const ConvGeom& g, int Cout, int act, float slope, void* workspace, size_t workspace_bytes,
-                   hipStream_t stream, int force, bool packed_already, PackJobs* collect) {
+HaloDgradPlan halo_dgrad_plan(int batch, int Cin, int Cout, const ConvGeom& g, size_t workspace_bytes, HaloDgradForm form) {
+    HaloDgradPlan p = HaloDgradPlan();
     const bool mode1 = g.OD == 4 && g.OH == 4 && g.OW == 4;
-    if (!mode1 && (g.OW % 8 != 0 || g.OH % 8 != 0 || g.OD % 2 != 0)) return 0;
-    if (Cout % 16 != 0 || Cin < 32 || Cin % 8 != 0) return 0;
-    if (((long)2 * g.Cy * g.OD * g.OH * g.OW + (long)(g.OH + 1) * g.OW + 1) * 4 >= (1L << 26)) return 0;   // offset | class word
-    if (!workspace || workspace_bytes < halo_dgrad_workspace_bytes(Cin, Cout)) return 0;
-    if ((long)batch * g.Cy * g.OD * g.OH * g.OW >= (1L << 31)) return 0;
-    if ((long)2 * g.Cy * g.OD * g.OH * g.OW * 4 >= (long)kBufRange || (long)Cout * 1024 >= (long)kBufRange) return 0;
+    if (!mode1 && (g.OW % 8 != 0 || g.OH % 8 != 0 || g.OD % 2 != 0)) return p;
+    if (Cout % 16 != 0 || Cin < 32 || Cin % 8 != 0) return p;
+    if (((long)2 * g.Cy * g.OD * g.OH * g.OW + (long)(g.OH + 1) * g.OW + 1) * 4 >= (1L << 26)) return p;   // offset | class word
+    if (workspace_bytes < halo_dgrad_workspace_bytes(Cin, Cout)) return p;
+    if ((long)batch * g.Cy * g.OD * g.OH * g.OW >= (1L << 31)) return p;
+    if ((long)2 * g.Cy * g.OD * g.OH * g.OW * 4 >= (long)kBufRange || (long)Cout * 1024 >= (long)kBufRange) return p;
     const int ntw = mode1 ? 1 : g.OW / 8, nth = mode1 ? 1 : g.OH / 8, ntd = mode1 ? 1 : g.OD / 2;
     const long tiles = mode1 ? (batch + 1) / 2 : (long)batch * ntd * nth * ntw;
     const int mtiles = (Cin + 63) / 64;
     // (round 4, scripts/small_batch_ab2.py: the gather form of the input gradient is slow at every size — 256 -> 128 channels at
     // 4^3: 110 us at 2 .. 16 samples, 145 at 32, against 75 us for one round of this kernel; 128 -> 64 at 8^3: 59 - 75 us against 43)
-    if (!force && tiles * mtiles * 8 < (mode1 ? 16 : 64)) return 0;
-    if (tiles >= (1L << 31) || mtiles > 65535) return 0;
-    float4* wp = (float4*)workspace;
-    if ((long)8 * mtiles * 2 * Cout * 1024 >= (long)kBufRange) return 0;
-    // parities per workgroup: as many as keep >= 512 workgroups (2 per CU); force bit 1 (impl 3): one parity per workgroup
+    if (!form.forced && tiles * mtiles * 8 < (mode1 ? 16 : 64)) return p;
+    if (tiles >= (1L << 31) || mtiles > 65535) return p;
+    if ((long)8 * mtiles * 2 * Cout * 1024 >= (long)kBufRange) return p;
+    // parities per workgroup: as many as keep >= 512 workgroups (2 per CU); form.one_parity: one parity per workgroup
     int ppw = 8;
-    while (ppw > 1 && (tiles * mtiles * (8 / ppw) < 512 || (force & 2) || (Cout / 16) % 2 != 0)) ppw >>= 1;
-    if (((force >> 2) & 15) && (Cout / 16) % 2 == 0) ppw = (force >> 2) & 15;   // tests: impl = 1 + 4 * ppw forces 2, 4 or 8 parities
+    while (ppw > 1 && (tiles * mtiles * (8 / ppw) < 512 || form.one_parity || (Cout / 16) % 2 != 0)) ppw >>= 1;
+    if (form.ppw && (Cout / 16) % 2 == 0) ppw = form.ppw;   // tests force 2, 4 or 8 parities
     // 32-row workgroups (four waves, one column tile each): when only 32 rows of the tile exist (Cin <= 32), and when 64-row workgroups
     // would leave CUs without one (small batches: 128 workgroups at 16 samples of a 4^3 grid) — twice as many, half as long
-    const bool r32 = !(force & 64) && (Cin <= 32 || tiles * mtiles * (8 / ppw) < 256);   // (force bit 6: 64-row workgroups at any size)
-    // depth-skip form of the 4^3 64-row kernel (conv_dgrad_halo_dskip_kernel, its own weight image: job kind 3); force bit 6 asks
-    // for it (0 if the grid is not 4^3)
-    const bool dskip = halo_dgrad_dskip_chosen(mode1, r32, force);
-    if ((force & 64) && !dskip) return 0;
-    if (collect) return collect->add(dskip ? 3 : 1, w, wp, Cout, Cin_total, Cin, mtiles * 2);
-    if (!packed_already) {
-        const long total = 8L * mtiles * 2 * Cout * 64;
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(pack_dgrad_frag_kernel, dim3(blocks), dim3(256), 0, stream, w, wp, Cout, Cin_total, Cin, mtiles * 2,
-                           dskip ? 1 : 0);
+    const bool r32 = !form.rows64_dskip && (Cin <= 32 || tiles * mtiles * (8 / ppw) < 256);
+    // Depth-skip form of the 4^3 64-row kernel (conv_dgrad_halo_dskip_kernel, its own weight image: job kind 3).  Forced calls (tests,
+    // A/B) get it only where they ask for it, without that conv_dgrad_halo_kernel<1>.  The dispatch takes it for every 64-row 4^3
+    // call — measured faster at 64, 128 and 256 samples.  Other grids and the 32-row workgroups have no
+    // depth-skip form.
+    const bool dskip = mode1 && !r32 && (!form.forced || form.rows64_dskip);
+    if (form.rows64_dskip && !dskip) return p;
+    p.served = true;
+    p.kernel = dskip ? HaloDgradKernel::dskip4
+                     : (mode1 ? (r32 ? HaloDgradKernel::rows32_4 : HaloDgradKernel::rows64_4)
+                              : (r32 ? HaloDgradKernel::rows32 : HaloDgradKernel::rows64));
+    p.grid = dim3((unsigned)tiles, r32 ? (unsigned)((Cin + 31) / 32) : (unsigned)mtiles, 8 / ppw);
+    p.block = 256;
+    // registers admit 3 workgroups per CU; take 3 only when the grid then needs fewer CU-slots in total (a 2048-workgroup
+    // grid is 4 full rounds at 2 per CU but 2.67 rounds at 3): otherwise a larger LDS request caps the CU at 2
+    p.lds = (size_t)2 * 16 * 256 * sizeof(float);
+    {
+        const long wgs = tiles * mtiles * (8 / ppw);
+        const long cost2 = ((wgs + 511) / 512) * 2, cost3 = ((wgs + 767) / 768) * 3;
+        if (cost2 <= cost3) p.lds = 56 * 1024;
     }
+    p.image = ImageJob{dskip ? 3 : 1, mtiles * 2, 0};
+    p.workspace_need = halo_dgrad_workspace_bytes(Cin, Cout);
+    p.mtiles = mtiles;
+    p.ppw = ppw;
+    p.ntd = ntd;
+    p.nth = nth;
+    p.ntw = ntw;
+    return p;
+}
+
+void halo_dgrad_pack(const HaloDgradPlan& p, const float* w, int Cin, int Cin_total, int Cout, void* workspace, hipStream_t stream) {
+    const long total = 8L * p.image.nt * Cout * 64;
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(pack_dgrad_frag_kernel, dim3(blocks), dim3(256), 0, stream, w, workspace_at<float4>(workspace, p.image.offset), Cout,
+                       Cin_total, Cin, p.image.nt, p.image.kind >> 1);
+}
+
+static HaloDgradArgs halo_dgrad_args(const HaloDgradPlan& p, const float* dy, const float* bias, float* dx, int batch, int Cin, int Cout,
+                                     const ConvGeom& g, int act, float slope, void* workspace) {
     HaloDgradArgs a;
     a.dy = dy;
-    a.wp = wp;
+    a.wp = workspace_at<float4>(workspace, p.image.offset);
     a.bias = bias;
     a.dx = dx;
     a.g = g;
     a.Cin = Cin;
     a.Cout = Cout;
-    a.mtiles = mtiles;
+    a.mtiles = p.mtiles;
     a.batch = batch;
-    a.dntw = FastDiv(ntw);
-    a.dnth = FastDiv(nth);
-    a.dntd = FastDiv(ntd);
+    a.ppw = p.ppw;
+    a.dntw = FastDiv(p.ntw);
+    a.dnth = FastDiv(p.nth);
+    a.dntd = FastDiv(p.ntd);
     a.act = act;
     a.slope = slope;
-    a.ppw = ppw;
-    // registers admit 3 workgroups per CU; take 3 only when the grid then needs fewer CU-slots in total (a 2048-workgroup
-    // grid is 4 full rounds at 2 per CU but 2.67 rounds at 3): otherwise a larger LDS request caps the CU at 2
-    size_t lds = (size_t)2 * 16 * 256 * sizeof(float);
-    {
-        const long wgs = tiles * mtiles * (8 / ppw);
-        const long cost2 = ((wgs + 511) / 512) * 2, cost3 = ((wgs + 767) / 768) * 3;
-        if (cost2 <= cost3) lds = 56 * 1024;
-    }
-    const dim3 grid((unsigned)tiles, r32 ? (unsigned)((Cin + 31) / 32) : (unsigned)mtiles, 8 / ppw);
-    if (dskip)
-        hipLaunchKernelGGL(conv_dgrad_halo_dskip_kernel, grid, dim3(256), lds, stream, a);
-    else if (mode1 && r32)
-        hipLaunchKernelGGL((conv_dgrad_halo32_kernel<1>), grid, dim3(256), lds, stream, a);
-    else if (mode1)
-        hipLaunchKernelGGL((conv_dgrad_halo_kernel<1>), grid, dim3(256), lds, stream, a);
-    else if (r32)
-        hipLaunchKernelGGL((conv_dgrad_halo32_kernel<0>), grid, dim3(256), lds, stream, a);
-    else
-        hipLaunchKernelGGL((conv_dgrad_halo_kernel<0>), grid, dim3(256), lds, stream, a);
-    return 1;
+    return a;
 }
+
+void halo_dgrad_launch(const HaloDgradPlan& p, const float* dy, const float* bias, float* dx, int batch, int Cin, int Cout,
+                       const ConvGeom& g, int act, float slope, void* workspace, hipStream_t stream) {
+    const HaloDgradArgs a = halo_dgrad_args(p, dy, bias, dx, batch, Cin, Cout, g, act, slope, workspace);
+    switch (p.kernel) {
+    case HaloDgradKernel::dskip4:
+        hipLaunchKernelGGL(conv_dgrad_halo_dskip_kernel, p.grid, dim3(p.block), p.lds, stream, a);
+        break;
+    case HaloDgradKernel::rows32_4:
+        hipLaunchKernelGGL((conv_dgrad_halo32_kernel<1>), p.grid, dim3(p.block), p.lds, stream, a);
+        break;
+    case HaloDgradKernel::rows64_4:
+        hipLaunchKernelGGL((conv_dgrad_halo_kernel<1>), p.grid, dim3(p.block), p.lds, stream, a);
+        break;
+    case HaloDgradKernel::rows32:
+        hipLaunchKernelGGL((conv_dgrad_halo32_kernel<0>), p.grid, dim3(p.block), p.lds, stream, a);
+        break;
+    case HaloDgradKernel::rows64:
+        hipLaunchKernelGGL((conv_dgrad_halo_kernel<0>), p.grid, dim3(p.block), p.lds, stream, a);
+        break;
+    }
+}
+
 
 // ================================================================================================================
 // wgrad form (nn.Conv3d / nn.ConvTranspose3d weight gradient):
@@ -2045,41 +2096,55 @@ static void wgrad_halo_plan(int batch, const ConvGeom& g, int Cin, int Cout, int
     if (nsplit < 1) nsplit = 1;
 }
 
-size_t halo_wgrad_workspace_bytes(int batch, int Cin, int Cout, int OD, int OH, int OW) {
-    if ((OH % 8 != 0 || OW % 8 != 0) && !(OD == 4 && OH == 4 && OW == 4)) return 0;
-    ConvGeom g;
-    g.OD = OD;
-    g.OH = OH;
-    g.OW = OW;
-    int nslice, nsplit, mtiles;
-    g.ID = 2 * OD;       // (wgrad_mode4 / wgrad_rows64 look at the output grid only)
-    g.IH = 2 * OH;
-    g.IW = 2 * OW;
-    wgrad_halo_plan(batch, g, Cin, Cout, nslice, nsplit, mtiles);
-    const size_t pack = (size_t)mtiles * 4 * nslice * 8 * 64 * sizeof(float4);      // (rows64: 2 mtiles row tiles are used)
-    const size_t part = (size_t)nsplit * Cout * Cin * 64 * sizeof(float);
-    return pack + part + 256;
-}
-
 // ---- the packed dy image written by the kernel that PRODUCES dy ---------------------------------------------------------------------
 // pack_wgrad_dy(4)_kernel re-reads the incoming gradient of a layer right after the activation backward wrote it (67 MB each way at
 // the critic's second layer: 18 us, 0.15 ms per WGAN step with the 4^3 form).  When the halo weight-gradient kernel will serve the
 // call and the grid is 8^3 or 4^3 with Cout a multiple of 128 (no padded row tiles), the producer writes the image itself:
 // sg_act_bwd_rowsum_pack8 (activation backward + bias row sums + image, 8^3) and sg_head_dot_bwd (4^3), then
-// sg_conv3d_k4s2p1_wgrad_prepacked skips the packing launch.  halo_wgrad_dy_image_plan answers whether, and with which MT / nslice.
-int halo_wgrad_dy_image_plan(int batch, int Cin, int Cout, const ConvGeom& g, size_t workspace_bytes, int* mt_total, long* nslice_out) {
+// sg_conv3d_k4s2p1_wgrad_prepacked skips the packing launch.  HaloWgradPlan::producer_image answers whether; dy_image.nt and nslice
+// say with which MT / nslice.
+HaloWgradPlan halo_wgrad_plan(int batch, int Cin, int Cout, const ConvGeom& g, size_t workspace_bytes, bool forced) {
+    HaloWgradPlan p = HaloWgradPlan();
     const bool mode4 = wgrad_mode4(g);
-    if (!(mode4 || (g.OD == 8 && g.OH == 8 && g.OW == 8)) || Cout % 128 != 0 || Cin < 2) return 0;
-    if ((long)batch * g.Cx * g.ID * g.IH * g.IW >= (1L << 31) || (long)2 * g.ID * g.IH * g.IW * 4 >= (1L << 26)) return 0;
+    if ((!mode4 && (g.OW % 8 != 0 || g.OH % 8 != 0)) || Cin < 2 || Cout < 32) return p;
     int nslice, nsplit, mtiles;
     wgrad_halo_plan(batch, g, Cin, Cout, nslice, nsplit, mtiles);
-    const int ntiles = ((Cin + 1) / 2) * mtiles;
-    if (Cout <= 64 || (long)ntiles * nsplit < 384) return 0;      // (the auto-dispatch rule of halo_wgrad_try)
-    if (workspace_bytes < halo_wgrad_workspace_bytes(batch, Cin, Cout, g.OD, g.OH, g.OW)) return 0;
-    *mt_total = mtiles * 4;
-    *nslice_out = nslice;
-    return 1;
+    const size_t pack_bytes = (size_t)mtiles * 4 * nslice * 8 * 64 * sizeof(float4);      // (rows64: 2 mtiles row tiles are used)
+    p.workspace_need = pack_bytes + (size_t)nsplit * Cout * Cin * 64 * sizeof(float) + 256;
+    if ((long)batch * g.Cx * g.ID * g.IH * g.IW >= (1L << 31)) return p;
+    if ((long)2 * g.ID * g.IH * g.IW * 4 >= (1L << 26)) return p;   // box offset | edge-class word needs offsets below 2^26
+    const bool rows64 = wgrad_rows64(g, Cin, Cout);
+    if (rows64 && (long)4 * g.ID * g.IH * g.IW * 4 >= (1L << 26)) return p;
+    const int ntiles = (rows64 ? Cin / 4 : (Cin + 1) / 2) * mtiles;
+    // auto-dispatch where it wins (round-1 A/B): no half-empty row tiles (Cout <= 64: the 64-row form, round 6) and enough workgroups
+    if (!forced && ((Cout <= 64 && !rows64) || (long)ntiles * nsplit < 384)) return p;
+    if (workspace_bytes < p.workspace_need) return p;
+    p.served = true;
+    p.nslice = nslice;
+    p.per_split = (nslice + nsplit - 1) / nsplit;
+    p.nsplit = (nslice + p.per_split - 1) / p.per_split;
+    p.mtiles = mtiles;
+    p.dy_image = ImageJob{mode4 ? 1 : 0, rows64 ? mtiles * 2 : mtiles * 4, 0};
+    p.producer_image = !forced && (mode4 || (g.OD == 8 && g.OH == 8 && g.OW == 8)) && Cout % 128 == 0;
+    p.partial_offset = pack_bytes;
+    p.block = 256;
+    if (mode4) {
+        p.kernel = HaloWgradKernel::halo4;
+        p.grid = dim3((Cin + 1) / 2, mtiles, p.nsplit);
+        p.lds = (size_t)2 * 2 * kW4CH * sizeof(float);
+    } else if (rows64) {
+        p.kernel = HaloWgradKernel::rows64;
+        p.grid = dim3(Cin / 4, mtiles, p.nsplit);
+        p.lds = (size_t)2 * 4 * kWHS * sizeof(float);
+    } else {
+        // OH == 8: the 8x8 tile spans H, which rows of the box are padding is static -> the form that skips them
+        p.kernel = g.OH == 8 ? HaloWgradKernel::rows128_skip_h : HaloWgradKernel::rows128;
+        p.grid = dim3((Cin + 1) / 2, mtiles, p.nsplit);
+        p.lds = g.OH == 8 ? (size_t)2 * 2 * kHD * kWROWD_SKIP * sizeof(float) : (size_t)2 * 2 * kWHS * sizeof(float);
+    }
+    return p;
 }
+
 
 // dz = dy * act'(y), row sums of dz, and dz in the halo weight-gradient kernel's A-fragment order, for [N][C][8][8][8] tensors: one
 // WAVE per (sample, channel) row of 512 voxels, lane = one (od, oh) line of 8: two b128 loads per operand, two b128 stores of dz,
@@ -2116,78 +2181,62 @@ int halo_act_bwd_pack8_launch(const float* y, const float* dy, float* dz, float*
     return 1;
 }
 
-int halo_wgrad_try(const float* dy, const float* x, float* dw, int batch, int Cin, int Cin_total, const ConvGeom& g, int Cout,
-                   void* workspace, size_t workspace_bytes, hipStream_t stream, int force, bool dy_packed) {
-    const bool mode4 = wgrad_mode4(g);
-    if ((!mode4 && (g.OW % 8 != 0 || g.OH % 8 != 0)) || Cin < 2 || Cout < 32) return 0;
-    if ((long)batch * g.Cx * g.ID * g.IH * g.IW >= (1L << 31)) return 0;
-    if ((long)2 * g.ID * g.IH * g.IW * 4 >= (1L << 26)) return 0;   // box offset | edge-class word needs offsets below 2^26
-    int nslice, nsplit, mtiles;
-    wgrad_halo_plan(batch, g, Cin, Cout, nslice, nsplit, mtiles);
-    const bool rows64 = wgrad_rows64(g, Cin, Cout) && (long)4 * g.ID * g.IH * g.IW * 4 < (1L << 26);
-    if (wgrad_rows64(g, Cin, Cout) && !rows64) return 0;
-    const int ntiles = (rows64 ? Cin / 4 : (Cin + 1) / 2) * mtiles;
-    // auto-dispatch where it wins (round-1 A/B): no half-empty row tiles (Cout <= 64: the 64-row form, round 6) and enough workgroups
-    if (!force && ((Cout <= 64 && !rows64) || (long)ntiles * nsplit < 384)) return 0;
-    const size_t need = halo_wgrad_workspace_bytes(batch, Cin, Cout, g.OD, g.OH, g.OW);
-    if (!workspace || workspace_bytes < need) return 0;
-    const int per_split = (nslice + nsplit - 1) / nsplit;
-    nsplit = (nslice + per_split - 1) / per_split;
+void halo_wgrad_pack(const HaloWgradPlan& p, const float* dy, int Cout, const ConvGeom& g, void* workspace, hipStream_t stream) {
+    float4* ap = workspace_at<float4>(workspace, p.dy_image.offset);
+    int blocks = (int)((p.partial_offset / sizeof(float4) + 255) / 256);
+    if (blocks > 8192) blocks = 8192;
+    if (p.dy_image.kind == 1)
+        hipLaunchKernelGGL(pack_wgrad_dy4_kernel, dim3(blocks), dim3(256), 0, stream, dy, ap, Cout, p.dy_image.nt, p.nslice);
+    else
+        hipLaunchKernelGGL(pack_wgrad_dy_kernel, dim3(blocks), dim3(256), 0, stream, dy, ap, g, Cout, p.dy_image.nt, p.nslice,
+                           FastDiv(g.OW / 8), FastDiv(g.OH / 8), FastDiv(g.OD));
+}
 
-    const FastDiv dntw(mode4 ? 1 : g.OW / 8), dnth(mode4 ? 1 : g.OH / 8), dOD(g.OD);
-    float4* ap = (float4*)workspace;
-    const size_t pack_floats4 = (size_t)mtiles * 4 * nslice * 8 * 64;
-    float* part = (float*)(ap + pack_floats4);
-    if (!dy_packed) {
-        int blocks = (int)((pack_floats4 + 255) / 256);
-        if (blocks > 8192) blocks = 8192;
-        if (mode4)
-            hipLaunchKernelGGL(pack_wgrad_dy4_kernel, dim3(blocks), dim3(256), 0, stream, dy, ap, Cout, mtiles * 4, nslice);
-        else
-            hipLaunchKernelGGL(pack_wgrad_dy_kernel, dim3(blocks), dim3(256), 0, stream, dy, ap, g, Cout, rows64 ? mtiles * 2 : mtiles * 4,
-                               nslice, dntw, dnth, dOD);
-    }
+static HaloWgradArgs halo_wgrad_args(const HaloWgradPlan& p, const float* x, float* dw, int Cin, int Cin_total, int Cout,
+                                     const ConvGeom& g, void* workspace) {
+    const bool mode4 = p.kernel == HaloWgradKernel::halo4, direct = p.nsplit == 1;
     HaloWgradArgs a;
-    a.ap = ap;
+    a.ap = workspace_at<float4>(workspace, p.dy_image.offset);
     a.x = x;
+    a.ws = direct ? dw : workspace_at<float>(workspace, p.partial_offset);
     a.g = g;
     a.Cin = Cin;
     a.Cout = Cout;
-    a.nslice = nslice;
-    a.per_split = per_split;
-    a.mt_total = rows64 ? mtiles * 2 : mtiles * 4;
-    a.dntw = dntw;
-    a.dnth = dnth;
-    a.dOD = dOD;
-    const bool direct = nsplit == 1;
-    a.ws = direct ? dw : part;
+    a.nslice = p.nslice;
+    a.per_split = p.per_split;
+    a.mt_total = p.dy_image.nt;
     a.ldw = direct ? (long)Cin_total * 64 : (long)Cin * 64;
-    if (mode4) {
-        hipLaunchKernelGGL(conv_wgrad_halo4_kernel, dim3((Cin + 1) / 2, mtiles, nsplit), dim3(256),
-                           (size_t)2 * 2 * kW4CH * sizeof(float), stream, a);
-    } else {
-        if (rows64) {
-            const size_t lds = (size_t)2 * 4 * kWHS * sizeof(float);
-            hipLaunchKernelGGL((conv_wgrad_halo_kernel<4, false>), dim3(Cin / 4, mtiles, nsplit), dim3(256), lds, stream, a);
-        } else {
-            // OH == 8: the 8x8 tile spans H, which rows of the box are padding is static -> the form that skips them
-            if (g.OH == 8) {
-                const size_t lds = (size_t)2 * 2 * kHD * kWROWD_SKIP * sizeof(float);
-                hipLaunchKernelGGL((conv_wgrad_halo_kernel<2, true>), dim3((Cin + 1) / 2, mtiles, nsplit), dim3(256), lds, stream, a);
-            } else {
-                const size_t lds = (size_t)2 * 2 * kWHS * sizeof(float);
-                hipLaunchKernelGGL((conv_wgrad_halo_kernel<2, false>), dim3((Cin + 1) / 2, mtiles, nsplit), dim3(256), lds, stream, a);
-            }
-        }
+    a.dntw = FastDiv(mode4 ? 1 : g.OW / 8);
+    a.dnth = FastDiv(mode4 ? 1 : g.OH / 8);
+    a.dOD = FastDiv(g.OD);
+    return a;
+}
+
+void halo_wgrad_launch(const HaloWgradPlan& p, const float* x, float* dw, int Cin, int Cin_total, int Cout, const ConvGeom& g,
+                       void* workspace, hipStream_t stream) {
+    const HaloWgradArgs a = halo_wgrad_args(p, x, dw, Cin, Cin_total, Cout, g, workspace);
+    switch (p.kernel) {
+    case HaloWgradKernel::halo4:
+        hipLaunchKernelGGL(conv_wgrad_halo4_kernel, p.grid, dim3(p.block), p.lds, stream, a);
+        break;
+    case HaloWgradKernel::rows64:
+        hipLaunchKernelGGL((conv_wgrad_halo_kernel<4, false>), p.grid, dim3(p.block), p.lds, stream, a);
+        break;
+    case HaloWgradKernel::rows128_skip_h:
+        hipLaunchKernelGGL((conv_wgrad_halo_kernel<2, true>), p.grid, dim3(p.block), p.lds, stream, a);
+        break;
+    case HaloWgradKernel::rows128:
+        hipLaunchKernelGGL((conv_wgrad_halo_kernel<2, false>), p.grid, dim3(p.block), p.lds, stream, a);
+        break;
     }
-    if (!direct) {
+    if (p.nsplit > 1) {
         const long total = (long)Cout * Cin * 64;
         int fb = (int)((total / 4 + 255) / 256);
         if (fb > 2048) fb = 2048;
-        hipLaunchKernelGGL(wgrad_halo_finalize_kernel, dim3(fb), dim3(256), 0, stream, (const float*)part, dw, Cout, Cin * 64,
-                           (long)Cin_total * 64, nsplit);
+        hipLaunchKernelGGL(wgrad_halo_finalize_kernel, dim3(fb), dim3(256), 0, stream, (const float*)a.ws, dw, Cout, Cin * 64,
+                           (long)Cin_total * 64, p.nsplit);
     }
-    return 1;
 }
+
 
 }  // namespace sg
