@@ -1218,6 +1218,45 @@ int sg_cloud_normals(const float* points, const int64_t* cloud_offsets, long S, 
 int sg_cloud_sdf(const float* points, const float* normals, const int64_t* cloud_offsets, const float* queries,
                  const int64_t* query_offsets, long S, long N, long M, int K, float* sdf, int* nearest, hipStream_t stream);
 
+/* ---- K20: upscaling voxel grids: cubic B-spline prefilter, zoom and sampling --------------------------------------------------------
+ * reference: scipy.ndimage.zoom(voxels_32, 4) of create_plot.py:826-828 ("hybrid_gan_upscaling"): a cubic B-spline prefilter with the
+ *            mirror boundary, then a resampling at the positions o (n - 1) / (N - 1).  All three entry points follow that call's
+ *            defaults (order 3, mode 'constant', grid_mode False); sg_spline_sample is scipy.ndimage.map_coordinates of the same kind.
+ * Grids are [S][D][H][W] fp32, 1 <= D, H, W <= SG_SPLINE_MAX_AXIS, at most 2^36 elements per array and call; anything else is
+ * SG_ERR_ARG before any launch.  S = 0, P = 0: 0 is returned and nothing is launched.  No workspace: the only stores are to the result
+ * arrays, every element of which is written; an input and an output must not be the same array.  All arithmetic is fp32, stated once
+ * in csrc/spline_core.h with explicit fmaf (contraction off): the same bits on the GPU, in the twin, in every kernel form and wherever
+ * a grid stands in a batch.
+ *
+ * sg_spline_prefilter (create_plot.py:826-828): coefficients [S][D][H][W] of the grids: the line filter along W, then H, then D.  A
+ *   line of n = 1 is copied; otherwise, with z = (float)(sqrt(3) - 2) and zn = z^(n-1): every c[i] times 6; c[0] = (sum over
+ *   i = 0 .. n-2 of z^i (c[i] + zn c[n-1-i])) / (1 - zn zn); c[i] += z c[i-1] upward; c[n-1] = (z c[n-2] + c[n-1]) z / (z z - 1);
+ *   c[i] = z (c[i+1] - c[i]) downward.  Forms (sg_spline_prefilter_form): 0 when D H (W | 1) <= SG_SPLINE_LDS_FLOATS — one workgroup
+ *   holds the grid in LDS —, else 1: one pass per axis through global memory, the W pass staged through LDS.
+ *
+ * sg_spline_zoom (create_plot.py:826-828): out [S][D2][H2][W2] from the coefficients (order 3) or from the grids themselves
+ *   (order 1; any other order is SG_ERR_ARG).  Per axis, output index o of N over an input of n: num = o (n - 1) in integers,
+ *   f = num / (N - 1), t = (float)(num % (N - 1)) / (float)(N - 1); N = 1: f = 0, t = 0.  The taps f - 1 .. f + 2 carry the weights
+ *   (1-t)^3/6, (3t^3 - 6t^2 + 4)/6, (-3t^3 + 3t^2 + 3t + 1)/6, t^3/6 (order 1: 0, 1 - t, t, 0) and are folded by the periodic mirror of
+ *   period 2 (n - 1) (n = 1: index 0).  The 64 products are summed along W first, then H, then D (sg_spline_dot4).  Downscaling uses
+ *   the same formula, without anti-aliasing.  Forms (sg_spline_zoom_form): 0 when the coefficient box of an 8 x 8 x 64 output tile and
+ *   its two intermediates fit SG_SPLINE_ZOOM_LDS_FLOATS, as with every zoom factor >= 1, — tiles evaluated separably in LDS —, else 1:
+ *   one lane per output.
+ *
+ * sg_spline_sample (create_plot.py:826-828, at arbitrary positions): values [S][P] and, unless NULL, gradient [S][P][3] at points
+ *   [S][P][3] given in index coordinates (d, h, w) of the coefficients [S][D][H][W].  Inside 0 <= x <= n - 1 on every axis:
+ *   f = floor(x), at most n - 2 (so x = n - 1 is t = 1), the same 64 taps, and the derivative weights for the gradient, which is
+ *   with respect to the index coordinates.  Outside on any axis (NaN included): the value is `outside`, the gradient 0. */
+#define SG_SPLINE_FORM_LDS 0
+#define SG_SPLINE_FORM_GLOBAL 1
+int sg_spline_prefilter_form(long D, long H, long W);
+int sg_spline_zoom_form(long D, long H, long W, long D2, long H2, long W2);
+int sg_spline_prefilter(const float* grids, long S, long D, long H, long W, float* coefficients, hipStream_t stream);
+int sg_spline_zoom(const float* coefficients, long S, long D, long H, long W, long D2, long H2, long W2, int order, float* out,
+                   hipStream_t stream);
+int sg_spline_sample(const float* coefficients, long S, long D, long H, long W, const float* points, long P, float outside, float* values,
+                     float* gradient, hipStream_t stream);
+
 /* ---- data-parallel gradient exchange: libshapegan_comm.so ----------------------------------------------
  * reference: nn.DataParallel's gradient reduce-add, train_hybrid_progressive_gan.py:62-68.  One process per GPU; one
  * ncclAllReduce(sum, fp32) of a slice of the flat gradient buffer per call, on the communicator's own stream, ordered after

@@ -3317,3 +3317,88 @@ int sg_cloud_sdf_cpu(const float* points, const float* normals, const int64_t* c
 
 }  // extern "C"
 #pragma GCC pop_options
+
+// ---- K20: cubic B-spline prefilter, zoom and sampling of voxel grids (header: sg_spline_*; csrc/spline.hip) ---------------------------
+// Every line filtered in place in the output, every output from its 64 taps: the formulas are csrc/spline_core.h's, which the HIP
+// kernels include; the forms of the HIP library are a matter of where its lanes keep their values and do not exist here.
+#pragma GCC push_options
+#pragma GCC optimize("fp-contract=off")
+#include "../csrc/spline_core.h"
+
+static bool spline_axes_ok(long D, long H, long W) {
+    return D >= 1 && H >= 1 && W >= 1 && D <= SG_SPLINE_MAX_AXIS && H <= SG_SPLINE_MAX_AXIS && W <= SG_SPLINE_MAX_AXIS;
+}
+static const long kSplineMaxElements = 1L << 36;
+
+extern "C" {
+
+int sg_spline_prefilter_form_cpu(long D, long H, long W) {
+    CPU_CHECK(spline_axes_ok(D, H, W));
+    return sg_spline_prefilter_form_of(D, H, W);
+}
+
+int sg_spline_zoom_form_cpu(long D, long H, long W, long D2, long H2, long W2) {
+    CPU_CHECK(spline_axes_ok(D, H, W) && spline_axes_ok(D2, H2, W2));
+    return sg_spline_zoom_form_of(D, H, W, D2, H2, W2);
+}
+
+int sg_spline_prefilter_cpu(const float* grids, long S, long D, long H, long W, float* coefficients, hipStream_t_) {
+    CPU_CHECK(S >= 0 && spline_axes_ok(D, H, W) && S <= kSplineMaxElements / (D * H * W));
+    CPU_CHECK((grids && coefficients && grids != coefficients) || S == 0);
+    const long n = D * H * W;
+#pragma omp parallel for schedule(static)
+    for (long s = 0; s < S; ++s) {
+        float* c = coefficients + s * n;
+        memcpy(c, grids + s * n, (size_t)n * sizeof(float));
+        for (long r = 0; r < D * H; ++r) sg_spline_line(c + r * W, 1, (int)W);
+        for (long d = 0; d < D; ++d)
+            for (long w = 0; w < W; ++w) sg_spline_line(c + d * H * W + w, W, (int)H);
+        for (long r = 0; r < H * W; ++r) sg_spline_line(c + r, H * W, (int)D);
+    }
+    return SG_OK;
+}
+
+int sg_spline_zoom_cpu(const float* coefficients, long S, long D, long H, long W, long D2, long H2, long W2, int order, float* out,
+                       hipStream_t_) {
+    CPU_CHECK(S >= 0 && spline_axes_ok(D, H, W) && spline_axes_ok(D2, H2, W2) && (order == 1 || order == 3));
+    CPU_CHECK(S <= kSplineMaxElements / (D * H * W) && S <= kSplineMaxElements / (D2 * H2 * W2));
+    CPU_CHECK((coefficients && out && coefficients != out) || S == 0);
+#pragma omp parallel for collapse(2) schedule(static)
+    for (long s = 0; s < S; ++s)
+        for (long od = 0; od < D2; ++od) {
+            int fd, fh, fw;
+            float td, th, tw;
+            sg_spline_coord((int)od, (int)D, (int)D2, &fd, &td);
+            for (long oh = 0; oh < H2; ++oh) {
+                sg_spline_coord((int)oh, (int)H, (int)H2, &fh, &th);
+                for (long ow = 0; ow < W2; ++ow) {
+                    sg_spline_coord((int)ow, (int)W, (int)W2, &fw, &tw);
+                    out[((s * D2 + od) * H2 + oh) * W2 + ow] =
+                        sg_spline_point(coefficients + s * D * H * W, (int)D, (int)H, (int)W, fd, td, fh, th, fw, tw, order, nullptr);
+                }
+            }
+        }
+    return SG_OK;
+}
+
+int sg_spline_sample_cpu(const float* coefficients, long S, long D, long H, long W, const float* points, long P, float outside,
+                         float* values, float* gradient, hipStream_t_) {
+    CPU_CHECK(S >= 0 && P >= 0 && spline_axes_ok(D, H, W) && S <= kSplineMaxElements / (D * H * W));
+    CPU_CHECK(S == 0 || P == 0 || S <= kSplineMaxElements / (3 * P));
+    CPU_CHECK((coefficients && points && values) || S == 0 || P == 0);
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < S * P; ++i) {
+        int fd, fh, fw;
+        float td, th, tw, g[3] = {0.f, 0.f, 0.f}, v = outside;
+        const bool in_d = sg_spline_locate(points[i * 3], (int)D, &fd, &td), in_h = sg_spline_locate(points[i * 3 + 1], (int)H, &fh, &th),
+                   in_w = sg_spline_locate(points[i * 3 + 2], (int)W, &fw, &tw);
+        if (in_d && in_h && in_w)
+            v = sg_spline_point(coefficients + (i / P) * D * H * W, (int)D, (int)H, (int)W, fd, td, fh, th, fw, tw, 3, gradient ? g : nullptr);
+        values[i] = v;
+        if (gradient) gradient[i * 3] = g[0], gradient[i * 3 + 1] = g[1], gradient[i * 3 + 2] = g[2];
+    }
+    return SG_OK;
+}
+
+}  // extern "C"
+#pragma GCC pop_options

@@ -300,9 +300,12 @@ def _mc_chunk(grids, level, spacing, origin, pad, pad_value):
     return verts, norms, faces, vo, to
 
 
-def marching_cubes(grids, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), pad=True, pad_value=1.0):
+def marching_cubes(grids, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), pad=True, pad_value=1.0, upscale=None):
     """Meshes one grid [R0,R1,R2] or a batch [S,R0,R1,R2] (torch tensor or numpy array; CPU tensors run on the twin) at `level`
-    and returns a MeshBatch on the grids' device.  Batches beyond the int32 limits of one call are split."""
+    and returns a MeshBatch on the grids' device.  Batches beyond the int32 limits of one call are split.
+    upscale: a zoom factor (4: create_plot.py:826-828).  Every grid is zoomed by the cubic B-spline of shapegan_amd.voxelzoom before
+    it is meshed, the pad goes around the zoomed grid, and spacing and origin are adjusted so that the first and the last sample of
+    every axis stay where they were: the mesh stays in the same box.  None: the grids are meshed as they are."""
     if isinstance(grids, np.ndarray):
         grids = torch.from_numpy(grids)
     if grids.dim() == 3:
@@ -313,10 +316,24 @@ def marching_cubes(grids, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 
     spacing, origin = _triple(spacing), _triple(origin)
     level, pad_value = float(level), float(pad_value)
     S = grids.shape[0]
-    per = max_shapes_per_call(grids.shape[1:], pad)
+    shape = tuple(grids.shape[1:])
+    if upscale is not None:
+        from . import voxelzoom
+        fine = voxelzoom.zoom_size(shape, upscale)
+        scale = tuple((n - 1) / (N - 1) if N > 1 else 1.0 for n, N in zip(shape, fine))
+        # sample i of the coarse grid sits at (i + pad) * spacing + origin, sample I of the fine one at (I + pad) * spacing' + origin'
+        origin = tuple(o + int(bool(pad)) * (s - s * k) for o, s, k in zip(origin, spacing, scale))
+        spacing = tuple(s * k for s, k in zip(spacing, scale))
+        shape = fine
+    per = max_shapes_per_call(shape, pad)
     if per < 1:
-        raise RuntimeError("marching_cubes: one grid of %s exceeds the int32 index limits" % (tuple(grids.shape[1:]),))
-    parts = [_mc_chunk(grids[s:s + per], level, spacing, origin, pad, pad_value) for s in range(0, S, per)]
+        raise RuntimeError("marching_cubes: one grid of %s exceeds the int32 index limits" % (shape,))
+
+    def chunk(s):
+        part = grids[s:s + per]
+        return part if upscale is None else voxelzoom.zoom_grids(part, size=shape)
+
+    parts = [_mc_chunk(chunk(s), level, spacing, origin, pad, pad_value) for s in range(0, S, per)]
     if len(parts) == 1:
         return MeshBatch(*parts[0])
     vo = [parts[0][3]]

@@ -68,19 +68,21 @@ def sample_point_clouds(sdf_net, sample_count, point_cloud_size, voxel_resolutio
     return result
 
 
-def sample_from_voxels(voxels, point_cloud_size, rescale='half_unit_sphere', clean=False):
+def sample_from_voxels(voxels, point_cloud_size, rescale='half_unit_sphere', clean=False, upscale=None):
     """Meshes each voxel grid of `voxels` [B,R,R,R] (numpy or tensor) padded with 1 at level 0 and samples it
-    (metrics.py:31-46); computed on `util.device`.  clean: as sample_point_clouds."""
+    (metrics.py:31-46); computed on `util.device`.  clean: as sample_point_clouds.
+    upscale: a zoom factor: every grid goes through the cubic B-spline zoom of shapegan_amd.voxelzoom before it is meshed
+    (marching_cubes(upscale=), create_plot.py:826-828); the chunks are sized by the upscaled resolution."""
     result = np.zeros((voxels.shape[0], point_cloud_size, 3))
     size = 2
     voxel_resolution = voxels.shape[1]
     if isinstance(voxels, np.ndarray):
         voxels = torch.from_numpy(voxels)
     voxels = voxels.to(device=device, dtype=torch.float32)
-    chunk = shapes_per_chunk(voxel_resolution, False)
+    chunk = shapes_per_chunk(voxel_resolution if upscale is None else int(round(voxel_resolution * upscale)), False)
     for begin in range(0, voxels.shape[0], chunk):
         batch = marching_cubes(voxels[begin:begin + chunk], level=0, spacing=size / voxel_resolution, origin=-size / 2, pad=True,
-                               pad_value=1.0)
+                               pad_value=1.0, upscale=upscale)
         if clean:
             batch = batch.clean(clean)
         points, empty = batch.sample_surface(point_cloud_size, return_empty=True)

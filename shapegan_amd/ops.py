@@ -2724,3 +2724,93 @@ def tsne_step(y, P, velocity, gains, exaggeration, momentum, lr, min_gain=0.01, 
     finally:
         L.reset_call_state()
     return grad if plogp is None else (grad, kl)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# K20: cubic B-spline resampling of voxel grids (csrc/spline.hip; shapegan_amd/voxelzoom.py is the public layer)
+# --------------------------------------------------------------------------------------------------------------
+def _spline_grids(what, grids):
+    """The raw wrappers pass pointers: anything but a contiguous float32 [S, D, H, W] would be read as garbage."""
+    if not torch.is_tensor(grids) or grids.dtype != torch.float32 or grids.dim() != 4 or not grids.is_contiguous():
+        raise ValueError("%s: expected a contiguous float32 [S, D, H, W] tensor" % what)
+    if grids.requires_grad:
+        raise ValueError("%s: not differentiable — detach the grids" % what)
+    if min(grids.shape[1:]) < 1:
+        raise ValueError("%s: a grid axis of length 0 in %s" % (what, tuple(grids.shape)))
+    return tuple(int(n) for n in grids.shape)
+
+
+def _spline_p(t):
+    return ptr(t) if t is not None and t.numel() else None
+
+
+def spline_prefilter_form(shape, like):
+    """Which kernel form sg_spline_prefilter takes for grids [D, H, W] (0: LDS-resident, 1: per-axis passes); `like` names the device."""
+    L.note_device(like)
+    try:
+        form = _lib().sg_spline_prefilter_form(*(int(n) for n in shape))
+    finally:
+        L.reset_call_state()
+    check(min(form, 0), "spline_prefilter_form")
+    return form
+
+
+def spline_zoom_form(shape, size, like):
+    """Which kernel form sg_spline_zoom takes from [D, H, W] to `size` (0: LDS tiles, 1: one lane per output)."""
+    L.note_device(like)
+    try:
+        form = _lib().sg_spline_zoom_form(*(int(n) for n in tuple(shape) + tuple(size)))
+    finally:
+        L.reset_call_state()
+    check(min(form, 0), "spline_zoom_form")
+    return form
+
+
+def spline_prefilter(grids):
+    """sg_spline_prefilter: the cubic B-spline coefficients [S, D, H, W] of the grids."""
+    S, D, H, W = _spline_grids("spline_prefilter", grids)
+    out = torch.empty((S, D, H, W), dtype=torch.float32, device=grids.device)
+    try:
+        L.note_device(grids)      # an empty call has no pointer to name its device
+        check(_lib().sg_spline_prefilter(_spline_p(grids), S, D, H, W, _spline_p(out), stream()), "spline_prefilter")
+    finally:
+        L.reset_call_state()
+    return out
+
+
+def spline_zoom(coefficients, size, order=3):
+    """sg_spline_zoom: [S, D2, H2, W2] from the coefficients (order 3) or the grids themselves (order 1)."""
+    S, D, H, W = _spline_grids("spline_zoom", coefficients)
+    size = tuple(int(n) for n in size)
+    if len(size) != 3 or min(size) < 1:
+        raise ValueError("spline_zoom: the output size must be three lengths >= 1, got %r" % (size,))
+    if order not in (1, 3):
+        raise ValueError("spline_zoom: order 1 or 3, got %r" % (order,))
+    out = torch.empty((S,) + size, dtype=torch.float32, device=coefficients.device)
+    try:
+        L.note_device(coefficients)      # an empty call has no pointer to name its device
+        check(_lib().sg_spline_zoom(_spline_p(coefficients), S, D, H, W, size[0], size[1], size[2], int(order), _spline_p(out), stream()),
+              "spline_zoom")
+    finally:
+        L.reset_call_state()
+    return out
+
+
+def spline_sample(coefficients, points, gradient=False, outside=1.0):
+    """sg_spline_sample: values [S, P] (and gradient [S, P, 3]) at points [S, P, 3] in index coordinates."""
+    S, D, H, W = _spline_grids("spline_sample", coefficients)
+    if (not torch.is_tensor(points) or points.dtype != torch.float32 or points.dim() != 3 or points.shape[0] != S or points.shape[2] != 3
+            or not points.is_contiguous()):
+        raise ValueError("spline_sample: points must be a contiguous float32 [S = %d, P, 3] tensor" % S)
+    if points.device != coefficients.device:
+        raise RuntimeError("spline_sample: the coefficients are on %s, the points on %s" % (coefficients.device, points.device))
+    P = int(points.shape[1])
+    values = torch.empty((S, P), dtype=torch.float32, device=coefficients.device)
+    grad = torch.empty((S, P, 3), dtype=torch.float32, device=coefficients.device) if gradient else None
+    try:
+        L.note_device(coefficients)      # an empty call has no pointer to name its device
+        check(_lib().sg_spline_sample(_spline_p(coefficients), S, D, H, W, _spline_p(points), P, float(outside), _spline_p(values),
+                                      _spline_p(grad), stream()), "spline_sample")
+    finally:
+        L.reset_call_state()
+    return (values, grad) if gradient else values

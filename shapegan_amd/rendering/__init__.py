@@ -64,11 +64,13 @@ class MeshRenderer(object):
             voxels = torch.from_numpy(voxels)
         return voxels.detach()
 
-    def _mesh_voxels(self, grids, pad, level):
+    def _mesh_voxels(self, grids, pad, level, upscale=None):
         R = grids.shape[-2]        # the reference's voxels.shape[1]
-        return M.marching_cubes(self._place(grids), level=level, spacing=2.0 / R, origin=-1.0, pad=bool(pad))
+        return M.marching_cubes(self._place(grids), level=level, spacing=2.0 / R, origin=-1.0, pad=bool(pad), upscale=upscale)
 
-    def set_voxels(self, voxels, use_marching_cubes=True, shade_smooth=False, pad=True, level=0):
+    def set_voxels(self, voxels, use_marching_cubes=True, shade_smooth=False, pad=True, level=0, upscale=None):
+        """upscale: a zoom factor: the grid goes through the cubic B-spline zoom of shapegan_amd.voxelzoom before it is meshed
+        (create_plot.py:826-828); None: it is meshed as it is."""
         if not use_marching_cubes:
             raise NotImplementedError("MeshRenderer.set_voxels(use_marching_cubes=False): the binary-voxel cube mesh "
                                       "(create_binary_voxel_mesh) is not implemented; pass an SDF grid")
@@ -77,7 +79,7 @@ class MeshRenderer(object):
             voxels = voxels.squeeze()
         if voxels.dim() != 3:
             raise ValueError("set_voxels: expected one grid of rank 3, got %s" % (tuple(voxels.shape),))
-        batch = self._mesh_voxels(voxels, pad, level)
+        batch = self._mesh_voxels(voxels, pad, level, upscale)
         if batch.faces.shape[0] == 0:
             return                 # no sign change: the previous mesh stays (the reference's `except ValueError: pass`)
         self.model_size = 1.4
@@ -118,13 +120,13 @@ class MeshRenderer(object):
         self.model_size = 1.08
         return self._finish(self._draw(raster.pack(batch, smooth=smooth)), return_tensor)
 
-    def render_voxels(self, grids, shade_smooth=False, pad=True, level=0, return_tensor=False):
-        """The same for SDF grids [S, R, R, R]; a grid without a sign change gives floor and background only."""
+    def render_voxels(self, grids, shade_smooth=False, pad=True, level=0, return_tensor=False, upscale=None):
+        """The same for SDF grids [S, R, R, R]; a grid without a sign change gives floor and background only.  upscale: as set_voxels."""
         grids = self._grids(grids)
         if grids.dim() != 4:
             raise ValueError("render_voxels: expected [S, R, R, R], got %s" % (tuple(grids.shape),))
         self.model_size = 1.4
-        return self._finish(self._draw(raster.pack(self._mesh_voxels(grids, pad, level), smooth=shade_smooth)), return_tensor)
+        return self._finish(self._draw(raster.pack(self._mesh_voxels(grids, pad, level, upscale), smooth=shade_smooth)), return_tensor)
 
     @staticmethod
     def _finish(images, return_tensor):
