@@ -1257,6 +1257,54 @@ int sg_spline_zoom(const float* coefficients, long S, long D, long H, long W, lo
 int sg_spline_sample(const float* coefficients, long S, long D, long H, long W, const float* points, long P, float outside, float* values,
                      float* gradient, hipStream_t stream);
 
+/* ---- K21: distance transforms of voxel grids: exact Euclidean distance transform and redistancing ------------------------------------
+ * reference: the voxel models and VoxelDataset (datasets.py:7-40) hold distances clamped to +-0.1, stored as sdf / 0.1: beyond the
+ *            truncation a grid says nothing but a sign.  scipy.ndimage.distance_transform_edt is the transform of an occupancy mask;
+ *            the same transform from the level crossings of a grid ("redistancing") gives a truncated grid its distances back.
+ * Grids are [S][D][H][W] fp32, 1 <= D, H, W <= SG_EDT_MAX_AXIS, at most 2^36 elements per array and call; spacing_d / _h / _w > 0 is
+ * the world length of one index step, a voxel's position its index times the spacing.  Anything else is SG_ERR_ARG before any launch;
+ * S = 0: 0 is returned and nothing is launched.  A SITE is a point q with an offset f(q) >= 0; the transform of a site set Q is
+ *   T(p) = min over q in Q of f(q) + |p - q|^2   over the voxels p of the same grid, +inf when the grid has no site.
+ * The grids of a call are independent.  T is computed by one pass per axis.  EXACTNESS: every pass returns, for every output p of a
+ * line, the exact minimum over the line's candidates fmaf(d, d, g[q]), d = (float)(p - q) * spacing of that axis in fp32, g the
+ * previous pass's result: min is exact and order-free, so the GPU in both forms and the twin return the same bits (csrc/edt_core.h
+ * states the arithmetic once, contraction off).  The scan goes outward from p and stops when d d alone exceeds the best so far, which
+ * is exact because g >= 0.  TIES are broken inside each pass by the smaller q; the nearest-site outputs follow from that.
+ *
+ * sg_edt_voxels (scipy.ndimage.distance_transform_edt): the sites are the background voxels, f = 0: a voxel with !(v < level), or with
+ *   v < level when `inside` is not 0.  Passes: W, then H, then D.  squared [S][D][H][W] = T; with unit spacing every candidate is an
+ *   integer below 2^24 and T is exact.  nearest (or NULL) [S][D][H][W] int: the linear index, within its grid, of a site that attains
+ *   T, -1 when the grid has none.
+ * sg_edt_crossings (redistancing): the sites are the points where a grid edge crosses `level` by linear interpolation, exactly the
+ *   vertices sg_mc_emit makes of the unpadded grid with origin 0: an edge from voxel a to its successor b along an axis crosses when
+ *   (va < level) != (vb < level), at the index coordinate u = (float)a + t, t = (level - va) / (vb - va) (mesh_core.h), f = 0.  The
+ *   edges along one axis are a family: its first pass runs along that axis, candidate fmaf(d, d, 0), d = ((float)p - u) * spacing,
+ *   and the two other axes follow in increasing order with integer offsets.  The families D, H, W are computed in this order and
+ *   squared = their minimum, the earlier family on a tie.  closest (or NULL) [S][D][H][W][3]: the world position of the attaining
+ *   crossing, ((float)a + t) * spacing on the edge's axis and index * spacing on the others; NaN when the grid has none.
+ * sg_edt_finish: out = s sqrt(squared), s = -1 where v < level, else +1; sqrt is correctly rounded; a grid without sites gives s inf.
+ *   keep_band != 0: a voxel with a 6-neighbour on the other side of the level keeps (v - level) * value_scale (world distance per
+ *   grid unit: 0.1 for VoxelDataset grids, 1 for raw distances).  out may be `squared` itself.  grids = NULL (keep_band must be 0):
+ *   out = sqrt(squared), the plain root, as scipy's transform returns it; level and value_scale are not used.
+ * Forms (sg_edt_form, from the shape alone): 0 when D H W <= SG_EDT_LDS_FLOATS — one workgroup holds the grid in LDS and runs every
+ *   pass there —, else 1: one launch per pass through global memory, neighbouring lanes on neighbouring w.
+ * workspace: caller-owned, sg_edt_workspace_bytes(sites, S, D, H, W, nearest) bytes (sites: SG_EDT_VOXELS / SG_EDT_CROSSINGS; nearest:
+ *   whether the optional output is requested; 0 bytes is possible, and NULL then allowed); fewer returns SG_ERR_WORKSPACE with the
+ *   outputs untouched.  Nothing is read from it that the same call did not write.  Every element of every requested output is
+ *   written.  All entries are asynchronous on `stream`, read no environment and keep no state. */
+#define SG_EDT_FORM_LDS 0
+#define SG_EDT_FORM_GLOBAL 1
+#define SG_EDT_VOXELS 0
+#define SG_EDT_CROSSINGS 1
+int sg_edt_form(long D, long H, long W);
+size_t sg_edt_workspace_bytes(int sites, long S, long D, long H, long W, int nearest);
+int sg_edt_voxels(const float* grids, long S, long D, long H, long W, float level, int inside, float spacing_d, float spacing_h,
+                  float spacing_w, float* squared, int* nearest, void* workspace, size_t workspace_bytes, hipStream_t stream);
+int sg_edt_crossings(const float* grids, long S, long D, long H, long W, float level, float spacing_d, float spacing_h, float spacing_w,
+                     float* squared, float* closest, void* workspace, size_t workspace_bytes, hipStream_t stream);
+int sg_edt_finish(const float* grids, const float* squared, long S, long D, long H, long W, float level, float value_scale, int keep_band,
+                  float* out, hipStream_t stream);
+
 /* ---- data-parallel gradient exchange: libshapegan_comm.so ----------------------------------------------
  * reference: nn.DataParallel's gradient reduce-add, train_hybrid_progressive_gan.py:62-68.  One process per GPU; one
  * ncclAllReduce(sum, fp32) of a slice of the flat gradient buffer per call, on the communicator's own stream, ordered after

@@ -27,6 +27,7 @@
 typedef void* hipStream_t_;
 #define SG_OK 0          // csrc/common.h (the header names the codes only in its comments)
 #define SG_ERR_ARG (-1)
+#define SG_ERR_WORKSPACE (-3)
 enum { ACT_NONE = 0, ACT_LEAKY = 1, ACT_RELU = 2, ACT_TANH = 3, ACT_SIGMOID = 4 };
 
 static thread_local char g_err[512];
@@ -3397,6 +3398,145 @@ int sg_spline_sample_cpu(const float* coefficients, long S, long D, long H, long
         values[i] = v;
         if (gradient) gradient[i * 3] = g[0], gradient[i * 3 + 1] = g[1], gradient[i * 3 + 2] = g[2];
     }
+    return SG_OK;
+}
+
+}  // extern "C"
+#pragma GCC pop_options
+
+// ---- K21: distance transforms of voxel grids (header: sg_edt_*; csrc/edt.hip) ----------------------------------------------------------
+// One grid at a time, every pass from one array to another, every output from csrc/edt_core.h's exact line minimum, which the HIP
+// kernels include: the passes, their order and the tie rules are the header's.  The scratch is the twin's own; the caller's workspace
+// is only measured, so that a short one fails here as it does on the GPU.
+#pragma GCC push_options
+#pragma GCC optimize("fp-contract=off")
+#include "../csrc/edt_core.h"
+
+static bool edt_axes_ok(long D, long H, long W) {
+    return D >= 1 && H >= 1 && W >= 1 && D <= SG_EDT_MAX_AXIS && H <= SG_EDT_MAX_AXIS && W <= SG_EDT_MAX_AXIS;
+}
+static bool edt_spacing_ok(float a, float b, float c) { return a > 0.f && b > 0.f && c > 0.f && a < INFINITY && b < INFINITY && c < INFINITY; }
+static const long kEdtMaxElements = 1L << 36;
+
+static size_t edt_workspace_bytes(int sites, long S, long D, long H, long W, int nearest) {
+    const size_t cells = (size_t)S * D * H * W * sizeof(float);
+    if (sg_edt_form_of(D, H, W) == 0) return sites == 1 && nearest ? 2 * cells : 0;
+    return cells * (2 + (nearest ? (sites == 1 ? 3 : 2) : 0));
+}
+
+// one axis pass of one grid: in -> out; merge keeps what out holds unless the new value is smaller
+static void edt_axis_pass(const float* in, const int* id_in, int axis, int D, int H, int W, float spacing, bool merge, float* out, int* id_out) {
+    int outer, n, inner;
+    sg_edt_view(axis, D, H, W, &outer, &n, &inner);
+    for (int o = 0; o < outer; ++o)
+        for (int p = 0; p < n; ++p)
+            for (int i = 0; i < inner; ++i) {
+                const long base = (long)o * n * inner + i, at = base + (long)p * inner;
+                int q;
+                const float r = sg_edt_axis(in + base, inner, n, p, spacing, &q);
+                if (merge && !(r < out[at])) continue;
+                out[at] = r;
+                if (id_out) id_out[at] = id_in[base + (long)q * inner];
+            }
+}
+
+extern "C" {
+
+int sg_edt_form_cpu(long D, long H, long W) {
+    CPU_CHECK(edt_axes_ok(D, H, W));
+    return sg_edt_form_of(D, H, W);
+}
+
+int sg_edt_voxels_cpu(const float* grids, long S, long D, long H, long W, float level, int inside, float spacing_d, float spacing_h,
+                      float spacing_w, float* squared, int* nearest, void* workspace, size_t workspace_bytes, hipStream_t_) {
+    CPU_CHECK(S >= 0 && edt_axes_ok(D, H, W) && S <= kEdtMaxElements / (D * H * W));
+    CPU_CHECK(edt_spacing_ok(spacing_d, spacing_h, spacing_w) && level == level);
+    CPU_CHECK((grids && squared && grids != squared) || S == 0);
+    if (S == 0) return SG_OK;
+    const size_t need = edt_workspace_bytes(0, S, D, H, W, nearest != nullptr);
+    if (need && (!workspace || workspace_bytes < need)) {
+        snprintf(g_err, sizeof(g_err), "%s: workspace of %zu B, %zu B needed", __func__, workspace_bytes, need);
+        return SG_ERR_WORKSPACE;
+    }
+    const long n = D * H * W;
+#pragma omp parallel for schedule(static)
+    for (long s = 0; s < S; ++s) {
+        const float* g = grids + s * n;
+        std::vector<float> A(n), B(n);
+        std::vector<int> IA(nearest ? n : 0), IB(nearest ? n : 0);
+        int* ia = nearest ? IA.data() : nullptr;
+        int* ib = nearest ? IB.data() : nullptr;
+        for (long i = 0; i < n; ++i) {
+            const bool site = sg_edt_is_site(g[i], level, inside);
+            A[i] = site ? 0.f : INFINITY;
+            if (ia) ia[i] = site ? (int)i : -1;
+        }
+        edt_axis_pass(A.data(), ia, 2, (int)D, (int)H, (int)W, spacing_w, false, B.data(), ib);
+        edt_axis_pass(B.data(), ib, 1, (int)D, (int)H, (int)W, spacing_h, false, A.data(), ia);
+        edt_axis_pass(A.data(), ia, 0, (int)D, (int)H, (int)W, spacing_d, false, squared + s * n, nearest ? nearest + s * n : nullptr);
+    }
+    return SG_OK;
+}
+
+int sg_edt_crossings_cpu(const float* grids, long S, long D, long H, long W, float level, float spacing_d, float spacing_h, float spacing_w,
+                         float* squared, float* closest, void* workspace, size_t workspace_bytes, hipStream_t_) {
+    CPU_CHECK(S >= 0 && edt_axes_ok(D, H, W) && S <= kEdtMaxElements / (D * H * W));
+    CPU_CHECK(edt_spacing_ok(spacing_d, spacing_h, spacing_w) && level == level);
+    CPU_CHECK((grids && squared && grids != squared && grids != closest && squared != closest) || S == 0);
+    if (S == 0) return SG_OK;
+    const size_t need = edt_workspace_bytes(1, S, D, H, W, closest != nullptr);
+    if (need && (!workspace || workspace_bytes < need)) {
+        snprintf(g_err, sizeof(g_err), "%s: workspace of %zu B, %zu B needed", __func__, workspace_bytes, need);
+        return SG_ERR_WORKSPACE;
+    }
+    const long n = D * H * W;
+    const float sp[3] = {spacing_d, spacing_h, spacing_w};
+#pragma omp parallel for schedule(static)
+    for (long s = 0; s < S; ++s) {
+        const float* g = grids + s * n;
+        std::vector<float> A(n), B(n);
+        std::vector<int> IA(closest ? n : 0), IB(closest ? n : 0), IC(closest ? n : 0);
+        int* ia = closest ? IA.data() : nullptr;
+        int* ib = closest ? IB.data() : nullptr;
+        int* ic = closest ? IC.data() : nullptr;
+        for (int axis = 0; axis < 3; ++axis) {
+            int outer, len, inner;
+            sg_edt_view(axis, (int)D, (int)H, (int)W, &outer, &len, &inner);
+            for (long i = 0; i < n; ++i) {
+                const long base = i / ((long)len * inner) * ((long)len * inner) + i % inner;
+                int q;
+                A[i] = sg_edt_cross(g + base, inner, len, (int)(i / inner % len), level, sp[axis], &q);
+                if (ia) ia[i] = q < 0 ? -1 : sg_edt_code((int)(base + (long)q * inner), axis);
+            }
+            const int b = sg_edt_other_axis(axis, 0), c = sg_edt_other_axis(axis, 1);
+            edt_axis_pass(A.data(), ia, b, (int)D, (int)H, (int)W, sp[b], false, B.data(), ib);
+            edt_axis_pass(B.data(), ib, c, (int)D, (int)H, (int)W, sp[c], axis > 0, squared + s * n, ic);
+        }
+        if (closest)
+            for (long i = 0; i < n; ++i) sg_edt_decode(g, (int)H, (int)W, ic[i], level, sp, closest + (s * n + i) * 3);
+    }
+    return SG_OK;
+}
+
+int sg_edt_finish_cpu(const float* grids, const float* squared, long S, long D, long H, long W, float level, float value_scale, int keep_band,
+                      float* out, hipStream_t_) {
+    CPU_CHECK(S >= 0 && edt_axes_ok(D, H, W) && S <= kEdtMaxElements / (D * H * W));
+    CPU_CHECK((squared && out && (grids ? grids != out && grids != squared : keep_band == 0)) || S == 0);
+    const long n = D * H * W;
+    if (!grids) {      // the plain root: no sign, no band
+#pragma omp parallel for schedule(static)
+        for (long i = 0; i < S * n; ++i) out[i] = sg_edt_root(squared[i]);
+        return SG_OK;
+    }
+#pragma omp parallel for collapse(2) schedule(static)
+    for (long s = 0; s < S; ++s)
+        for (long d = 0; d < D; ++d)
+            for (long h = 0; h < H; ++h)
+                for (long w = 0; w < W; ++w) {
+                    const long i = s * n + (d * H + h) * W + w;
+                    out[i] = sg_edt_finish_value(grids + s * n, (int)D, (int)H, (int)W, (int)d, (int)h, (int)w, squared[i], level, value_scale,
+                                                 keep_band);
+                }
     return SG_OK;
 }
 

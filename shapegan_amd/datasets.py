@@ -26,10 +26,14 @@ class VoxelDataset(object):
     """datasets.py:7-40: same constructor, `__len__`, `__getitem__` (host path, one item: exactly the reference's
     numpy -> clamp_ -> /= sequence), `glob`, `from_split`.  `resident()` / `stream()` are the native batch paths."""
 
-    def __init__(self, files, clamp=0.1, rescale_sdf=True):
+    def __init__(self, files, clamp=0.1, rescale_sdf=True, occupancy=False):
+        """occupancy: the files hold occupancy grids (non-zero: occupied), not distances: `resident()` and `stream()` turn every
+        batch into signed distances on the device (shapegan_amd.voxeldist.occupancy_to_sdf, grids that span [-1, 1]) before the
+        clamp / rescale; `__getitem__` stays the reference's host path and returns the file as it is."""
         self.files = files
         self.clamp = clamp
         self.rescale_sdf = rescale_sdf
+        self.occupancy = occupancy
 
     def __len__(self):
         return len(self.files)
@@ -59,6 +63,13 @@ class VoxelDataset(object):
     def _divisor(self):
         return float(self.clamp) if (self.clamp is not None and self.rescale_sdf) else 0.0
 
+    def _distances(self, batch):
+        """occupancy=True: the batch, in place, as signed distances."""
+        if self.occupancy:
+            from . import voxeldist
+            batch.copy_(voxeldist.occupancy_to_sdf(batch))
+        return batch
+
     def resident(self, device="cuda", max_bytes=64 << 30):
         """Loads every file into one [N,R,R,R] HBM tensor and applies clamp / rescale there (one kernel pass)."""
         first = np.load(self.files[0])
@@ -68,7 +79,7 @@ class VoxelDataset(object):
         host = torch.empty((len(self.files),) + tuple(first.shape), dtype=torch.float32).pin_memory()
         for i, name in enumerate(self.files):
             host[i] = torch.from_numpy(np.load(name))
-        data = host.to(device, non_blocking=True)
+        data = self._distances(host.to(device, non_blocking=True))
         if self.clamp is not None:
             ops.voxel_prepare(data, self.clamp, self._divisor())
         return ResidentVoxels(data)
@@ -164,6 +175,7 @@ class VoxelStream(object):
                     batch.view(self.pinned[slot].shape).copy_(self.pinned[slot], non_blocking=True)
                 else:
                     batch = self.pinned[slot][:len(names)].to(self.device, non_blocking=True)
+                ds._distances(batch.view(self.pinned[slot][:len(names)].shape))
                 if ds.clamp is not None:
                     ops.voxel_prepare(batch, ds.clamp, ds._divisor())
                 done = torch.cuda.Event()

@@ -300,12 +300,17 @@ def _mc_chunk(grids, level, spacing, origin, pad, pad_value):
     return verts, norms, faces, vo, to
 
 
-def marching_cubes(grids, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), pad=True, pad_value=1.0, upscale=None):
+def marching_cubes(grids, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), pad=True, pad_value=1.0, upscale=None,
+                   redistance=False):
     """Meshes one grid [R0,R1,R2] or a batch [S,R0,R1,R2] (torch tensor or numpy array; CPU tensors run on the twin) at `level`
     and returns a MeshBatch on the grids' device.  Batches beyond the int32 limits of one call are split.
     upscale: a zoom factor (4: create_plot.py:826-828).  Every grid is zoomed by the cubic B-spline of shapegan_amd.voxelzoom before
     it is meshed, the pad goes around the zoomed grid, and spacing and origin are adjusted so that the first and the last sample of
-    every axis stay where they were: the mesh stays in the same box.  None: the grids are meshed as they are."""
+    every axis stay where they were: the mesh stays in the same box.  None: the grids are meshed as they are.
+    redistance: True, or the world distance one grid unit stands for (True: 0.1, the grids of datasets.py:7-40).  Every grid is first
+    redistanced about its zero level (shapegan_amd.voxeldist.redistance_grids with this call's spacing; the values next to the
+    surface are kept) and divided by that scale again, so it stays in grid units and holds distances beyond its truncation: a `level`
+    outside [-1, 1] is then an offset surface (choose pad_value beyond it).  It comes before upscale.  False: the call as it was."""
     if isinstance(grids, np.ndarray):
         grids = torch.from_numpy(grids)
     if grids.dim() == 3:
@@ -317,6 +322,7 @@ def marching_cubes(grids, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 
     level, pad_value = float(level), float(pad_value)
     S = grids.shape[0]
     shape = tuple(grids.shape[1:])
+    coarse_spacing = spacing
     if upscale is not None:
         from . import voxelzoom
         fine = voxelzoom.zoom_size(shape, upscale)
@@ -331,6 +337,10 @@ def marching_cubes(grids, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 
 
     def chunk(s):
         part = grids[s:s + per]
+        if redistance:
+            from . import voxeldist
+            scale = 0.1 if redistance is True else float(redistance)
+            part = voxeldist.redistance_grids(part, 0.0, coarse_spacing, scale, True) / scale
         return part if upscale is None else voxelzoom.zoom_grids(part, size=shape)
 
     parts = [_mc_chunk(chunk(s), level, spacing, origin, pad, pad_value) for s in range(0, S, per)]

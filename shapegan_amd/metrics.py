@@ -68,11 +68,12 @@ def sample_point_clouds(sdf_net, sample_count, point_cloud_size, voxel_resolutio
     return result
 
 
-def sample_from_voxels(voxels, point_cloud_size, rescale='half_unit_sphere', clean=False, upscale=None):
+def sample_from_voxels(voxels, point_cloud_size, rescale='half_unit_sphere', clean=False, upscale=None, redistance=False):
     """Meshes each voxel grid of `voxels` [B,R,R,R] (numpy or tensor) padded with 1 at level 0 and samples it
     (metrics.py:31-46); computed on `util.device`.  clean: as sample_point_clouds.
     upscale: a zoom factor: every grid goes through the cubic B-spline zoom of shapegan_amd.voxelzoom before it is meshed
-    (marching_cubes(upscale=), create_plot.py:826-828); the chunks are sized by the upscaled resolution."""
+    (marching_cubes(upscale=), create_plot.py:826-828); the chunks are sized by the upscaled resolution.
+    redistance: marching_cubes(redistance=): the grids get their distances back beyond the truncation before they are meshed."""
     result = np.zeros((voxels.shape[0], point_cloud_size, 3))
     size = 2
     voxel_resolution = voxels.shape[1]
@@ -82,7 +83,7 @@ def sample_from_voxels(voxels, point_cloud_size, rescale='half_unit_sphere', cle
     chunk = shapes_per_chunk(voxel_resolution if upscale is None else int(round(voxel_resolution * upscale)), False)
     for begin in range(0, voxels.shape[0], chunk):
         batch = marching_cubes(voxels[begin:begin + chunk], level=0, spacing=size / voxel_resolution, origin=-size / 2, pad=True,
-                               pad_value=1.0, upscale=upscale)
+                               pad_value=1.0, upscale=upscale, redistance=redistance)
         if clean:
             batch = batch.clean(clean)
         points, empty = batch.sample_surface(point_cloud_size, return_empty=True)

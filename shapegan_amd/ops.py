@@ -2814,3 +2814,85 @@ def spline_sample(coefficients, points, gradient=False, outside=1.0):
     finally:
         L.reset_call_state()
     return (values, grad) if gradient else values
+
+
+# --------------------------------------------------------------------------------------------------------------
+# K21: distance transforms of voxel grids (csrc/edt.hip; shapegan_amd/voxeldist.py is the public layer)
+# --------------------------------------------------------------------------------------------------------------
+EDT_VOXELS, EDT_CROSSINGS = L.abi.DEFINES["SG_EDT_VOXELS"], L.abi.DEFINES["SG_EDT_CROSSINGS"]
+
+
+def _edt_spacing(what, spacing):
+    spacing = (float(spacing),) * 3 if np.isscalar(spacing) else tuple(float(s) for s in spacing)
+    if len(spacing) != 3 or not all(0.0 < s < float("inf") for s in spacing):
+        raise ValueError("%s: spacing is one positive length or one per axis, got %r" % (what, spacing))
+    return spacing
+
+
+def edt_form(shape, like):
+    """Which kernel form the sg_edt_* entries take for grids [D, H, W] (0: LDS-resident, 1: per-axis passes); `like` names the device."""
+    L.note_device(like)
+    try:
+        form = _lib().sg_edt_form(*(int(n) for n in shape))
+    finally:
+        L.reset_call_state()
+    check(min(form, 0), "edt_form")
+    return form
+
+
+def _edt_workspace(sites, shape, nearest, device):
+    return workspace("edt", _lib().sg_edt_workspace_bytes(sites, *shape, int(bool(nearest))), device)
+
+
+def edt_voxels(grids, level=0.5, inside=True, spacing=1.0, nearest=False):
+    """sg_edt_voxels: squared [S, D, H, W] distances to the nearest background voxel (v < level with `inside`, else !(v < level)) and,
+    with nearest=True, the int32 linear index of one within its grid (-1: the grid has none)."""
+    shape = _spline_grids("edt_voxels", grids)
+    sp = _edt_spacing("edt_voxels", spacing)
+    squared = torch.empty(shape, dtype=torch.float32, device=grids.device)
+    index = torch.empty(shape, dtype=torch.int32, device=grids.device) if nearest else None
+    try:
+        L.note_device(grids)      # an empty call has no pointer to name its device
+        ws = _edt_workspace(EDT_VOXELS, shape, nearest, grids.device)
+        check(_lib().sg_edt_voxels(_spline_p(grids), *shape, float(level), int(bool(inside)), sp[0], sp[1], sp[2], _spline_p(squared),
+                                   _spline_p(index), ptr(ws), ws.numel(), stream()), "edt_voxels")
+    finally:
+        L.reset_call_state()
+    return (squared, index) if nearest else squared
+
+
+def edt_crossings(grids, level=0.0, spacing=1.0, closest=False):
+    """sg_edt_crossings: squared [S, D, H, W] distances to the nearest point where a grid edge crosses `level` and, with closest=True,
+    that point's world position [S, D, H, W, 3] (NaN: the grid has none)."""
+    shape = _spline_grids("edt_crossings", grids)
+    sp = _edt_spacing("edt_crossings", spacing)
+    squared = torch.empty(shape, dtype=torch.float32, device=grids.device)
+    where = torch.empty(shape + (3,), dtype=torch.float32, device=grids.device) if closest else None
+    try:
+        L.note_device(grids)
+        ws = _edt_workspace(EDT_CROSSINGS, shape, closest, grids.device)
+        check(_lib().sg_edt_crossings(_spline_p(grids), *shape, float(level), sp[0], sp[1], sp[2], _spline_p(squared), _spline_p(where),
+                                      ptr(ws), ws.numel(), stream()), "edt_crossings")
+    finally:
+        L.reset_call_state()
+    return (squared, where) if closest else squared
+
+
+def edt_finish(grids, squared, level=0.0, value_scale=1.0, keep_band=False):
+    """sg_edt_finish: signed distances [S, D, H, W] from the squared ones: -sqrt where grids < level, +sqrt elsewhere; keep_band keeps
+    (grids - level) * value_scale at the voxels that have a 6-neighbour on the other side of the level.  grids=None: the plain,
+    correctly rounded root of `squared`."""
+    shape = _spline_grids("edt_finish", squared)
+    if grids is None:
+        if keep_band:
+            raise ValueError("edt_finish: keep_band needs the grids")
+    elif _spline_grids("edt_finish", grids) != shape or squared.device != grids.device:
+        raise ValueError("edt_finish: the squared distances must have the grids' shape and device")
+    out = torch.empty(shape, dtype=torch.float32, device=squared.device)
+    try:
+        L.note_device(squared)
+        check(_lib().sg_edt_finish(_spline_p(grids), _spline_p(squared), *shape, float(level), float(value_scale), int(bool(keep_band)),
+                                   _spline_p(out), stream()), "edt_finish")
+    finally:
+        L.reset_call_state()
+    return out
