@@ -93,7 +93,24 @@ int sg_conv3d_k4s2p1_dgrad_impl(const float* dy, const float* w, const float* bi
 /* (impl 1: the LDS-halo kernel, 3: one output parity per workgroup, 1 + 4 ppw: ppw parities; + 64: the depth-skip form of the
  * 4^3 -> 8^3 64-row kernel, conv_dgrad_halo_dskip_kernel, at any batch size (SG_ERR_ARG on other grids) — without it a forced call
  * gets conv_dgrad_halo_kernel<1> / conv_dgrad_halo32_kernel<1>; the dispatching entries take the depth-skip form for every 64-row
- * 4^3 call.  Semantics of the depth-skip forms: see sg_conv3d_k4s2p1_fwd_impl.) */
+ * 4^3 call.  Semantics of the depth-skip forms: see sg_conv3d_k4s2p1_fwd_impl.
+ * + 128: the depth-walk form of the 8^3 -> 16^3 64-row kernel, conv_dgrad_halo_dwalk_kernel, at any batch size: dy grids of depth 8
+ * (h, w multiples of 8), Cin > 32, an even Cout / 16; SG_ERR_ARG on other shapes and together with the ppw / one-parity / + 64
+ * bits.  A workgroup walks one depth half of a sample so that every wave carries the same share of the products with the depth
+ * padding, which are not issued (1/16 of the MFMAs; semantics as the depth-skip forms, bit-equal to conv_dgrad_halo_kernel<0> for
+ * finite inputs up to the sign of a zero).  Without the bit a forced call gets conv_dgrad_halo_kernel<0> /
+ * conv_dgrad_halo32_kernel<0>; the dispatching entries take the depth-walk form where its grid has at least 512 workgroups.) */
+/* Which kernel sg_conv3d_k4s2p1_dgrad / _dgrad_keep launch for a call on tensors of exactly Cin / Cout channels (dy grid O) with a
+ * workspace of workspace_bytes: the plan the call itself makes.  Host code only, no GPU needed (addition to ABI 8, backward
+ * compatible).  SG_DGRAD_FORM_NONE: another kernel family (one-channel layers, the gather kernel). */
+#define SG_DGRAD_FORM_NONE 0
+#define SG_DGRAD_FORM_DSKIP4 1       /* conv_dgrad_halo_dskip_kernel (4^3 grids) */
+#define SG_DGRAD_FORM_ROWS32_4 2     /* conv_dgrad_halo32_kernel<1> */
+#define SG_DGRAD_FORM_ROWS64_4 3     /* conv_dgrad_halo_kernel<1> */
+#define SG_DGRAD_FORM_ROWS32 4       /* conv_dgrad_halo32_kernel<0> */
+#define SG_DGRAD_FORM_ROWS64 5       /* conv_dgrad_halo_kernel<0> */
+#define SG_DGRAD_FORM_DEPTH_WALK 6   /* conv_dgrad_halo_dwalk_kernel */
+int sg_conv3d_k4s2p1_dgrad_form(int batch, int Cin, int Cout, int OD, int OH, int OW, size_t workspace_bytes);
 /* dw[Cout, Cin_total(first Cin channels written), 4,4,4] = sum_{n,o} dy * x-patches; split-K workspace optional */
 size_t sg_conv3d_k4s2p1_wgrad_workspace_bytes(int batch, int Cin, int Cout, int OD, int OH, int OW);
 int sg_conv3d_k4s2p1_wgrad_impl(const float* dy, const float* x, float* dw, int batch, int Cin, int Cin_total, int Cx,

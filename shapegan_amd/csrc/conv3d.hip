@@ -822,12 +822,29 @@ long long sg_conv3d_k4s2p1_image_layout(int kind, const int* dims, size_t worksp
     return h ? (long long)h : 1;
 }
 
+// Which kernel sg_conv3d_k4s2p1_dgrad / _dgrad_keep launch for a call on tensors of exactly Cin / Cout channels with a workspace of
+// `workspace_bytes`: SG_DGRAD_FORM_NONE when the call goes to another kernel family (one-channel layers, the gather kernel), else
+// 1 + the HaloDgradKernel of the plan the call itself makes.  Pure host code.
+int sg_conv3d_k4s2p1_dgrad_form(int batch, int Cin, int Cout, int OD, int OH, int OW, size_t workspace_bytes) {
+    static_assert((int)HaloDgradKernel::dskip4 + 1 == SG_DGRAD_FORM_DSKIP4 && (int)HaloDgradKernel::rows32_4 + 1 == SG_DGRAD_FORM_ROWS32_4 &&
+                  (int)HaloDgradKernel::rows64_4 + 1 == SG_DGRAD_FORM_ROWS64_4 && (int)HaloDgradKernel::rows32 + 1 == SG_DGRAD_FORM_ROWS32 &&
+                  (int)HaloDgradKernel::rows64 + 1 == SG_DGRAD_FORM_ROWS64 && (int)HaloDgradKernel::rows64_dwalk + 1 == SG_DGRAD_FORM_DEPTH_WALK,
+                  "SG_DGRAD_FORM_* mirror HaloDgradKernel");
+    ConvGeom g;
+    if (batch <= 0 || Cin <= 1 || Cout <= 0 || !query_geom(g, Cin, Cout, OD, OH, OW)) return SG_DGRAD_FORM_NONE;
+    if ((long)batch * g.O3() >= (1L << 31) || (long)batch * g.I3() >= (1L << 31)) return SG_DGRAD_FORM_NONE;
+    if (edge_dgrad_plan(batch, Cin, Cout, g, workspace_bytes).served) return SG_DGRAD_FORM_NONE;
+    const HaloDgradPlan hp = halo_dgrad_plan(batch, Cin, Cout, g, workspace_bytes);
+    return hp.served ? 1 + (int)hp.kernel : SG_DGRAD_FORM_NONE;
+}
+
 // testing / tuning: impl 1 forces the LDS-halo dgrad kernel (SG_ERR_ARG if the shape is not eligible)
 int sg_conv3d_k4s2p1_dgrad_impl(const float* dy, const float* w, const float* bias, float* dx, int batch, int Cin,
                                 int Cin_total, int Cx, int Cout, int ID, int IH, int IW, int act, float slope,
                                 void* workspace, size_t workspace_bytes, int impl, hipStream_t stream) {
     // impl 1: forced, 3: one parity per workgroup, 1 + 4 ppw: ppw = 2, 4 or 8 parities; + 64: the depth-skip form of the 4^3 64-row
-    // kernel (4^3 grids only)
+    // kernel (4^3 grids only); + 128: the depth-walk form of the 64-row kernel (dy grids of depth 8, Cin > 32, an even Cout / 16; not
+    // together with the ppw / one-parity bits)
     HaloDgradForm form;
     SG_CHECK_ARG(dy && w && dx && batch > 0 && Cin > 0 && Cin <= Cin_total && Cin <= Cx && Cout > 0 &&
                  halo_dgrad_form_decode(impl, &form) && form.forced &&

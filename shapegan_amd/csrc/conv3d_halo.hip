@@ -1391,6 +1391,252 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) c
     }
 }
 
+// ---- depth-walk form of conv_dgrad_halo_kernel<0> (8^3 -> 16^3: dy grids with OD == 8, 64-row workgroups) ---------------------
+// The same MFMA (32x32x2), dy boxes (3 x 9 x 9 per channel), copy and weight pipelines, weight image (mode 0) and paired stores as
+// conv_dgrad_halo_body<0, false>; what changes is which work a workgroup and a wave own, so that the products with the DEPTH
+// padding can be left out evenly.  Plane hd of a box is dy depth qd0 - 1 + hd + pd: depth -1 only for (plane pair 0, pd 0, hd 0)
+// and depth 8 only for (plane pair 3, pd 1, hd 2) — the column tile of plane qd 0 with td 1, resp. of plane qd 7 with td 0: 2 of
+// the 32 (plane, pd, td) combinations, 1/16 of the MFMAs.  In the present form they sit in one wave (wn = plane) of the tdi 0 / 3
+// workgroups, where dropping them only makes that wave wait for its partners.  Here
+//   one workgroup = (sample, 8 x 8 h/w tile, depth half hf = blockIdx.x & 1, output parity ph = blockIdx.z) x 64 input channels;
+//   it walks the two plane pairs tdi = 2 hf, 2 hf + 1 of its half and for each (pd 0, pw 0), (pd 0, pw 1), (pd 1, pw 0), (pd 1, pw 1):
+//   8 passes of Cout / 16 stages, pw 0 / 1 adjacent (8-byte stores), exactly one (plane pair, pd) of them on a depth edge:
+//   (0, pd 0) for hf 0 — passes 0, 1 — and (3, pd 1) for hf 1 — passes 6, 7;
+//   wave (wm, wn): row half wm, h half wn (qh 0-3 / 4-7) of the tile; its two column tiles tn are the two PLANES of the pair.
+// In an edge pass the tile (tn 0, td 1) — low edge — or (tn 1, td 0) — high edge — is all padding for every wave alike: its B
+// registers are not read and its MFMAs not issued (6 of 8 per channel remain) in 2 of 8 passes: every workgroup and every wave issues 15/16
+// of the present form's MFMAs.  The stage body takes the edge as a compile-time tag (0 none, 1 low, 2 high), chosen per pass by a
+// wave-uniform branch outside the stages, which stay one basic block.
+// A B fragment depends on the box plane hd = tn + 1 - td only: (tn 0, td 0) and (tn 1, td 1) are the same two LDS words, so a channel
+// costs 6 reads (3 ds_read2_b32) instead of 8, and 4 in an edge pass.  LDS read addresses: ONE register per lane with buffer, channel,
+// plane and tap as immediate offsets (conv_dgrad_halo_dskip_kernel's scheme) instead of the 32 pinned addresses of
+// conv_dgrad_halo_body — with those the kernel needs 276 registers and loses its second wave per SIMD.  The price is one v_add_u32
+// per channel where the 8-bit offsets of the merged reads do not reach (against 6 - 8 MFMAs of 16 passes): the only VALU work of a stage.
+// Compiler gate: 238 VGPR, no AGPR, scratch 0, no VGPR spill, 2 waves/SIMD; 55.0 KB of code (conv_dgrad_halo_kernel<0>: 65.8 KB), of
+// which a workgroup runs four stage bodies (2 buffers x {inner, its edge}), against an instruction cache of 64 KB per two CUs.
+// The box of the second plane pair lies 2 OH OW floats behind the first one's: a scalar, next to pshift.  The offset | edge-class
+// words hold the offsets of the FIRST pair's box and the depth classes (bits 26, 27) of the workgroup's EDGE box (the first for
+// hf 0, the second for hf 1); the inner box has no depth padding (OD == 8), its passes mask both depth bits off.
+// Semantics: the k order of every accumulator is the present form's (co ascending, then j) and the dropped products have B = 0: for
+// finite inputs the results are bit-equal up to the sign of a zero.  A non-finite weight on a tap that meets only depth padding
+// gives NaN (0 x inf) in conv_dgrad_halo_kernel<0> and the sum over the in-range positions here, as in the other depth-skip forms.
+// The h / w padding is multiplied as before.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) conv_dgrad_halo_dwalk_kernel(HaloDgradArgs a) {
+    constexpr int NTN = 2;
+    constexpr int kDCC = 16, kDNF = 16, kDBUF = kDNF * 256;
+    using BX = DBox<0>;
+    constexpr int kDB = BX::CH;
+    extern __shared__ __attribute__((aligned(16))) float box[];  // [2][kDBUF], a buffer = [kDCC][kDB] + tail
+    const int hf = blockIdx.x & 1, ph = blockIdx.z;
+    uint32_t twi, thi, n, q1;
+    a.dntw.divmod(blockIdx.x >> 1, q1, twi);
+    a.dnth.divmod(q1, n, thi);
+    const int qd0 = hf * 4, qh0 = thi * 8, qw0 = twi * 8;      // qd0: the first plane pair of the half
+    const int qd0e = hf ? a.g.OD - 2 : 0;                      // the plane pair on the depth edge
+    const int ci0 = blockIdx.y * 64;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1, r = lane & 31, kpar = lane >> 5;
+    // lane -> position inside a 32-position column tile (4 h x 8 w of plane tn); address of tap (td,th): lanebase + tn*PL + (1-td)*PL + (1-th)*BW
+    const int lanebase = wn * BX::TNOFF + (r >> 3) * BX::BW + (r & 7) + 1 - kpar;
+
+    f32x16 acc[NTN];
+#pragma unroll
+    for (int t = 0; t < NTN; ++t)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[t][q] = 0.f;
+
+    lds_float* const bl = (lds_float*)box;
+    // one read address per lane; buffer, channel, plane and tap are immediate offsets (at most 2*kDBUF floats = 32 KB < the 16-bit field)
+    const lds_float* bb = bl + lanebase;
+    pin_vgpr(bb);
+    lds_float* sdst = bl + tid;   // element f of a stage goes to sdst[256 f] (+ buffer)
+    pin_vgpr(sdst);
+
+    const int G = a.Cout;  // one k-group per output channel
+    const unsigned par_bytes = (unsigned)(a.mtiles * 2) * (unsigned)G * 1024u;   // weight image: [parity][row tile][G][64] float4
+    const __amdgpu_buffer_rsrc_t wres = make_rsrc(a.wp + ((long)(blockIdx.y * 2 + wm) * G) * 64);
+    const unsigned wvoff = lane * 16;
+
+    // copy bookkeeping: that of conv_dgrad_halo_body<0, false> with the depth classes of the edge box (header comment)
+    const int O3 = a.g.OD * a.g.OH * a.g.OW;
+    const int obias = (a.g.OH + 1) * a.g.OW + 1;
+    const __amdgpu_buffer_rsrc_t dres = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(a.dy + (long)n * a.g.Cy * O3 - obias), 0, 1 << 26, 0x00020000);
+    const unsigned chan_bytes = (unsigned)O3 * 4u;
+    const unsigned pair_bytes = (unsigned)(2 * a.g.OH * a.g.OW) * 4u;      // box origin of the second plane pair against the first
+    unsigned gword[kDNF], goff[kDNF];
+#pragma unroll
+    for (int f = 0; f < kDNF; ++f) {
+        const int e = tid + 256 * f;
+        const int ci = e / kDB;
+        const int rem = e - ci * kDB;
+        const int hd = rem / BX::PL, hh = (rem - hd * BX::PL) / BX::BW, hw = rem % BX::BW;
+        const int od = qd0 - 1 + hd, ode = qd0e - 1 + hd, oh = qh0 - 1 + hh, ow = qw0 - 1 + hw;   // parity 0; parity bit p adds p
+        const bool never = e >= kDCC * kDB;
+        const unsigned cls = (ode < 0 ? 1u << 26 : 0u) | (ode + 1 >= a.g.OD ? 1u << 27 : 0u) | (oh < 0 ? 1u << 28 : 0u) |
+                             (oh + 1 >= a.g.OH ? 1u << 29 : 0u) | (ow < 0 ? 1u << 30 : 0u) | (ow + 1 >= a.g.OW ? 1u << 31 : 0u);
+        const int off0 = ci * O3 + (od * a.g.OH + oh) * a.g.OW + ow + obias;   // >= 0
+        gword[f] = never ? 0xffffffffu : ((unsigned)off0 * 4u) | cls;
+        pin_vgpr(gword[f]);
+    }
+    // pass i = 0 .. 7: plane pair i >> 2, pd = (i >> 1) & 1, pw = i & 1
+    unsigned pshift = 0;   // scalar byte offset of the current pass's box against (first pair, parity 0)
+    auto set_goff = [&](int i) __attribute__((always_inline)) {
+        const int pair = i >> 2, pd = (i >> 1) & 1, pw = i & 1;
+        const bool dedge = pair == hf;
+        const unsigned mask = 0x03ffffffu | (dedge ? (pd ? 1u << 27 : 1u << 26) : 0u) | (ph ? 1u << 29 : 1u << 28) | (pw ? 1u << 31 : 1u << 30);
+#pragma unroll
+        for (int f = 0; f < kDNF; ++f) goff[f] = gword[f] & mask;
+        pshift = (unsigned)((pd * a.g.OH + ph) * a.g.OW + pw) * 4u + (unsigned)pair * pair_bytes;
+    };
+    const long I3 = (long)a.g.ID * a.g.IH * a.g.IW;
+    // stores: one lane offset per plane of the FIRST pair (position of parity 0 + the kpar row); row block of 4 channels, parity and
+    // plane-pair shift in the scalar offset
+    const __amdgpu_buffer_rsrc_t ores = make_rsrc(a.dx + (long)n * a.g.Cx * I3);
+    const __amdgpu_buffer_rsrc_t bres = make_rsrc(a.bias ? a.bias : a.dx);
+    unsigned ovoff[NTN];
+#pragma unroll
+    for (int tn = 0; tn < NTN; ++tn) {
+        const int qd = qd0 + tn, qh = qh0 + wn * 4 + (r >> 3), qw = qw0 + (r & 7);
+        ovoff[tn] = (unsigned)(((2 * qd) * a.g.IH + 2 * qh) * a.g.IW + 2 * qw + 4 * kpar * (int)I3) * 4u;
+        pin_vgpr(ovoff[tn]);
+    }
+    const unsigned bvoff = kpar * 16;
+    const unsigned opair_bytes = (unsigned)(4 * a.g.IH * a.g.IW) * 4u;
+    float keep[NTN][16];
+#pragma unroll
+    for (int t = 0; t < NTN; ++t)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) keep[t][q] = 0.f;
+    auto write_pass = [&](int i) __attribute__((always_inline)) {   // dx[n][ci][2q + p] = act(acc + bias[ci]); acc = 0
+        const int pair = i >> 2, pd = (i >> 1) & 1, pw = i & 1;
+        const unsigned oshift = (unsigned)((pd * a.g.IH + ph) * a.g.IW) * 4u + (unsigned)pair * opair_bytes;   // of the (pd, ph, pw = 0) element
+        if (pw == 0) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int cis = ci0 + wm * 32 + (q & 3) + 8 * (q >> 2);
+                const float bv = a.bias && cis < a.Cin ? buf_load(bres, bvoff, (unsigned)cis * 4u) : 0.f;
+#pragma unroll
+                for (int tn = 0; tn < NTN; ++tn) keep[tn][q] = sg_apply_act(acc[tn][q] + bv, a.act, a.slope);
+            }
+        } else {      // (pw 0, pw 1) as one 8-byte piece
+            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int cis = ci0 + wm * 32 + (q & 3) + 8 * (q >> 2);   // scalar part of the channel; the lane adds 4*kpar
+                if (cis < a.Cin) {   // Cin % 8 == 0: the whole 8-channel block is in or out
+                    const float bv = a.bias ? buf_load(bres, bvoff, (unsigned)cis * 4u) : 0.f;
+#pragma unroll
+                    for (int tn = 0; tn < NTN; ++tn) {
+                        u32x2 v;
+                        v.x = __builtin_bit_cast(unsigned, keep[tn][q]);
+                        v.y = __builtin_bit_cast(unsigned, sg_apply_act(acc[tn][q] + bv, a.act, a.slope));
+                        __builtin_amdgcn_raw_buffer_store_b64(v, ores, (int)ovoff[tn], (int)((unsigned)cis * (unsigned)I3 * 4u + oshift), 0);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NTN; ++t)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[t][q] = 0.f;
+    };
+    auto pass_weights = [&](int i) __attribute__((always_inline)) {      // byte offset of pass i's parity in the weight image
+        return (unsigned)(4 * ((i >> 1) & 1) + 2 * ph + (i & 1)) * par_bytes;
+    };
+
+    set_goff(0);
+    float fv[kDNF];
+    constexpr int kRing = 8;   // <= kDCC: the ring never reaches past the next stage
+    float4 aring[kRing];
+    unsigned wcur = pass_weights(0);   // scalar byte offset of (parity, stage) in the weight image
+#pragma unroll
+    for (int f = 0; f < kDNF; ++f) fv[f] = buf_load(dres, goff[f], pshift);
+#pragma unroll
+    for (int u = 0; u < kRing; ++u) aring[u] = buf_load4(wres, wvoff, wcur + (unsigned)u * 1024u);
+#pragma unroll
+    for (int f = 0; f < kDNF; ++f) sdst[256 * f] = fv[f];
+    __syncthreads();
+
+    constexpr int O00 = BX::PL + BX::BW, O01 = BX::PL, O10 = BX::BW, O11 = 0;  // (td,th) -> box offset
+    const int nstage = a.Cout / kDCC;      // even (halo_dgrad_plan)
+    // One stage, one basic block.  EDGE: 0 every tile is issued, 1 tile (tn 0, td 1) is depth padding, 2 tile (tn 1, td 0) is.
+    auto stage = [&](auto tag, auto edgetag, unsigned dys, unsigned wnext) __attribute__((always_inline)) {
+        constexpr int CUR = decltype(tag)::value, NXT = CUR ^ 1, EDGE = decltype(edgetag)::value;
+        constexpr int kOff[4] = {O00, O01, O10, O11};
+        float bq[NTN][4];
+#pragma unroll
+        for (int tn = 0; tn < NTN; ++tn)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)      // j = 2 td + th
+                if (!((EDGE == 1 && tn == 0 && j >= 2) || (EDGE == 2 && tn == 1 && j < 2))) bq[tn][j] = bb[CUR * kDBUF + tn * BX::PL + kOff[j]];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int c = 0; c < kDCC; ++c) {  // one k-group per channel
+            const float4 a_cur = aring[c % kRing];
+            aring[c % kRing] = c + kRing < kDCC ? buf_load4(wres, wvoff, wcur + (unsigned)(c + kRing) * 1024u)
+                                                : buf_load4(wres, wvoff, wnext + (unsigned)(c + kRing - kDCC) * 1024u);
+            float b[NTN][4];
+#pragma unroll
+            for (int tn = 0; tn < NTN; ++tn)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (!((EDGE == 1 && tn == 0 && j >= 2) || (EDGE == 2 && tn == 1 && j < 2))) b[tn][j] = bq[tn][j];
+            if (c + 1 < kDCC) {
+#pragma unroll
+                for (int tn = 0; tn < NTN; ++tn)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (!((EDGE == 1 && tn == 0 && j >= 2) || (EDGE == 2 && tn == 1 && j < 2)))
+                            bq[tn][j] = bb[CUR * kDBUF + (c + 1) * kDB + tn * BX::PL + kOff[j]];
+            }
+            if (c < kDCC / 2) {  // copy of the next box: two loads per group in the first half of the stage ...
+#pragma unroll
+                for (int f = 2 * c; f < 2 * c + 2; ++f) fv[f] = buf_load(dres, goff[f], dys + pshift);
+            } else {             // ... each value goes to LDS 8 groups after its load
+#pragma unroll
+                for (int f = 2 * (c - kDCC / 2); f < 2 * (c - kDCC / 2) + 2; ++f) sdst[NXT * kDBUF + 256 * f] = fv[f];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const float av[4] = {a_cur.x, a_cur.y, a_cur.z, a_cur.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int tn = 0; tn < NTN; ++tn)
+                    if (!((EDGE == 1 && tn == 0 && j >= 2) || (EDGE == 2 && tn == 1 && j < 2)))
+                        acc[tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], b[tn][j], acc[tn], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        wcur = wnext;
+        __syncthreads();
+    };
+    auto run_pass = [&](auto edgetag, int i) __attribute__((always_inline)) {
+        const bool more = i + 1 < 8;
+        // the stage after this pass's last one: the next pass's first (new box origin) or, at the very end, the last stage again
+        // (copied into the idle buffer, never read)
+        const unsigned wlast = more ? pass_weights(i + 1) : pass_weights(i) + (unsigned)(nstage - 1) * kDCC * 1024u;
+        const unsigned dlast = more ? 0u : (unsigned)(nstage - 1) * kDCC * chan_bytes;
+        for (int s = 0; s + 1 < nstage; s += 2) {   // stages in pairs: the buffer index is a compile-time constant
+            stage(IntTag<0>(), edgetag, (unsigned)(s + 1) * kDCC * chan_bytes, wcur + kDCC * 1024u);
+            const bool last = s + 2 == nstage;
+            if (last && more) set_goff(i + 1);
+            stage(IntTag<1>(), edgetag, last ? dlast : (unsigned)(s + 2) * kDCC * chan_bytes, last ? wlast : wcur + kDCC * 1024u);
+        }
+    };
+    for (int i = 0; i < 8; ++i) {
+        const bool edge = hf ? i >= 6 : i < 2;      // wave-uniform
+        if (!edge)
+            run_pass(IntTag<0>(), i);
+        else if (hf == 0)
+            run_pass(IntTag<1>(), i);
+        else
+            run_pass(IntTag<2>(), i);
+        write_pass(i);
+    }
+}
+
 size_t halo_dgrad_workspace_bytes(int Cin, int Cout) { return (size_t)8 * ((Cin + 63) / 64) * 64 * Cout * 8 * sizeof(float); }
 
 bool halo_dgrad_form_decode(int impl, HaloDgradForm* form) {
@@ -1398,7 +1644,8 @@ bool halo_dgrad_form_decode(int impl, HaloDgradForm* form) {
     form->one_parity = (impl & 2) != 0;
     form->ppw = (impl >> 2) & 15;
     form->rows64_dskip = (impl & 64) != 0;
-    return (impl & ~127) == 0;
+    form->depth_walk = (impl & 128) != 0;
+    return (impl & ~255) == 0;
 }
 
 HaloDgradPlan halo_dgrad_plan(int batch, int Cin, int Cout, const ConvGeom& g, size_t workspace_bytes, HaloDgradForm form) {
@@ -1431,24 +1678,33 @@ HaloDgradPlan halo_dgrad_plan(int batch, int Cin, int Cout, const ConvGeom& g, s
     // depth-skip form.
     const bool dskip = mode1 && !r32 && (!form.forced || form.rows64_dskip);
     if (form.rows64_dskip && !dskip) return p;
+    // Depth-walk form of the 64-row kernel for dy grids of depth 8 (conv_dgrad_halo_dwalk_kernel: the same weight image, job kind 1).
+    // A workgroup is (sample, h/w tile, depth half, output parity ph) and walks its 2 plane pairs x (pd, pw): an even stage count as
+    // for several parities per workgroup.  Forced calls get it where they ask for it (impl bit 128, not together with the ppw /
+    // one-parity bits), the dispatch where it fills a round of two workgroups per CU (DESIGN.md section 3.1 has the measurements).
+    const long walk_tiles = (long)batch * nth * ntw * 2;      // grid x
+    const bool walk_shape = !mode1 && g.OD == 8 && Cin > 32 && (Cout / 16) % 2 == 0 && walk_tiles < (1L << 31);
+    if (form.depth_walk && (!walk_shape || form.ppw || form.one_parity || form.rows64_dskip)) return p;
+    const bool dwalk = walk_shape && (form.forced ? form.depth_walk : walk_tiles * mtiles * 2 >= 512);
     p.served = true;
     p.kernel = dskip ? HaloDgradKernel::dskip4
                      : (mode1 ? (r32 ? HaloDgradKernel::rows32_4 : HaloDgradKernel::rows64_4)
-                              : (r32 ? HaloDgradKernel::rows32 : HaloDgradKernel::rows64));
-    p.grid = dim3((unsigned)tiles, r32 ? (unsigned)((Cin + 31) / 32) : (unsigned)mtiles, 8 / ppw);
+                              : (dwalk ? HaloDgradKernel::rows64_dwalk : (r32 ? HaloDgradKernel::rows32 : HaloDgradKernel::rows64)));
+    p.grid = dwalk ? dim3((unsigned)walk_tiles, (unsigned)mtiles, 2)
+                   : dim3((unsigned)tiles, r32 ? (unsigned)((Cin + 31) / 32) : (unsigned)mtiles, 8 / ppw);
     p.block = 256;
     // registers admit 3 workgroups per CU; take 3 only when the grid then needs fewer CU-slots in total (a 2048-workgroup
     // grid is 4 full rounds at 2 per CU but 2.67 rounds at 3): otherwise a larger LDS request caps the CU at 2
     p.lds = (size_t)2 * 16 * 256 * sizeof(float);
     {
-        const long wgs = tiles * mtiles * (8 / ppw);
+        const long wgs = dwalk ? walk_tiles * mtiles * 2 : tiles * mtiles * (8 / ppw);
         const long cost2 = ((wgs + 511) / 512) * 2, cost3 = ((wgs + 767) / 768) * 3;
         if (cost2 <= cost3) p.lds = 56 * 1024;
     }
     p.image = ImageJob{dskip ? 3 : 1, mtiles * 2, 0};
     p.workspace_need = halo_dgrad_workspace_bytes(Cin, Cout);
     p.mtiles = mtiles;
-    p.ppw = ppw;
+    p.ppw = dwalk ? 8 : ppw;      // (the depth walk: 8 passes per workgroup)
     p.ntd = ntd;
     p.nth = nth;
     p.ntw = ntw;
@@ -1502,6 +1758,9 @@ void halo_dgrad_launch(const HaloDgradPlan& p, const float* dy, const float* bia
         break;
     case HaloDgradKernel::rows64:
         hipLaunchKernelGGL((conv_dgrad_halo_kernel<0>), p.grid, dim3(p.block), p.lds, stream, a);
+        break;
+    case HaloDgradKernel::rows64_dwalk:
+        hipLaunchKernelGGL(conv_dgrad_halo_dwalk_kernel, p.grid, dim3(p.block), p.lds, stream, a);
         break;
     }
 }

@@ -117,6 +117,7 @@ struct HaloDgradForm {
     bool one_parity;     // impl bit 1 (impl 3): one output parity per workgroup
     int ppw;             // impl bits 2-5 (impl 1 + 4 ppw): 2, 4 or 8 parities per workgroup
     bool rows64_dskip;   // impl bit 6: 64-row workgroups at any size, in the depth-skip form (4^3 grids only)
+    bool depth_walk;     // impl bit 7: 64-row workgroups at any size, in the depth-walk form (dy grids of depth 8 only)
 };
 bool halo_dgrad_form_decode(int impl, HaloDgradForm* form);      // false: bits the ABI does not define
 
@@ -136,7 +137,8 @@ void halo_fwd_launch(const HaloFwdPlan& p, const float* x, const float* bias, fl
                      int act, float slope, void* workspace, hipStream_t stream);
 
 size_t halo_dgrad_workspace_bytes(int Cin, int Cout);     // the input-gradient weight image
-enum class HaloDgradKernel { dskip4, rows32_4, rows64_4, rows32, rows64 };      // (_4: the 4^3 box of two samples)
+// (_4: the 4^3 box of two samples; rows64_dwalk: the depth-walk form for dy grids of depth 8; SG_DGRAD_FORM_* of the ABI = 1 + these values)
+enum class HaloDgradKernel { dskip4, rows32_4, rows64_4, rows32, rows64, rows64_dwalk };
 struct HaloDgradPlan : KernelPlan {
     HaloDgradKernel kernel;
     ImageJob image;

@@ -185,6 +185,9 @@ int sg_conv3d_k4s2p1_dgrad_keep_cpu(const float* dy, const float* w, const float
                                     size_t wb, int, void* st) {     // (nothing is packed here: nothing to keep)
     return sg_conv3d_k4s2p1_dgrad_cpu(dy, w, bias, dx, batch, Cin, Cin_total, Cx, Cout, ID, IH, IW, act, slope, ws, wb, st);
 }
+int sg_conv3d_k4s2p1_dgrad_form_cpu(int, int, int, int, int, int, size_t) {     // (one loop nest serves every shape: no kernel forms here)
+    return 0;      // SG_DGRAD_FORM_NONE
+}
 int sg_conv3d_k4s2p1_fwd_keep_cpu(const float* x, const float* w, const float* bias, float* y, int batch, int Cin, int Cin_total,
                                   int Cx, int Cout, int ID, int IH, int IW, int act, float slope, void* ws, size_t wb, int, void* st) {
     return sg_conv3d_k4s2p1_fwd_cpu(x, w, bias, y, batch, Cin, Cin_total, Cx, Cout, ID, IH, IW, act, slope, ws, wb, st);

@@ -216,6 +216,14 @@ def conv_dgrad_halo_raw(dy, w, bias, cin, act=ACT_NONE, slope=0.0, impl=1):
     return dx
 
 
+def conv_dgrad_form(batch, cin, cout, ogrid):
+    """Which kernel conv_dgrad_raw launches for dy [batch, cout, *ogrid] -> dx of cin channels, with the workspace conv_dgrad_raw gives
+    the call: one of the SG_DGRAD_FORM_* values of include/shapegan_hip.h (0: not an LDS-halo kernel).  Host code, no GPU needed."""
+    lib = L._load_hip()      # (the HIP library's own answer: the twin has one loop nest and no forms)
+    nb = lib.sg_conv3d_k4s2p1_dgrad_workspace_bytes_for(batch, cin, cout, *ogrid)
+    return lib.sg_conv3d_k4s2p1_dgrad_form(batch, cin, cout, *ogrid, nb)
+
+
 _WGRAD_WS_CAP = 256 << 20
 
 
