@@ -364,6 +364,31 @@ int sg_sdfnet_latent_grad(const float* points, const float* target, const int64_
 int sg_sdfnet_latent_reduce(const float* partials, const int64_t* tile_off, const int64_t* seg_off, long nshapes, long win_count,
                             float* t1, float* t5, float* loss, hipStream_t stream);
 
+/* ---- K7e: the pose of a cloud fitted together with its latent code (csrc/latent_pose_fit.hip; serves shapegan_amd/reconstruct.py
+ * fit_codes_and_poses and SDFNet.latent_pose_loss_and_grad).  Additions to ABI 8, backward compatible.  Everything K7c says about
+ * points, target, seg_off, the window, tiles and tile_off holds; `points` are OBSERVED coordinates q, and shape s carries
+ * pose [S][16] (floats): floats 0..11 a row-major 3x4 affine A|t that maps q to canonical x = A q + t, float 12 the target scale ts,
+ * floats 13..15 ignored.
+ * sg_sdfnet_latent_pose_grad: one launch; per tile, in float32 and in this order,
+ *     x_c = fma(A_c0, qx, fma(A_c1, qy, fma(A_c2, qz, t_c)))      (c = 0, 1, 2)
+ *   then K7c at x with target' = clamp(ts * target, +-cutoff): out = tanh(v), d = out - target', dz8 = sign(d) (1 - out^2) / m_s, the
+ *   chain back, and the point gradient of K7d, g = W5[:, 256:259]^T dZ5 + W1[:, 0:3]^T dZ1, which stays on the chip; per point also
+ *   e = -sign(d) target / m_s where -cutoff < ts * target < cutoff, else 0.
+ *   partials [T][SG_SDFNET_POSE_PARTIAL_ROW]: floats [0, 513) as K7c's row; [513, 522) sum_p g_c q_j, row-major (c, j): d loss / dA;
+ *   [522, 525) sum_p g_c: d loss / dt; 525 sum_p e: d loss / d ts; 526, 527 zero.  Every row is written in full, the row of a tile
+ *   that names nothing (all zeros) included; every sum has a fixed order, so a shape's rows do not depend on the other shapes of the
+ *   call.  With the identity pose and ts = 1, floats [0, 513) equal sg_sdfnet_latent_grad's bit for bit.
+ * sg_sdfnet_latent_pose_reduce: t1, t5, loss as sg_sdfnet_latent_reduce, and gpose [nshapes][16]: floats 0..11 the gradient of
+ *   loss_s with respect to A|t in pose's layout, float 12 with respect to ts, floats 13..15 zero; a shape's tiles are added in tile
+ *   order in double.
+ * SG_ERR_ARG before any launch: a NULL pointer, nshapes < 1, ntiles < 1 or >= 2^31, win_start < 0, cutoff < 0. */
+#define SG_SDFNET_POSE_PARTIAL_ROW 528 /* 513 + 9 + 3 + 1 + 2 */
+int sg_sdfnet_latent_pose_grad(const float* points, const float* target, const int64_t* seg_off, long nshapes, const float* zb1,
+                               const float* zb5, const float* packed, const float* pose, float cutoff, long win_start,
+                               long win_count, const int* tiles, long ntiles, float* partials, hipStream_t stream);
+int sg_sdfnet_latent_pose_reduce(const float* partials, const int64_t* tile_off, const int64_t* seg_off, long nshapes,
+                                 long win_count, float* t1, float* t5, float* loss, float* gpose, hipStream_t stream);
+
 /* ---- K7d: points onto a level set of a frozen SDFNet — value, point gradient and Newton steps of a tile in one launch (serves
  * SDFNet.sdf_and_gradient / project_to_level_set and shapegan_amd/surface.py: exact normals, refined meshes, oriented surface
  * clouds).  The reference takes normals and surface points from autograd with respect to the points and one first-order step that

@@ -103,6 +103,21 @@ class SDFNet(SavableModule):
             return fit.step(latent_table, start, count, sigma)
         return ops.latent_step_composed(self._pack_shapes, self._params(), points, sdf, latent_table, off, cutoff, sigma, start, count)
 
+    def latent_pose_loss_and_grad(self, points, sdf, latent_table, poses, segment_offsets, cutoff=0.1, sigma=0.0, window=None):
+        """latent_loss_and_grad for clouds in their own frame: points [N,3] are OBSERVED coordinates q and poses [S,16] hold, per
+        shape, the row-major 3x4 affine A|t to the canonical frame (x = A q + t) and at float 12 the scale ts of the targets ->
+            loss [S]         = mean_p |SDFNet(A q_p + t, z_s) - clamp(ts sdf_p, +-cutoff)|
+            grad_z [S,L]     = d/dz_s (loss_s + sigma * mean_k z_{s,k}^2)
+            grad_pose [S,16] = d loss_s / d poses[s] (floats 13..15 zero).
+        One fused launch per chunk of shapes (csrc/latent_pose_fit.hip); the point gradient it contracts never leaves the chip."""
+        off = ops.check_segments(points, sdf, latent_table, segment_offsets)
+        ops.check_poses(poses, latent_table.shape[0], points.device)
+        start, count = (0, 0) if window is None else (int(window[0]), int(window[1]))
+        if start < 0:
+            raise ValueError("the window starts at %d" % start)
+        fit = ops.LatentPoseFit(self._pack_shapes, self._params(), points, sdf, segment_offsets, off, cutoff)
+        return fit.step(latent_table, poses, start, count, sigma)
+
     def surface_projector(self, latent_codes):
         """ops.SurfaceProjector for these codes [S,L] (or one code [L]): weight image and latent fold made once, for callers that
         project many batches of points onto the same shapes."""

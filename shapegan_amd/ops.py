@@ -1395,16 +1395,22 @@ class LatentFit(object):
             self.plans[count] = plan
         return plan
 
-    def step(self, z, start, count, sigma):
+    def _run(self, z, pose, start, count, sigma):
+        """The step of LatentFit (pose None) and of LatentPoseFit: the chunks, the latent fold and its backward are the same, the
+        two launches in between and their row length differ.  -> (loss [S], grad [S, L], grad_pose [S, 16] or None)."""
         if start < 0:
             raise ValueError("the window starts at %d" % start)
         z = f32c(z.detach())
         if tuple(z.shape) != (self.S, self.L):
             raise ValueError("latent_table must be [%d, %d], got %s" % (self.S, self.L, tuple(z.shape)))
+        if pose is not None:
+            check_poses(pose, self.S, self.dev)
+            pose = f32c(pose.detach())
         lib = _lib()
         w1, b1, w5, b5 = self.params[0], self.params[1], self.params[8], self.params[9]
         loss = torch.empty(self.S, dtype=torch.float32, device=self.dev)
         grad = torch.empty((self.S, self.L), dtype=torch.float32, device=self.dev)
+        gpose = None if pose is None else torch.empty((self.S, 16), dtype=torch.float32, device=self.dev)
         for a, b, tiles, tile_off, ntiles in self._plan(int(count)):
             S = b - a
             zc, so = z[a:b], self.seg_off[a:b + 1]
@@ -1412,17 +1418,54 @@ class LatentFit(object):
             zb5 = torch.empty((S, _H), dtype=torch.float32, device=self.dev)
             check(lib.sg_sdfnet_shape_bias(ptr(zc), S, self.L, ptr(w1), ptr(b1), ptr(w5), ptr(b5), ptr(zb1), ptr(zb5), stream()),
                   "sdfnet_shape_bias")
-            part = torch.empty((ntiles, _LATENT_ROW), dtype=torch.float32, device=self.dev)
-            check(lib.sg_sdfnet_latent_grad(ptr(self.points), ptr(self.sdf), ptr(so), S, ptr(zb1), ptr(zb5), ptr(self.packed),
-                                            self.cutoff, int(start), int(count), ptr(tiles), ntiles, ptr(part), stream()),
-                  "sdfnet_latent_grad")
+            part = torch.empty((ntiles, _LATENT_ROW if pose is None else _POSE_ROW), dtype=torch.float32, device=self.dev)
+            if pose is None:
+                check(lib.sg_sdfnet_latent_grad(ptr(self.points), ptr(self.sdf), ptr(so), S, ptr(zb1), ptr(zb5), ptr(self.packed),
+                                                self.cutoff, int(start), int(count), ptr(tiles), ntiles, ptr(part), stream()),
+                      "sdfnet_latent_grad")
+            else:
+                check(lib.sg_sdfnet_latent_pose_grad(ptr(self.points), ptr(self.sdf), ptr(so), S, ptr(zb1), ptr(zb5), ptr(self.packed),
+                                                     ptr(pose[a:b]), self.cutoff, int(start), int(count), ptr(tiles), ntiles,
+                                                     ptr(part), stream()), "sdfnet_latent_pose_grad")
             t1 = torch.empty((_H, S), dtype=torch.float32, device=self.dev)
             t5 = torch.empty((_H, S), dtype=torch.float32, device=self.dev)
-            check(lib.sg_sdfnet_latent_reduce(ptr(part), ptr(tile_off), ptr(so), S, int(count), ptr(t1), ptr(t5), ptr(loss[a:b]),
-                                              stream()), "sdfnet_latent_reduce")
+            if pose is None:
+                check(lib.sg_sdfnet_latent_reduce(ptr(part), ptr(tile_off), ptr(so), S, int(count), ptr(t1), ptr(t5), ptr(loss[a:b]),
+                                                  stream()), "sdfnet_latent_reduce")
+            else:
+                check(lib.sg_sdfnet_latent_pose_reduce(ptr(part), ptr(tile_off), ptr(so), S, int(count), ptr(t1), ptr(t5),
+                                                       ptr(loss[a:b]), ptr(gpose[a:b]), stream()), "sdfnet_latent_pose_reduce")
             check(lib.sg_sdfnet_shape_bias_bwd(ptr(t1), ptr(t5), S, ptr(zc), self.L, ptr(w1), ptr(w5), None, None, ptr(grad[a:b]),
                                                None, 2.0 * float(sigma) / self.L, stream()), "sdfnet_shape_bias_bwd")
-        return loss, grad
+        return loss, grad, gpose
+
+    def step(self, z, start, count, sigma):
+        return self._run(z, None, start, count, sigma)[:2]
+
+
+_POSE_ROW = L.abi.DEFINES["SG_SDFNET_POSE_PARTIAL_ROW"]      # _LATENT_ROW + 9 + 3 + 1 + 2
+
+
+def check_poses(pose, nshapes, device=None):
+    """The argument checks of the pose step, before anything is launched: float pose rows [S, 16], on the fit's device."""
+    if pose.dim() != 2 or tuple(pose.shape) != (nshapes, 16):
+        raise ValueError("pose must be [S, 16] = [%d, 16], got %s" % (nshapes, tuple(pose.shape)))
+    if not pose.dtype.is_floating_point:
+        raise ValueError("pose must be a floating-point tensor, got %s" % pose.dtype)
+    if device is not None and pose.device != device:
+        raise ValueError("pose is on %s, the points on %s" % (pose.device, device))
+
+
+class LatentPoseFit(LatentFit):
+    """LatentFit with a pose per shape (csrc/latent_pose_fit.hip): the points are observed coordinates q, pose [S, 16] holds the
+    row-major 3x4 affine A|t to canonical x = A q + t and, at float 12, the scale ts of the targets.  The same plan, chunking and
+    launches around the two pose entry points (LatentFit._run).
+    step(z, pose, start, count, sigma) -> (loss [S], grad_z [S, L], grad_pose [S, 16]): grad_pose in pose's layout, floats 13..15 zero."""
+
+    def step(self, z, pose, start, count, sigma):
+        if pose is None:
+            raise ValueError("pose must be [S, 16], got None")
+        return self._run(z, pose, start, count, sigma)
 
 
 # ---- points onto a level set: value, point gradient and Newton steps with the weights frozen (csrc/sdfnet_project.hip) -------------
