@@ -364,7 +364,7 @@ int sg_sdfnet_latent_grad(const float* points, const float* target, const int64_
 int sg_sdfnet_latent_reduce(const float* partials, const int64_t* tile_off, const int64_t* seg_off, long nshapes, long win_count,
                             float* t1, float* t5, float* loss, hipStream_t stream);
 
-/* ---- K7e: the pose of a cloud fitted together with its latent code (csrc/latent_pose_fit.hip; serves shapegan_amd/reconstruct.py
+/* ---- K7e: the pose of a cloud fitted together with its latent code (csrc/latent_fit.hip; serves shapegan_amd/reconstruct.py
  * fit_codes_and_poses and SDFNet.latent_pose_loss_and_grad).  Additions to ABI 8, backward compatible.  Everything K7c says about
  * points, target, seg_off, the window, tiles and tile_off holds; `points` are OBSERVED coordinates q, and shape s carries
  * pose [S][16] (floats): floats 0..11 a row-major 3x4 affine A|t that maps q to canonical x = A q + t, float 12 the target scale ts,

@@ -1,4 +1,4 @@
-"""One iteration of the pose fit (shapegan_amd/reconstruct.py fit_codes_and_poses, csrc/latent_pose_fit.hip) on the GPU with the seeded
+"""One iteration of the pose fit (shapegan_amd/reconstruct.py fit_codes_and_poses, csrc/latent_fit.hip) on the GPU with the seeded
 chairs weights; prints one JSON line.
 
     python scripts/pose_fit_bench.py [--iters 100] [--rounds 3]

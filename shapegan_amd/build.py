@@ -21,7 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libshapegan_hip.so")
-SOURCES = ["conv3d.hip", "conv3d_halo.hip", "conv3d_edge.hip", "gemm.hip", "sdfnet.hip", "latent_fit.hip", "latent_pose_fit.hip", "sdfnet_project.hip", "batchnorm.hip", "elementwise.hip", "pointnet.hip", "losses.hip", "sdf_batch.hip", "head.hip", "mesh.hip", "raymarch.hip", "pointcloud.hip", "raster.hip", "emd.hip", "meshsdf.hip", "tsne.hip", "brickgrid.hip", "topology.hip", "simplify.hip", "cloud.hip", "spline.hip", "edt.hip"]
+SOURCES = ["conv3d.hip", "conv3d_halo.hip", "conv3d_edge.hip", "gemm.hip", "sdfnet.hip", "latent_fit.hip", "sdfnet_project.hip", "batchnorm.hip", "elementwise.hip", "pointnet.hip", "losses.hip", "sdf_batch.hip", "head.hip", "mesh.hip", "raymarch.hip", "pointcloud.hip", "raster.hip", "emd.hip", "meshsdf.hip", "tsne.hip", "brickgrid.hip", "topology.hip", "simplify.hip", "cloud.hip", "spline.hip", "edt.hip"]
 ABI_HEADER = abi.HEADER
 # the arithmetic the HIP kernels share with the twin: an edit rebuilds both libraries
 CORE_HEADERS = [os.path.join(CSRC, h) for h in ("core_fn.h", "mc_tables.h", "mesh_core.h", "raymarch_core.h", "pointcloud_core.h", "raster_core.h", "meshsdf_core.h", "tsne_core.h", "brickgrid_core.h", "project_core.h", "topology_core.h", "simplify_core.h", "cloud_core.h", "spline_core.h", "edt_core.h")]

@@ -1,8 +1,9 @@
 // shapegan_amd/csrc/sdfnet_frozen.h — SDFNet with FROZEN weights on a 32-point tile of one shape, per-shape bias mode: what the latent
-// fit (latent_fit.hip, K7c) and the level-set projection (sdfnet_project.hip, K7d) share.  Both run sdfnet_fwd_tile with KEEP, hold the
-// seven sign words a lane produces in registers instead of storing them, and walk the chain back through the transposed packs of the
-// same weight image, dZ_l = (T_{l+1} dZ_{l+1}) * ReLU'(H_l), in the forward's own [256][P] LDS tile.  They differ in the epilogue of
-// the forward (Io::store: what dz8 is) and in what they do with dZ5 and dZ1 (the functor of sdfnet_frozen_bwd_tile).
+// fit without and with a pose (latent_fit.hip, K7c and K7e) and the level-set projection (sdfnet_project.hip, K7d) share.  All run
+// sdfnet_fwd_tile with KEEP, hold the seven sign words a lane produces in registers instead of storing them, and walk the chain back
+// through the transposed packs of the same weight image, dZ_l = (T_{l+1} dZ_{l+1}) * ReLU'(H_l), in the forward's own [256][P] LDS tile.
+// They differ in the epilogue of the forward (Io::store: what dz8 is) and in what they do with dZ5 and dZ1 (the functor of
+// sdfnet_frozen_bwd_tile): row sums over the tile's points (the fit), the point gradient (SdfPointGrad: K7d and K7e), or both.
 #pragma once
 #include "sdfnet_tile.h"
 
@@ -32,6 +33,25 @@ __device__ __forceinline__ SdfTileRow sdf_tile_row(const int* tiles, const int64
         t.n = seg_off[t.s + 1] - t.beg;
     }
     return t;
+}
+
+// The points of a row's tile that a call uses.  Shape s uses m = n or min(win_count, n) of its points, the i-th being
+// beg + (win_start + i) mod n (a window that wraps around the cloud); the tile holds cnt <= P of them from i0 on, cnt <= 0 for a row that
+// names nothing.  m is the divisor of the shape's mean.
+struct SdfTileWindow {
+    long beg, n, m, cnt, first;      // first = (win_start + i0) mod n
+    __device__ __forceinline__ long index(long gp) const {
+        const long i = first + gp;      // (gp < cnt <= n and first < n: one wrap at most)
+        return beg + (i >= n ? i - n : i);
+    }
+};
+__device__ __forceinline__ SdfTileWindow sdf_tile_window(const SdfTileRow& row, long win_start, long win_count, int P) {
+    SdfTileWindow w{row.beg, row.n, 0, 0, 0};
+    w.m = row.n <= 0 ? 0 : (win_count <= 0 || win_count > row.n ? row.n : win_count);
+    w.cnt = row.i0 < 0 ? 0 : w.m - row.i0;
+    if (w.cnt > P) w.cnt = P;
+    if (w.cnt > 0) w.first = (win_start + row.i0) % row.n;
+    return w;
 }
 
 // The forward's arguments for one tile of `cnt` points that takes its bias rows from zb1 / zb5 directly (shape = p0 / pps = 0), stores
@@ -119,5 +139,48 @@ __device__ __forceinline__ void sdfnet_frozen_bwd_tile(const float* packed, cons
         if (i > 0) __syncthreads();
     }
 }
+
+// The point gradient of a tile, g[p] = W5[:, 256:259]^T dZ5[:, p] + W1[:, 0:3]^T dZ1[:, p]: every lane multiplies the 16 rows of dZ5
+// (later dZ1) it holds for its point by the matching rows of the point columns — K split over the eight waves, VALU, while the tile
+// still holds the image.  The forward's bias vectors (7 KB behind H, X and the layer-8 partials) are dead once its last GEMM has
+// started and are staged again by every forward: the chain back keeps the point columns there, Wx[2][256][3].
+static_assert(2 * kH * 3 <= 7 * kH, "the point columns fit where the forward keeps its biases");
+template <int P>
+struct SdfPointGrad {
+    float* Wx;
+    const lds_float* wxw;               // the rows of this lane's elements of the tile: wave * 32 + frag_row(q, kh)
+    float gx = 0.f, gy = 0.f, gz = 0.f;      // this lane's 16 rows of W5x^T dZ5 + W1x^T dZ1 for point lane & 31
+    __device__ __forceinline__ SdfPointGrad(float* smem, const SdfPackLayout& lay)
+        : Wx(smem + kH * P + lay.KUp * (P + 1) + 16 * P),
+          wxw((const lds_float*)Wx + ((threadIdx.x >> 6) * 32 + 4 * ((threadIdx.x & 63) >> 5)) * 3) {}
+    // by the whole workgroup between the forward and the barrier in front of sdfnet_frozen_bwd_tile
+    __device__ __forceinline__ void stage(const float* packed, const SdfPackLayout& lay) const {
+        // element M(c, k) of a transposed 32-row pack (pack_mfma_a_kernel): ((k >> 3) * 64 + c + 32 (k & 1)) * 4 + ((k >> 1) & 3)
+        for (int e = threadIdx.x; e < 2 * kH * 3; e += 512) {
+            const int l = e / (kH * 3), k = (e - l * kH * 3) / 3, c = e % 3;
+            Wx[e] = packed[(l ? lay.T5i : lay.T1) + ((k >> 3) * 64 + c + 32 * (k & 1)) * 4 + ((k >> 1) & 3)];
+        }
+    }
+    // from the chain's functor, for the elements of images i == 4 (dZ5) and i == 0 (dZ1)
+    __device__ __forceinline__ void add(int i, int q, float g) {
+        const lds_float* w = wxw + (i == 0 ? 0 : kH * 3) + frag_rowoff(q) * 3;
+        gx = __builtin_fmaf(w[0], g, gx);
+        gy = __builtin_fmaf(w[1], g, gy);
+        gz = __builtin_fmaf(w[2], g, gz);
+    }
+    // The two half-waves hold rows 4 kh + {0..3, 8..11, ...} of the same point; their sum goes to gp [8][3][P] (LDS), which the
+    // caller adds in wave order behind a barrier.
+    __device__ __forceinline__ void partials(float* gp) {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31;
+        gx += __shfl_xor(gx, 32, 64);
+        gy += __shfl_xor(gy, 32, 64);
+        gz += __shfl_xor(gz, 32, 64);
+        if (lane < 32) {
+            gp[(wave * 3 + 0) * P + r] = gx;
+            gp[(wave * 3 + 1) * P + r] = gy;
+            gp[(wave * 3 + 2) * P + r] = gz;
+        }
+    }
+};
 
 }  // namespace sg

@@ -12,9 +12,9 @@
 //      an LDS xyz[32][3] the tile owns, the seven sign words kept in registers;
 //   2. out = tanh(v), dz8 = 1 - out^2, and the chain back through the transposed packs: sdfnet_frozen_bwd_tile (sdfnet_frozen.h), the
 //      one K7c runs — that header also has the sign keeping, the table row and the forward's arguments;
-//   3. the two products above: every lane multiplies the 16 rows of dZ5 (later dZ1) it holds for its point by the matching rows of
-//      the point columns — K split over the eight waves, VALU, while the tile still holds the image —, the two half-waves are added
-//      and the eight waves' [3][32] partials meet in LDS, summed in wave order;
+//   3. the two products above (SdfPointGrad in the same header, shared with the pose fit of latent_fit.hip): every lane multiplies the
+//      16 rows of dZ5 (later dZ1) it holds for its point by the matching rows of the point columns, the two half-waves are added and
+//      the eight waves' [3][32] partials meet in LDS, summed in wave order;
 //   4. on all rounds but the last, the step of project_core.h on xyz.
 // Memory traffic: 12 B in and 28 B out per point, whatever the number of rounds.  There is no reduction across points: the k order of a
 // point's sums is fixed (q within the lane, half-wave, wave), so its outputs do not depend on the rest of the call or on its place.
@@ -63,8 +63,7 @@ template <int P>
 __global__ void __launch_bounds__(512, 4) sdfnet_project_kernel(ProjectArgs f) {
     __shared__ float s_xyz[P * 3], s_out[P], s_dz8[P], s_gp[8 * 3 * P];
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int kh = lane >> 5, r = lane & 31;
+    const int tid = threadIdx.x;
     const SdfTileRow row = sdf_tile_row(f.tiles, f.seg_off, f.S, blockIdx.x);
     const int s = row.s;
     long cnt = row.i0 < 0 ? 0 : row.n - row.i0;
@@ -86,12 +85,6 @@ __global__ void __launch_bounds__(512, 4) sdfnet_project_kernel(ProjectArgs f) {
     // (packed / zb1 / zb5 are set by every round, below)
     SdfFwdArgs a = sdf_frozen_tile_args(f.points, nullptr, f.lay, nullptr, nullptr, cnt);
 
-    // the forward's bias vectors (7 KB behind H, X and the layer-8 partials) are dead once its last GEMM has started and are staged
-    // again by every forward: the backward keeps the point columns of W1 / W5 there, Wx[2][256][3]
-    float* const Wx = smem + kH * P + f.lay.KUp * (P + 1) + 16 * P;
-    // the rows of this lane's elements of the tile: wave * 32 + frag_row(q, kh)
-    const lds_float* const wxw = (const lds_float*)Wx + (wave * 32 + 4 * kh) * 3;
-
 #pragma unroll 1
     for (int round = 0;; ++round) {
         // (the rounds load the same weights and biases: pointers the compiler cannot see through keep it from hoisting those loads out
@@ -104,33 +97,16 @@ __global__ void __launch_bounds__(512, 4) sdfnet_project_kernel(ProjectArgs f) {
 #pragma unroll
         for (int e = 0; e < 7; ++e) signs[e] = 0u;
         sdfnet_fwd_tile<P, true, false, false, ProjectIo, true>(a, 0, io);
-        // element M(c, k) of a transposed 32-row pack (pack_mfma_a_kernel): ((k >> 3) * 64 + c + 32 (k & 1)) * 4 + ((k >> 1) & 3)
-        for (int e = tid; e < 2 * kH * 3; e += 512) {
-            const int l = e / (kH * 3), k = (e - l * kH * 3) / 3, c = e % 3;
-            Wx[e] = packed[(l ? f.lay.T5i : f.lay.T1) + ((k >> 3) * 64 + c + 32 * (k & 1)) * 4 + ((k >> 1) & 3)];
-        }
+        SdfPointGrad<P> pg(smem, f.lay);
+        pg.stage(packed, f.lay);      // (through this round's opaque pointer)
         __syncthreads();      // out / dz8 of every point and Wx are in LDS, every read of H7 is done
 
-        // the chain back (sdfnet_frozen.h); dZ5 and dZ1 are the images behind the point gradient
-        float gx = 0.f, gy = 0.f, gz = 0.f;      // this lane's 16 rows of W5x^T dZ5 + W1x^T dZ1 for point r
+        // the chain back and the point gradient (sdfnet_frozen.h); dZ5 and dZ1 are the images behind it
         sdfnet_frozen_bwd_tile<P>(packed, f.lay, smem, signs[0], signs[1], signs[2], signs[3], signs[4], signs[5], signs[6], s_dz8,
                                   [&](int i, int q, float g) __attribute__((always_inline)) {
-                                      if (i == 4 || i == 0) {
-                                          const lds_float* w = wxw + (i == 0 ? 0 : kH * 3) + frag_rowoff(q) * 3;
-                                          gx = __builtin_fmaf(w[0], g, gx);
-                                          gy = __builtin_fmaf(w[1], g, gy);
-                                          gz = __builtin_fmaf(w[2], g, gz);
-                                      }
+                                      if (i == 4 || i == 0) pg.add(i, q, g);
                                   });
-        // the two half-waves hold rows 4 kh + {0..3, 8..11, ...} of the same point; then the eight waves in wave order
-        gx += __shfl_xor(gx, 32, 64);
-        gy += __shfl_xor(gy, 32, 64);
-        gz += __shfl_xor(gz, 32, 64);
-        if (kh == 0) {
-            s_gp[(wave * 3 + 0) * P + r] = gx;
-            s_gp[(wave * 3 + 1) * P + r] = gy;
-            s_gp[(wave * 3 + 2) * P + r] = gz;
-        }
+        pg.partials(s_gp);      // the two half-waves; then the eight waves in wave order
         __syncthreads();
         const bool last = round == f.iterations;
         if (tid < P) {
@@ -165,8 +141,6 @@ __global__ void __launch_bounds__(512, 4) sdfnet_project_kernel(ProjectArgs f) {
         __syncthreads();      // the next forward stages the moved points
     }
 }
-
-static_assert(2 * kH * 3 <= 7 * kH, "the point columns fit where the forward keeps its biases");
 
 }  // namespace sg
 

@@ -706,6 +706,15 @@ static void sdf_shape_point_chain(const CpuSdf& v, const float (*h)[256], float 
         if (layer == 4) on_dz5(g);
     }
 }
+// the chain and the point gradient gp[3] = W5[:, 256:259]^T dZ5 + W1[:, 0:3]^T dZ1 of its upstream gradient
+template <class OnDz5>
+static void sdf_shape_point_grad(const CpuSdf& v, const float (*h)[256], float d8, float* g, float* gp, OnDz5 on_dz5) {
+    sdf_shape_point_chain(v, h, d8, g, [&](const float* dz5) {
+        on_dz5(dz5);
+        dense_t(v.W5i, 3, dz5, gp, false);
+    });
+    dense_t(v.W1k, 3, g, gp, true);
+}
 }
 // the header's tile layout of the backward partials (sg_sdfnet_bwd_blocks / sg_sdfnet_bwd_tile_start)
 static void sdf_bwd_plan(long N, long& nbig, long& nsmall) {
@@ -894,154 +903,131 @@ int sg_sdfnet_bwd_finish_cpu(const float* dz, const float* bias_partials, long l
     return SG_OK;
 }
 
-// ---- K7c: loss and latent-only gradient with frozen weights (header: sg_sdfnet_latent_grad / sg_sdfnet_latent_reduce) -------------
+// ---- K7c / K7e: loss and latent-only gradient with frozen weights, without and with a pose (header: sg_sdfnet_latent_grad /
+// sg_sdfnet_latent_reduce, sg_sdfnet_latent_pose_grad / sg_sdfnet_latent_pose_reduce; csrc/latent_fit.hip) ------------------------------
 // Per tile of the caller's table: the forward of sg_sdfnet_fwd_cpu point by point (the same `dense` calls in the same order, so a
 // target made by that forward gives d == 0 exactly), the upstream gradient of the header, the chain of sg_sdfnet_bwd_cpu, and the
-// tile's row sums of dZ1 / dZ5 and sum of |d|.
-int sg_sdfnet_latent_grad_cpu(const float* points, const float* target, const int64_t* seg_off, long nshapes, const float* zb1,
-                              const float* zb5, const float* packed, float cutoff, long win_start, long win_count,
-                              const int* tiles, long ntiles, float* partials, void*) {
-    CPU_CHECK(points && target && seg_off && zb1 && zb5 && packed && tiles && partials);
-    CPU_CHECK(nshapes >= 1 && win_start >= 0 && ntiles >= 1 && cutoff >= 0.f);
-    for (long s = 0; s < nshapes; ++s) CPU_CHECK(seg_off[s + 1] - seg_off[s] >= 1);
+// tile's row sums of dZ1 / dZ5 and sum of |d|.  With a pose the same loop at x = A q + t (the header's fma order) with target' =
+// clamp(ts target), and the point gradient as in sg_sdfnet_project_cpu, contracted with q per tile in point order.  Without one x is
+// the point itself: one body, so the identity pose with ts = 1 gives floats [0, 513) of the row without a pose bit for bit.
+extern "C++" {
+template <bool POSE>
+static void sdf_latent_grad_tiles(const float* points, const float* target, const int64_t* seg_off, long nshapes, const float* zb1,
+                                  const float* zb5, const float* packed, const float* pose, float cutoff, long win_start,
+                                  long win_count, const int* tiles, long ntiles, float* partials) {
+    constexpr int ROW = POSE ? SG_SDFNET_POSE_PARTIAL_ROW : SG_SDFNET_LATENT_PARTIAL_ROW;
     const CpuSdf v = sdf_view(packed, 3);
 #pragma omp parallel for schedule(dynamic)
     for (long t = 0; t < ntiles; ++t) {
-        float* prow = partials + t * SG_SDFNET_LATENT_PARTIAL_ROW;
-        for (int e = 0; e < SG_SDFNET_LATENT_PARTIAL_ROW; ++e) prow[e] = 0.f;
+        float* prow = partials + t * ROW;
+        for (int e = 0; e < ROW; ++e) prow[e] = 0.f;
         const long s = tiles[2 * t], i0 = tiles[2 * t + 1];
         if (s < 0 || s >= nshapes || i0 < 0) continue;
         const long beg = seg_off[s], n = seg_off[s + 1] - beg;
         const long m = win_count <= 0 || win_count > n ? n : win_count;
         long cnt = m - i0;
         if (cnt > SG_SDFNET_LATENT_TILE) cnt = SG_SDFNET_LATENT_TILE;
-        double s1[256] = {0}, s5[256] = {0};
-        float labs = 0.f;
-        for (long i = 0; i < cnt; ++i) {
-            const long pi = beg + (win_start + i0 + i) % n;
-            float h[7][256], g[256];
-            const float o = tanhf(sdf_shape_point_fwd(v, points + pi * 3, zb1 + s * 256, zb5 + s * 256, h));
-            const float tg = fminf(fmaxf(target[pi], -cutoff), cutoff);
-            const float d = o - tg;
-            labs += fabsf(d);
-            const float d8 = (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * ((1.f - o * o) / (float)m);
-            sdf_shape_point_chain(v, h, d8, g, [&](const float* dz5) {
-                for (int r = 0; r < 256; ++r) s5[r] += dz5[r];
-            });
-            for (int r = 0; r < 256; ++r) s1[r] += g[r];
-        }
-        for (int r = 0; r < 256; ++r) {
-            prow[r] = (float)s1[r];
-            prow[256 + r] = (float)s5[r];
-        }
-        prow[512] = labs;
-    }
-    return SG_OK;
-}
-int sg_sdfnet_latent_reduce_cpu(const float* partials, const int64_t* tile_off, const int64_t* seg_off, long nshapes, long win_count,
-                                float* t1, float* t5, float* loss, void*) {
-    CPU_CHECK(partials && tile_off && seg_off && t1 && t5 && loss && nshapes >= 1);
-#pragma omp parallel for schedule(static)
-    for (long s = 0; s < nshapes; ++s) {
-        const long ta = tile_off[s], tb = tile_off[s + 1];
-        for (int r = 0; r < 512; ++r) {
-            double a = 0;
-            for (long t = ta; t < tb; ++t) a += partials[t * SG_SDFNET_LATENT_PARTIAL_ROW + r];
-            (r < 256 ? t1 : t5)[(long)(r & 255) * nshapes + s] = (float)a;
-        }
-        double l = 0;
-        for (long t = ta; t < tb; ++t) l += partials[t * SG_SDFNET_LATENT_PARTIAL_ROW + 512];
-        const long n = seg_off[s + 1] - seg_off[s];
-        const long m = win_count <= 0 || win_count > n ? n : win_count;
-        loss[s] = (float)(l / (double)(m > 0 ? m : 1));
-    }
-    return SG_OK;
-}
-
-// ---- K7e: the pose fitted with the code (header: sg_sdfnet_latent_pose_grad / sg_sdfnet_latent_pose_reduce) -------------------------
-// K7c's loop at x = A q + t (the header's fma order) with target' = clamp(ts target): the same calls in the same order, so the
-// identity pose with ts = 1 gives sg_sdfnet_latent_grad_cpu's floats [0, 513) bit for bit; the point gradient as in
-// sg_sdfnet_project_cpu, contracted with q per tile in point order.
-int sg_sdfnet_latent_pose_grad_cpu(const float* points, const float* target, const int64_t* seg_off, long nshapes, const float* zb1,
-                                   const float* zb5, const float* packed, const float* pose, float cutoff, long win_start,
-                                   long win_count, const int* tiles, long ntiles, float* partials, void*) {
-    CPU_CHECK(points && target && seg_off && zb1 && zb5 && packed && pose && tiles && partials);
-    CPU_CHECK(nshapes >= 1 && win_start >= 0 && ntiles >= 1 && ntiles < (1L << 31) && cutoff >= 0.f);
-    for (long s = 0; s < nshapes; ++s) CPU_CHECK(seg_off[s + 1] - seg_off[s] >= 1);
-    const CpuSdf v = sdf_view(packed, 3);
-#pragma omp parallel for schedule(dynamic)
-    for (long t = 0; t < ntiles; ++t) {
-        float* prow = partials + t * SG_SDFNET_POSE_PARTIAL_ROW;
-        for (int e = 0; e < SG_SDFNET_POSE_PARTIAL_ROW; ++e) prow[e] = 0.f;
-        const long s = tiles[2 * t], i0 = tiles[2 * t + 1];
-        if (s < 0 || s >= nshapes || i0 < 0) continue;
-        const long beg = seg_off[s], n = seg_off[s + 1] - beg;
-        const long m = win_count <= 0 || win_count > n ? n : win_count;
-        long cnt = m - i0;
-        if (cnt > SG_SDFNET_LATENT_TILE) cnt = SG_SDFNET_LATENT_TILE;
-        const float* ps = pose + s * 16;
-        const float ts = ps[12];
+        const float* ps = POSE ? pose + s * 16 : nullptr;
         double s1[256] = {0}, s5[256] = {0};
         float labs = 0.f, gq[9] = {0.f}, gs[3] = {0.f}, es = 0.f;
         for (long i = 0; i < cnt; ++i) {
             const long pi = beg + (win_start + i0 + i) % n;
             const float* q = points + pi * 3;
-            float x[3], h[7][256], g[256], gp[3] = {0.f, 0.f, 0.f};
-            for (int c = 0; c < 3; ++c)
-                x[c] = fmaf(ps[4 * c], q[0], fmaf(ps[4 * c + 1], q[1], fmaf(ps[4 * c + 2], q[2], ps[4 * c + 3])));
-            const float o = tanhf(sdf_shape_point_fwd(v, x, zb1 + s * 256, zb5 + s * 256, h));
-            const float raw = target[pi], st = ts * raw;
+            float xp[3], h[7][256], g[256];
+            if (POSE)
+                for (int c = 0; c < 3; ++c)
+                    xp[c] = fmaf(ps[4 * c], q[0], fmaf(ps[4 * c + 1], q[1], fmaf(ps[4 * c + 2], q[2], ps[4 * c + 3])));
+            const float o = tanhf(sdf_shape_point_fwd(v, POSE ? xp : q, zb1 + s * 256, zb5 + s * 256, h));
+            const float raw = target[pi], st = POSE ? ps[12] * raw : raw;
             const float tg = fminf(fmaxf(st, -cutoff), cutoff);
             const float d = o - tg;
             labs += fabsf(d);
             const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
             const float d8 = sg * ((1.f - o * o) / (float)m);
-            if (st > -cutoff && st < cutoff) es += (-sg * raw) / (float)m;
-            sdf_shape_point_chain(v, h, d8, g, [&](const float* dz5) {
+            auto sum5 = [&](const float* dz5) {
                 for (int r = 0; r < 256; ++r) s5[r] += dz5[r];
-                dense_t(v.W5i, 3, dz5, gp, false);
-            });
-            for (int r = 0; r < 256; ++r) s1[r] += g[r];
-            dense_t(v.W1k, 3, g, gp, true);
-            for (int c = 0; c < 3; ++c) {
-                for (int j = 0; j < 3; ++j) gq[3 * c + j] += gp[c] * q[j];
-                gs[c] += gp[c];
+            };
+            if (POSE) {
+                float gp[3] = {0.f, 0.f, 0.f};
+                if (st > -cutoff && st < cutoff) es += (-sg * raw) / (float)m;
+                sdf_shape_point_grad(v, h, d8, g, gp, sum5);
+                for (int c = 0; c < 3; ++c) {
+                    for (int j = 0; j < 3; ++j) gq[3 * c + j] += gp[c] * q[j];
+                    gs[c] += gp[c];
+                }
+            } else {
+                sdf_shape_point_chain(v, h, d8, g, sum5);
             }
+            for (int r = 0; r < 256; ++r) s1[r] += g[r];
         }
         for (int r = 0; r < 256; ++r) {
             prow[r] = (float)s1[r];
             prow[256 + r] = (float)s5[r];
         }
         prow[512] = labs;
-        for (int e = 0; e < 9; ++e) prow[513 + e] = gq[e];
-        for (int c = 0; c < 3; ++c) prow[522 + c] = gs[c];
-        prow[525] = es;
+        if (POSE) {
+            for (int e = 0; e < 9; ++e) prow[513 + e] = gq[e];
+            for (int c = 0; c < 3; ++c) prow[522 + c] = gs[c];
+            prow[525] = es;
+        }
     }
-    return SG_OK;
 }
-int sg_sdfnet_latent_pose_reduce_cpu(const float* partials, const int64_t* tile_off, const int64_t* seg_off, long nshapes,
-                                     long win_count, float* t1, float* t5, float* loss, float* gpose, void*) {
-    CPU_CHECK(partials && tile_off && seg_off && t1 && t5 && loss && gpose && nshapes >= 1 && nshapes < (1L << 31));
+template <bool POSE>
+static void sdf_latent_reduce(const float* partials, const int64_t* tile_off, const int64_t* seg_off, long nshapes, long win_count,
+                              float* t1, float* t5, float* loss, float* gpose) {
+    constexpr int ROW = POSE ? SG_SDFNET_POSE_PARTIAL_ROW : SG_SDFNET_LATENT_PARTIAL_ROW;
 #pragma omp parallel for schedule(static)
     for (long s = 0; s < nshapes; ++s) {
         const long ta = tile_off[s], tb = tile_off[s + 1];
-        for (int r = 0; r < 512 + 16; ++r) {
+        for (int r = 0; r < (POSE ? 512 + 16 : 512); ++r) {
             const int k = r - 512;      // float k of gpose, in pose's layout: rows of A_c0 A_c1 A_c2 t_c, then ts
             const int col = r < 512 ? r : k == 12 ? 525 : (k & 3) == 3 ? 522 + (k >> 2) : 513 + 3 * (k >> 2) + (k & 3);
             double a = 0;
             if (r < 512 + 13)
-                for (long t = ta; t < tb; ++t) a += partials[t * SG_SDFNET_POSE_PARTIAL_ROW + col];
+                for (long t = ta; t < tb; ++t) a += partials[t * ROW + col];
             if (r < 512)
                 (r < 256 ? t1 : t5)[(long)(r & 255) * nshapes + s] = (float)a;
             else
                 gpose[s * 16 + (r - 512)] = (float)a;
         }
         double l = 0;
-        for (long t = ta; t < tb; ++t) l += partials[t * SG_SDFNET_POSE_PARTIAL_ROW + 512];
+        for (long t = ta; t < tb; ++t) l += partials[t * ROW + 512];
         const long n = seg_off[s + 1] - seg_off[s];
         const long m = win_count <= 0 || win_count > n ? n : win_count;
         loss[s] = (float)(l / (double)(m > 0 ? m : 1));
     }
+}
+}
+int sg_sdfnet_latent_grad_cpu(const float* points, const float* target, const int64_t* seg_off, long nshapes, const float* zb1,
+                              const float* zb5, const float* packed, float cutoff, long win_start, long win_count,
+                              const int* tiles, long ntiles, float* partials, void*) {
+    CPU_CHECK(points && target && seg_off && zb1 && zb5 && packed && tiles && partials);
+    CPU_CHECK(nshapes >= 1 && win_start >= 0 && ntiles >= 1 && ntiles < (1L << 31) && cutoff >= 0.f);
+    for (long s = 0; s < nshapes; ++s) CPU_CHECK(seg_off[s + 1] - seg_off[s] >= 1);
+    sdf_latent_grad_tiles<false>(points, target, seg_off, nshapes, zb1, zb5, packed, nullptr, cutoff, win_start, win_count, tiles, ntiles,
+                                 partials);
+    return SG_OK;
+}
+int sg_sdfnet_latent_reduce_cpu(const float* partials, const int64_t* tile_off, const int64_t* seg_off, long nshapes, long win_count,
+                                float* t1, float* t5, float* loss, void*) {
+    CPU_CHECK(partials && tile_off && seg_off && t1 && t5 && loss && nshapes >= 1);
+    sdf_latent_reduce<false>(partials, tile_off, seg_off, nshapes, win_count, t1, t5, loss, nullptr);
+    return SG_OK;
+}
+int sg_sdfnet_latent_pose_grad_cpu(const float* points, const float* target, const int64_t* seg_off, long nshapes, const float* zb1,
+                                   const float* zb5, const float* packed, const float* pose, float cutoff, long win_start,
+                                   long win_count, const int* tiles, long ntiles, float* partials, void*) {
+    CPU_CHECK(points && target && seg_off && zb1 && zb5 && packed && pose && tiles && partials);
+    CPU_CHECK(nshapes >= 1 && win_start >= 0 && ntiles >= 1 && ntiles < (1L << 31) && cutoff >= 0.f);
+    for (long s = 0; s < nshapes; ++s) CPU_CHECK(seg_off[s + 1] - seg_off[s] >= 1);
+    sdf_latent_grad_tiles<true>(points, target, seg_off, nshapes, zb1, zb5, packed, pose, cutoff, win_start, win_count, tiles, ntiles,
+                                partials);
+    return SG_OK;
+}
+int sg_sdfnet_latent_pose_reduce_cpu(const float* partials, const int64_t* tile_off, const int64_t* seg_off, long nshapes,
+                                     long win_count, float* t1, float* t5, float* loss, float* gpose, void*) {
+    CPU_CHECK(partials && tile_off && seg_off && t1 && t5 && loss && gpose && nshapes >= 1 && nshapes < (1L << 31));
+    sdf_latent_reduce<true>(partials, tile_off, seg_off, nshapes, win_count, t1, t5, loss, gpose);
     return SG_OK;
 }
 
@@ -3300,8 +3286,7 @@ int sg_sdfnet_project_cpu(const float* points, const int64_t* seg_off, long nsha
             for (int round = 0; round <= iterations; ++round) {
                 float h[7][256], g[256];
                 o = tanhf(sdf_shape_point_fwd(v, x, zb1 + s * 256, zb5 + s * 256, h));
-                sdf_shape_point_chain(v, h, 1.f - o * o, g, [&](const float* dz5) { dense_t(v.W5i, 3, dz5, gp, false); });
-                dense_t(v.W1k, 3, g, gp, true);
+                sdf_shape_point_grad(v, h, 1.f - o * o, g, gp, [](const float*) {});
                 if (round < iterations) sg_project_step(x, o, gp, level, rule, max_step);
             }
             if (out_points)

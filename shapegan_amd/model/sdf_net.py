@@ -109,7 +109,7 @@ class SDFNet(SavableModule):
             loss [S]         = mean_p |SDFNet(A q_p + t, z_s) - clamp(ts sdf_p, +-cutoff)|
             grad_z [S,L]     = d/dz_s (loss_s + sigma * mean_k z_{s,k}^2)
             grad_pose [S,16] = d loss_s / d poses[s] (floats 13..15 zero).
-        One fused launch per chunk of shapes (csrc/latent_pose_fit.hip); the point gradient it contracts never leaves the chip."""
+        One fused launch per chunk of shapes (csrc/latent_fit.hip); the point gradient it contracts never leaves the chip."""
         off = ops.check_segments(points, sdf, latent_table, segment_offsets)
         ops.check_poses(poses, latent_table.shape[0], points.device)
         start, count = (0, 0) if window is None else (int(window[0]), int(window[1]))

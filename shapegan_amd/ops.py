@@ -1457,7 +1457,7 @@ def check_poses(pose, nshapes, device=None):
 
 
 class LatentPoseFit(LatentFit):
-    """LatentFit with a pose per shape (csrc/latent_pose_fit.hip): the points are observed coordinates q, pose [S, 16] holds the
+    """LatentFit with a pose per shape (csrc/latent_fit.hip): the points are observed coordinates q, pose [S, 16] holds the
     row-major 3x4 affine A|t to canonical x = A q + t and, at float 12, the scale ts of the targets.  The same plan, chunking and
     launches around the two pose entry points (LatentFit._run).
     step(z, pose, start, count, sigma) -> (loss [S], grad_z [S, L], grad_pose [S, 16]): grad_pose in pose's layout, floats 13..15 zero."""

@@ -16,7 +16,7 @@ csrc/latent_fit.hip (SDFNet.latent_loss_and_grad), with Adam through sg_adam_ste
     python -m shapegan_amd.reconstruct --net models/sdf_net.to --clouds DIR --pose similarity --pose-starts 4 --out codes.to --poses-out poses.to
 
 --clouds and --partial fit to the SDF of an oriented point cloud (shapegan_amd.cloudsdf, mesh_to_sdf's 'normal' sign) instead of a mesh's.
---pose fits a pose per shape together with its code (fit_codes_and_poses, csrc/latent_pose_fit.hip): a partial scan's bounding sphere is
+--pose fits a pose per shape together with its code (fit_codes_and_poses, csrc/latent_fit.hip): a partial scan's bounding sphere is
 not the object's and a sensor's cloud is not upright, and the network is the only model of where the shape should be.
 """
 import argparse
@@ -89,7 +89,7 @@ def fit_latent_codes(sdf_net, points, sdf, segment_offsets=None, points_per_shap
     return z, loss
 
 
-# ---- pose with the code: clouds in an unknown similarity frame (csrc/latent_pose_fit.hip) ------------------------------------------------
+# ---- pose with the code: clouds in an unknown similarity frame (csrc/latent_fit.hip) ------------------------------------------------
 # which of (rotation vector, translation, log scale) a pose model leaves free
 POSE_MODELS = {"translation": (False, True, False), "translation+scale": (False, True, True), "rigid": (True, True, False),
                "similarity": (True, True, True)}
@@ -210,7 +210,7 @@ def fit_codes_and_poses(sdf_net, points, sdf, segment_offsets=None, points_per_s
 
     pose: "translation", "translation+scale", "rigid" or "similarity" — which of the rotation vector, the translation and log s are
     free; the others stay at their initial values (pose_init: a Poses, None: the identity).  Adam on the codes with `lr`, Adam on the
-    pose parameters with `pose_lr`, both through sg_adam_step; the step itself is one fused launch (csrc/latent_pose_fit.hip), the map
+    pose parameters with `pose_lr`, both through sg_adam_step; the step itself is one fused launch (csrc/latent_fit.hip), the map
     from the parameters to the kernel's pose rows and its backward are small batched torch.
     rotation_starts = K > 1: a fit from a wrong basin does not turn a chair around, so every shape is fitted from K yaw angles
     2 pi k / K about `up` (after pose_init) and the start with the smallest final data term is kept.  The K fits run as K * S shapes of

@@ -1,4 +1,4 @@
-"""Inputs, float64 references and test bodies of the pose fit: SDFNet.latent_pose_loss_and_grad (csrc/latent_pose_fit.hip and its twin),
+"""Inputs, float64 references and test bodies of the pose fit: SDFNet.latent_pose_loss_and_grad (csrc/latent_fit.hip and its twin),
 ops.LatentPoseFit and reconstruct.fit_codes_and_poses.  Run on the twin by tests/test_latent_pose.py and on the GPU by
 tests/test_gpu_latent_pose.py; nothing here is a test by itself.
 

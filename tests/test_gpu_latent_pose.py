@@ -1,4 +1,4 @@
-"""The pose fit on the GPU: csrc/latent_pose_fit.hip (bodies: tests/latent_pose_forms.py; the same bodies on the twin: tests/test_latent_pose.py)."""
+"""The pose fit on the GPU: csrc/latent_fit.hip (bodies: tests/latent_pose_forms.py; the same bodies on the twin: tests/test_latent_pose.py)."""
 import pytest
 
 import latent_pose_forms as F
