@@ -227,6 +227,9 @@ int sg_segsum(const float* x, float* out, long rows, long ld, const int64_t* seg
  * reference: model/gan.py:10,14,18; model/autoencoder.py:17,21,25,29,38,46,56,60,64 -> aten::batch_norm(_backward).
  * x [N,C,S]; momentum/eps as torch (0.1 / 1e-5); running_var gets the unbiased estimate. */
 size_t sg_bn_workspace_bytes(int C);
+/* The launch plan of the entries below for x [N,C,S] (host code, no GPU needed): *nsplit slices per channel in the statistics passes
+ * (at most 64), *napply >= *nsplit in the apply passes.  S % 4 == 0 takes the float4 form of every kernel, anything else the scalar one. */
+int sg_bn_plan(int N, int C, long S, int* nsplit, int* napply);
 int sg_bn_train_fwd(const float* x, const float* gamma, const float* beta, float* y, float* save_mean, float* save_invstd,
                     float* running_mean, float* running_var, long long* num_batches_tracked, int N, int C, long S,
                     float eps, float momentum, int act, float slope, void* workspace, size_t workspace_bytes,

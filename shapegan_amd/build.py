@@ -24,7 +24,7 @@ LIB = os.path.join(HERE, "libshapegan_hip.so")
 SOURCES = ["conv3d.hip", "conv3d_halo.hip", "conv3d_edge.hip", "gemm.hip", "sdfnet.hip", "latent_fit.hip", "sdfnet_project.hip", "batchnorm.hip", "elementwise.hip", "pointnet.hip", "losses.hip", "sdf_batch.hip", "head.hip", "mesh.hip", "raymarch.hip", "pointcloud.hip", "raster.hip", "emd.hip", "meshsdf.hip", "tsne.hip", "brickgrid.hip", "topology.hip", "simplify.hip", "cloud.hip", "spline.hip", "edt.hip"]
 ABI_HEADER = abi.HEADER
 # the arithmetic the HIP kernels share with the twin: an edit rebuilds both libraries
-CORE_HEADERS = [os.path.join(CSRC, h) for h in ("core_fn.h", "mc_tables.h", "mesh_core.h", "raymarch_core.h", "pointcloud_core.h", "raster_core.h", "meshsdf_core.h", "tsne_core.h", "brickgrid_core.h", "project_core.h", "topology_core.h", "simplify_core.h", "cloud_core.h", "spline_core.h", "edt_core.h")]
+CORE_HEADERS = [os.path.join(CSRC, h) for h in ("core_fn.h", "mc_tables.h", "mesh_core.h", "raymarch_core.h", "pointcloud_core.h", "raster_core.h", "meshsdf_core.h", "tsne_core.h", "brickgrid_core.h", "project_core.h", "topology_core.h", "simplify_core.h", "cloud_core.h", "spline_core.h", "edt_core.h", "batchnorm_core.h")]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "mfma_tile.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "sdfnet_tile.h"), os.path.join(CSRC, "sdfnet_frozen.h")] + CORE_HEADERS + [ABI_HEADER]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

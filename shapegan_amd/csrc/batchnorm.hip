@@ -8,43 +8,20 @@
 // workgroup streams its slice with float4 loads, reduces per wave with shuffles (DPP), then across the 4 waves
 // through LDS; the partials are combined in double at the head of the second pass (finalize + apply in one launch), whose
 // (channel, 0) workgroup also updates the running statistics.
-// Sums are shifted by the channel's first element so E[x^2]-E[x]^2 does not cancel when |mean| >> std.
+// Sums are shifted by K, the channel's first element, so E[x^2]-E[x]^2 does not cancel when |mean| >> std.  Where the sums show that K
+// itself was more than 8 std from the mean (an outlier as first element), the finalize forms the channel's statistics again around
+// the mean they give (bn_group_stats: one wave, double, rare).
 #include "common.h"
+#include "batchnorm_core.h"
 #include "../../include/shapegan_hip.h"
 
 namespace sg {
 
-// iterate the elements of channel c: for n in [0,N): x[(n*C + c)*S + s], s in [0,S)
-// flat index e in [0, N*S): n = e / S, s = e % S
-__device__ __forceinline__ long chan_addr(long e, int c, int C, long S) {
-    const long n = e / S, s = e - n * S;
-    return (n * C + c) * S + s;
-}
-
-// the same walk without a 64-bit division per element: a float4 group at flat index e (e % 4 == 0, S % 4 == 0 so a group never
-// straddles two samples) and steps of `step` elements
-struct ChanWalk {
-    long n, s, S;
-    int c, C;
-    __device__ ChanWalk(long e, int c_, int C_, long S_) : S(S_), c(c_), C(C_) {
-        n = e / S_;
-        s = e - n * S_;
-    }
-    __device__ __forceinline__ long addr() const { return (n * C + c) * S + s; }
-    __device__ __forceinline__ void advance(long step) {
-        s += step;
-        if (s >= S) {
-            if (step <= S) {
-                s -= S;
-                ++n;
-            } else {
-                const long k = s / S;
-                n += k;
-                s -= k * S;
-            }
-        }
-    }
-};
+// the elements of channel c: for n in [0,N): x[(n*C + c)*S + s], s in [0,S); flat index e in [0, N*S): n = e / S, s = e % S
+// (chan_addr, the division-free ChanWalk, the slices and the shift K of the sums: batchnorm_core.h, shared with the twin)
+__device__ __forceinline__ long chan_addr(long e, int c, int C, long S) { return sg_bn_chan_addr(e, c, C, S); }
+typedef SgChanWalk ChanWalk;
+__device__ __forceinline__ float bn_shift(const float* __restrict__ x, int c, long S) { return sg_bn_shift(x, c, S); }
 
 // partial[c][split] = {sum(x-K), sum((x-K)^2)}
 // (grid z = group: the tensor is [groups][N][C][S] and every group of N samples has statistics of its own — several generator
@@ -55,9 +32,9 @@ __global__ void __launch_bounds__(256) bn_stats_kernel(const float* __restrict__
     x += (long)blockIdx.z * N * C * S;
     partial += (long)blockIdx.z * C * nsplit * 2;
     const long total = (long)N * S;
-    const long chunk = ((total + nsplit - 1) / nsplit + 3) & ~3L;
-    const long beg = sp * chunk, end = min(total, beg + chunk);
-    const float K = x[(long)c * S];
+    long beg, end;
+    sg_bn_slice(total, nsplit, sp, &beg, &end);
+    const float K = bn_shift(x, c, S);
     float s1 = 0.f, s2 = 0.f;
     if ((S & 3) == 0 && (beg & 3) == 0) {
         for (long e = beg + (long)threadIdx.x * 4; e < end; e += 1024) {
@@ -136,10 +113,28 @@ __device__ __forceinline__ void bn_group_stats(const float* __restrict__ x, cons
     s1 = sg_wave_sum_d(s1);
     s2 = sg_wave_sum_d(s2);
     const double n = (double)N * (double)S;
-    const double K = (double)x[((long)g * N * C + c) * S];
-    const double m = s1 / n;
+    const float* xg = x + (long)g * N * C * S;
+    double K = (double)bn_shift(xg, c, S);
+    double m = s1 / n;
     double var = s2 / n - m * m;
     if (var < 0) var = 0;
+    // wave-uniform: the same walk in a fixed order in every workgroup of the channel (and once more per group in bn_update_running).
+    // One wave, double, a division per element: its cost is not measured; it is paid only by channels whose shift was far.
+    if (sg_bn_shift_was_far(m, var)) {
+        K = (double)(float)(K + m);
+        const long total = (long)N * S;
+        double t1 = 0.0, t2 = 0.0;
+        for (long e = lane; e < total; e += 64) {
+            const double a = (double)xg[chan_addr(e, c, C, S)] - K;
+            t1 += a;
+            t2 += a * a;
+        }
+        t1 = sg_wave_sum_d(t1);
+        t2 = sg_wave_sum_d(t2);
+        m = t1 / n;
+        var = t2 / n - m * m;
+        if (var < 0) var = 0;
+    }
     mu = (float)(K + m);
     is = (float)(1.0 / sqrt(var + (double)eps));
     var_out = var;
@@ -197,8 +192,8 @@ __global__ void __launch_bounds__(256) bn_finalize_apply_kernel(const float* __r
     y += (long)g * N * C * S;
     const float sc = gamma[c] * stat[1], sh = beta[c] - stat[0] * sc;
     const long total = (long)N * S;
-    const long chunk = ((total + nsplit - 1) / nsplit + 3) & ~3L;
-    const long beg = sp * chunk, end = min(total, beg + chunk);
+    long beg, end;
+    sg_bn_slice(total, nsplit, sp, &beg, &end);
     if ((S & 3) == 0) {
         for (long e = beg + (long)threadIdx.x * 4; e < end; e += 1024) {
             const long ad = chan_addr(e, c, C, S);
@@ -266,8 +261,8 @@ __global__ void __launch_bounds__(256) bn_bwd_stats_kernel(const float* __restri
                                                            int N, int C, long S, int nsplit, int act, float slope) {
     const int c = blockIdx.x, sp = blockIdx.y;
     const long total = (long)N * S;
-    const long chunk = ((total + nsplit - 1) / nsplit + 3) & ~3L;
-    const long beg = sp * chunk, end = min(total, beg + chunk);
+    long beg, end;
+    sg_bn_slice(total, nsplit, sp, &beg, &end);
     const float mu = mean[c], is = invstd[c], g = gamma[c], b = beta[c];
     float s1 = 0.f, s2 = 0.f;
     if ((S & 3) == 0 && (beg & 3) == 0) {
@@ -353,8 +348,8 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_apply_kernel(const float*
     const float is = invstd[c], g = gamma[c], b = beta[c], mu = mean[c];
     const float db = sums[0] * inv_n, dg = sums[1] * inv_n;
     const long total = (long)N * S;
-    const long chunk = ((total + nsplit - 1) / nsplit + 3) & ~3L;
-    const long beg = sp * chunk, end = min(total, beg + chunk);
+    long beg, end;
+    sg_bn_slice(total, nsplit, sp, &beg, &end);
     if ((S & 3) == 0 && (beg & 3) == 0) {
         ChanWalk w(beg + (long)threadIdx.x * 4, c, C, S);
         for (long e = beg + (long)threadIdx.x * 4; e < end; e += 1024) {
@@ -384,27 +379,8 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_apply_kernel(const float*
     }
 }
 
-static int bn_nsplit(int N, int C, long S) {
-    const long per = (long)N * S;
-    long want = 1024 / (C > 0 ? C : 1);  // ~4 workgroups per CU overall
-    if (want < 1) want = 1;
-    long maxs = per / 4096;              // each split at least 4096 elements
-    if (maxs < 1) maxs = 1;
-    long s = want < maxs ? want : maxs;
-    if (s > 64) s = 64;
-    return (int)s;
-}
-// slices per channel of the apply passes: enough workgroups to fill the chip (~8 per CU), each at least 4096 elements
-static int bn_apply_split(int N, int C, long S) {
-    const long per = (long)N * S;
-    long want = (2048 + C - 1) / (C > 0 ? C : 1);
-    long maxs = per / 4096;
-    if (maxs < 1) maxs = 1;
-    long s = want < maxs ? want : maxs;
-    if (s > 1024) s = 1024;
-    if (s < 1) s = 1;
-    return (int)s;
-}
+static int bn_nsplit(int N, int C, long S) { return sg_bn_nsplit(N, C, S); }
+static int bn_apply_split(int N, int C, long S) { return sg_bn_apply_split(N, C, S); }
 static int ew_blocks(long total, int per_thread) {
     long b = (total + 256L * per_thread - 1) / (256L * per_thread);
     if (b > 2048) b = 2048;
@@ -419,6 +395,13 @@ using namespace sg;
 extern "C" {
 
 size_t sg_bn_workspace_bytes(int C) { return (size_t)C * 64 * 2 * sizeof(double); }
+
+int sg_bn_plan(int N, int C, long S, int* nsplit, int* napply) {
+    SG_CHECK_ARG(nsplit && napply && N > 0 && C > 0 && S > 0);
+    *nsplit = bn_nsplit(N, C, S);
+    *napply = bn_apply_split(N, C, S);
+    return SG_OK;
+}
 
 int sg_bn_train_fwd_grouped(const float* x, const float* gamma, const float* beta, float* y, float* save_mean, float* save_invstd,
                             float* running_mean, float* running_var, long long* num_batches_tracked, int groups, int N, int C,
@@ -473,7 +456,7 @@ int sg_bn_train_stats(const float* x, const float* gamma, const float* beta, flo
 int sg_bn_eval_fwd(const float* x, const float* gamma, const float* beta, float* y, const float* running_mean,
                    const float* running_var, float* save_mean, float* save_invstd, int N, int C, long S, float eps,
                    int act, float slope, hipStream_t stream) {
-    SG_CHECK_ARG(x && gamma && beta && y && running_mean && running_var && save_mean && save_invstd && N > 0 && C > 0);
+    SG_CHECK_ARG(x && gamma && beta && y && running_mean && running_var && save_mean && save_invstd && N > 0 && C > 0 && S > 0);
     hipLaunchKernelGGL(bn_eval_stats_kernel, dim3(sg_cdiv(C, 256)), dim3(256), 0, stream, running_mean, running_var,
                        save_mean, save_invstd, C, eps);
     const long total = (long)N * C * S;

@@ -378,33 +378,121 @@ int sg_colsum_tall_cpu(const float* x, float* out, long batch, long batch_stride
 }
 
 // ---- K4: BatchNorm ---------------------------------------------------------------------------------------------------------
+#include "../csrc/batchnorm_core.h"
+// the HIP launchers' plan, from the functions they share with this file (the loops below are plain: one pass per channel)
+int sg_bn_plan_cpu(int N, int C, long S, int* nsplit, int* napply) {
+    CPU_CHECK(nsplit && napply && N > 0 && C > 0 && S > 0);
+    *nsplit = sg_bn_nsplit(N, C, S);
+    *napply = sg_bn_apply_split(N, C, S);
+    return SG_OK;
+}
+// The entries below walk a channel as the HIP kernels do (csrc/batchnorm.hip): the slices of sg_bn_plan, 256 lanes per slice with fp32
+// sums of (x - K) and (x - K)^2 each, float4 groups where S % 4 == 0, the lanes' sums combined in double; the apply passes in `napply`
+// slices.  A mistake in the slice arithmetic, the walk or the shift shows here as it would on the GPU.
+namespace bn_twin {
+// {sum(x-K), sum((x-K)^2)} of slice sp of channel c (bn_stats_kernel)
+static void stats_slice(const float* x, int c, int N, int C, long S, int nsplit, int sp, double* out) {
+    const long total = (long)N * S;
+    long beg, end;
+    sg_bn_slice(total, nsplit, sp, &beg, &end);
+    const float K = sg_bn_shift(x, c, S);
+    double d1 = 0, d2 = 0;
+    for (int lane = 0; lane < 256; ++lane) {
+        float s1 = 0.f, s2 = 0.f;
+        if ((S & 3) == 0 && (beg & 3) == 0) {
+            for (long e = beg + (long)lane * 4; e < end; e += 1024) {
+                const float* v = x + sg_bn_chan_addr(e, c, C, S);
+                const float a = v[0] - K, b = v[1] - K, cc = v[2] - K, d = v[3] - K;
+                s1 += (a + b) + (cc + d);
+                s2 += (a * a + b * b) + (cc * cc + d * d);
+            }
+        } else {
+            for (long e = beg + lane; e < end; e += 256) {
+                const float a = x[sg_bn_chan_addr(e, c, C, S)] - K;
+                s1 += a;
+                s2 += a * a;
+            }
+        }
+        d1 += s1;
+        d2 += s2;
+    }
+    out[0] = d1;
+    out[1] = d2;
+}
+// mean, invstd and the biased variance of channel c from its nparts partials (bn_group_stats)
+static void group_stats(const float* x, const double* partial, int c, int N, int C, long S, int nparts, float eps, float& mu, float& is,
+                        double& var) {
+    double s1 = 0, s2 = 0;
+    for (int p = 0; p < nparts; ++p) {
+        s1 += partial[p * 2];
+        s2 += partial[p * 2 + 1];
+    }
+    const double n = (double)N * (double)S;
+    double K = (double)sg_bn_shift(x, c, S);
+    double m = s1 / n;
+    var = s2 / n - m * m;
+    if (var < 0) var = 0;
+    if (sg_bn_shift_was_far(m, var)) {      // the statistics again around the mean the sums give, in double
+        K = (double)(float)(K + m);
+        const long total = (long)N * S;
+        double t1 = 0, t2 = 0;
+        for (long e = 0; e < total; ++e) {
+            const double a = (double)x[sg_bn_chan_addr(e, c, C, S)] - K;
+            t1 += a;
+            t2 += a * a;
+        }
+        m = t1 / n;
+        var = t2 / n - m * m;
+        if (var < 0) var = 0;
+    }
+    mu = (float)(K + m);
+    is = (float)(1.0 / sqrt(var + (double)eps));
+}
+// statistics of channel c and the running update (bn_update_running with one group)
+static void channel_stats(const float* x, int c, int N, int C, long S, float eps, float momentum, float* running_mean, float* running_var,
+                          float& mu, float& is) {
+    const int ns = sg_bn_nsplit(N, C, S);
+    double partial[64 * 2];
+    for (int sp = 0; sp < ns; ++sp) stats_slice(x, c, N, C, S, ns, sp, partial + sp * 2);
+    double var;
+    group_stats(x, partial, c, N, C, S, ns, eps, mu, is, var);
+    const double n = (double)N * (double)S;
+    const double unbiased = n > 1 ? var * n / (n - 1) : var;
+    if (running_mean) {
+        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
+        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
+    }
+}
+}  // namespace bn_twin
+
 int sg_bn_train_fwd_cpu(const float* x, const float* gamma, const float* beta, float* y, float* save_mean, float* save_invstd,
                         float* running_mean, float* running_var, long long* num_batches_tracked, int N, int C, long S, float eps,
                         float momentum, int act, float slope, void*, size_t, void*) {
     CPU_CHECK(x && gamma && beta && y && save_mean && save_invstd && N > 0 && C > 0 && S > 0);
-    const double cnt = (double)N * S;
+    const long total = (long)N * S;
+    const int na = sg_bn_apply_split(N, C, S);
 #pragma omp parallel for schedule(static)
     for (int c = 0; c < C; ++c) {
-        double s = 0, s2 = 0;
-        for (int n = 0; n < N; ++n) {
-            const float* p = x + ((long)n * C + c) * S;
-            for (long e = 0; e < S; ++e) s += p[e];
-        }
-        const double mu = s / cnt;
-        for (int n = 0; n < N; ++n) {
-            const float* p = x + ((long)n * C + c) * S;
-            for (long e = 0; e < S; ++e) s2 += (p[e] - mu) * (p[e] - mu);
-        }
-        const double var = s2 / cnt;
-        const float is = (float)(1.0 / sqrt(var + (double)eps));
-        save_mean[c] = (float)mu;
+        float mu, is;
+        bn_twin::channel_stats(x, c, N, C, S, eps, momentum, running_mean, running_var, mu, is);
+        save_mean[c] = mu;
         save_invstd[c] = is;
-        if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mu;
-        if (running_var) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)(cnt > 1 ? s2 / (cnt - 1) : var);
-        for (int n = 0; n < N; ++n) {
-            const float* p = x + ((long)n * C + c) * S;
-            float* q = y + ((long)n * C + c) * S;
-            for (long e = 0; e < S; ++e) q[e] = apply_act(gamma[c] * ((p[e] - (float)mu) * is) + beta[c], act, slope);
+        // bn_finalize_apply_kernel's slices; the affine map in the centred form gamma ((x - mean) invstd) + beta, which does not lose
+        // |mean| / std in the rounding of shift as the kernels' fma(x, scale, shift) does
+        for (int sp = 0; sp < na; ++sp) {
+            long beg, end;
+            sg_bn_slice(total, na, sp, &beg, &end);
+            if ((S & 3) == 0) {
+                for (long e = beg; e < end; e += 4) {
+                    const long ad = sg_bn_chan_addr(e, c, C, S);
+                    for (int j = 0; j < 4; ++j) y[ad + j] = apply_act(gamma[c] * ((x[ad + j] - mu) * is) + beta[c], act, slope);
+                }
+            } else {
+                for (long e = beg; e < end; ++e) {
+                    const long ad = sg_bn_chan_addr(e, c, C, S);
+                    y[ad] = apply_act(gamma[c] * ((x[ad] - mu) * is) + beta[c], act, slope);
+                }
+            }
         }
     }
     if (num_batches_tracked) *num_batches_tracked += 1;
@@ -414,27 +502,14 @@ int sg_bn_train_stats_cpu(const float* x, const float* gamma, const float* beta,
                           float* running_mean, float* running_var, long long* num_batches_tracked, float* scale, float* shift,
                           int N, int C, long S, float eps, float momentum, void*, size_t, void*) {
     CPU_CHECK(x && gamma && beta && save_mean && save_invstd && scale && shift && N > 0 && C > 0 && S > 0);
-    const double cnt = (double)N * S;
 #pragma omp parallel for schedule(static)
     for (int c = 0; c < C; ++c) {
-        double s = 0, s2 = 0;
-        for (int n = 0; n < N; ++n) {
-            const float* p = x + ((long)n * C + c) * S;
-            for (long e = 0; e < S; ++e) s += p[e];
-        }
-        const double mu = s / cnt;
-        for (int n = 0; n < N; ++n) {
-            const float* p = x + ((long)n * C + c) * S;
-            for (long e = 0; e < S; ++e) s2 += (p[e] - mu) * (p[e] - mu);
-        }
-        const double var = s2 / cnt;
-        const float is = (float)(1.0 / sqrt(var + (double)eps));
-        save_mean[c] = (float)mu;
+        float mu, is;
+        bn_twin::channel_stats(x, c, N, C, S, eps, momentum, running_mean, running_var, mu, is);
+        save_mean[c] = mu;
         save_invstd[c] = is;
         scale[c] = gamma[c] * is;
-        shift[c] = beta[c] - (float)mu * scale[c];
-        if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mu;
-        if (running_var) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)(cnt > 1 ? s2 / (cnt - 1) : var);
+        shift[c] = beta[c] - mu * scale[c];
     }
     if (num_batches_tracked) *num_batches_tracked += 1;
     return SG_OK;
@@ -443,7 +518,7 @@ int sg_bn_train_fwd_grouped_cpu(const float* x, const float* gamma, const float*
                                 float* save_invstd, float* running_mean, float* running_var, long long* num_batches_tracked,
                                 int groups, int N, int C, long S, float eps, float momentum, int act, float slope, void* ws, size_t wb,
                                 void* st) {
-    CPU_CHECK(groups > 0);
+    CPU_CHECK(groups > 0 && groups <= 64);
     for (int g = 0; g < groups; ++g) {     // the groups are independent batches, applied one after the other
         const long off = (long)g * N * C * S;
         const int rc = sg_bn_train_fwd_cpu(x + off, gamma, beta, y + off, save_mean + (long)g * C, save_invstd + (long)g * C,
@@ -457,7 +532,7 @@ int sg_bn_train_stats_grouped_cpu(const float* x, const float* gamma, const floa
                                   float* running_mean, float* running_var, long long* num_batches_tracked, float* scale,
                                   float* shift, int groups, int N, int C, long S, float eps, float momentum, void* ws, size_t wb,
                                   void* st) {
-    CPU_CHECK(groups > 0);
+    CPU_CHECK(groups > 0 && groups <= 64);
     for (int g = 0; g < groups; ++g) {
         const int rc = sg_bn_train_stats_cpu(x + (long)g * N * C * S, gamma, beta, save_mean + (long)g * C, save_invstd + (long)g * C,
                                              running_mean, running_var, num_batches_tracked, scale + (long)g * C,
@@ -487,29 +562,82 @@ int sg_bn_bwd_cpu(const float* dy, const float* x, const float* gamma, const flo
                   const float* save_invstd, float* dx, float* dgamma, float* dbeta, int N, int C, long S, int train, int act,
                   float slope, void*, size_t, void*) {
     CPU_CHECK(dy && x && gamma && beta && save_mean && save_invstd && dx && dgamma && dbeta && N > 0 && C > 0 && S > 0);
-    const double cnt = (double)N * S;
+    const long total = (long)N * S;
+    const int ns = sg_bn_nsplit(N, C, S), na = sg_bn_apply_split(N, C, S);
 #pragma omp parallel for schedule(static)
     for (int c = 0; c < C; ++c) {
         const float mu = save_mean[c], is = save_invstd[c], g = gamma[c], b = beta[c];
-        double s1 = 0, s2 = 0;
-        for (int n = 0; n < N; ++n) {
-            const long base = ((long)n * C + c) * S;
-            for (long e = 0; e < S; ++e) {
-                const float xh = (x[base + e] - mu) * is;
-                const float gg = act_grad_out(apply_act(g * xh + b, act, slope), dy[base + e], act, slope);
-                s1 += gg;
-                s2 += (double)gg * xh;
+        auto grad = [&](float xh, float d) { return act_grad_out(apply_act(fmaf(g, xh, b), act, slope), d, act, slope); };
+        double t1 = 0, t2 = 0;
+        for (int sp = 0; sp < ns; ++sp) {      // bn_bwd_stats_kernel: {sum(g), sum(g * xhat)}, two float4 groups in flight per lane
+            long beg, end;
+            sg_bn_slice(total, ns, sp, &beg, &end);
+            for (int lane = 0; lane < 256; ++lane) {
+                float s1 = 0.f, s2 = 0.f;
+                if ((S & 3) == 0 && (beg & 3) == 0) {
+                    SgChanWalk w(beg + (long)lane * 4, c, C, S);
+                    long e = beg + (long)lane * 4;
+                    for (; e + 1024 < end; e += 2048) {
+                        const long a0 = w.addr();
+                        w.advance(1024);
+                        const long a1 = w.addr();
+                        w.advance(1024);
+                        for (int j = 0; j < 4; ++j) {
+                            const float xh0 = (x[a0 + j] - mu) * is, xh1 = (x[a1 + j] - mu) * is;
+                            const float g0 = grad(xh0, dy[a0 + j]), g1 = grad(xh1, dy[a1 + j]);
+                            s1 += g0 + g1;
+                            s2 += g0 * xh0 + g1 * xh1;
+                        }
+                    }
+                    if (e < end) {
+                        const long a0 = w.addr();
+                        for (int j = 0; j < 4; ++j) {
+                            const float xh0 = (x[a0 + j] - mu) * is;
+                            const float g0 = grad(xh0, dy[a0 + j]);
+                            s1 += g0;
+                            s2 += g0 * xh0;
+                        }
+                    }
+                } else {
+                    for (long e = beg + lane; e < end; e += 256) {
+                        const long ad = sg_bn_chan_addr(e, c, C, S);
+                        const float xh = (x[ad] - mu) * is;
+                        const float gg = grad(xh, dy[ad]);
+                        s1 += gg;
+                        s2 += gg * xh;
+                    }
+                }
+                t1 += s1;
+                t2 += s2;
             }
         }
-        dbeta[c] = (float)s1;
-        dgamma[c] = (float)s2;
-        const float m1 = (float)(s1 / cnt), m2 = (float)(s2 / cnt);
-        for (int n = 0; n < N; ++n) {
-            const long base = ((long)n * C + c) * S;
-            for (long e = 0; e < S; ++e) {
-                const float xh = (x[base + e] - mu) * is;
-                const float gg = act_grad_out(apply_act(g * xh + b, act, slope), dy[base + e], act, slope);
-                dx[base + e] = g * is * (train ? gg - m1 - xh * m2 : gg);
+        dbeta[c] = (float)t1;
+        dgamma[c] = (float)t2;
+        const float inv_n = 1.f / ((float)N * (float)S);
+        const float db = (float)t1 * inv_n, dg = (float)t2 * inv_n;
+        for (int sp = 0; sp < na; ++sp) {      // bn_bwd_finalize_apply_kernel
+            long beg, end;
+            sg_bn_slice(total, na, sp, &beg, &end);
+            if ((S & 3) == 0 && (beg & 3) == 0) {
+                for (int lane = 0; lane < 256; ++lane) {
+                    SgChanWalk w(beg + (long)lane * 4, c, C, S);
+                    for (long e = beg + (long)lane * 4; e < end; e += 1024) {
+                        const long ad = w.addr();
+                        w.advance(1024);
+                        for (int j = 0; j < 4; ++j) {
+                            const float xh = (x[ad + j] - mu) * is;
+                            const float gg = grad(xh, dy[ad + j]);
+                            dx[ad + j] = g * is * (train ? gg - db - xh * dg : gg);
+                        }
+                    }
+                }
+                continue;
+            }
+            for (long e = beg; e < end; ++e) {
+                const long ad = sg_bn_chan_addr(e, c, C, S);
+                const float xh = (x[ad] - mu) * is;
+                const float gg = grad(xh, dy[ad]);
+                dx[ad] = g * is * (train ? gg - db - xh * dg : gg);
             }
         }
     }

@@ -597,6 +597,15 @@ def convT_to1_pre_served(x, w):
             bool(_lib().sg_convT3d_k4s2p1_to1_pre_eligible(x.shape[0], x.shape[1], x.shape[2], x.shape[3], x.shape[4])))
 
 
+def bn_plan(N, C, S):
+    """(nsplit, napply) of the BatchNorm launchers for x [N, C, S]: slices per channel of the statistics and of the apply passes
+    (sg_bn_plan).  Host code, no GPU needed."""
+    import ctypes
+    nsplit, napply = ctypes.c_int(0), ctypes.c_int(0)
+    check(L._load_hip().sg_bn_plan(N, C, S, ctypes.addressof(nsplit), ctypes.addressof(napply)), "bn_plan")
+    return nsplit.value, napply.value
+
+
 def bn_train_stats_affine(x, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, groups=1):
     """Batch statistics of x [N,C,*S] with torch's running-statistics update, WITHOUT writing the normalised tensor: returns
     (scale, shift) with batch_norm(x)[:, c] == x[:, c] * scale[c] + shift[c] (sg_bn_train_stats).  No autograd: inference-mode

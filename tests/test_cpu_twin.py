@@ -14,6 +14,7 @@ import torch.nn as nn
 import shapegan_amd.lib as L
 import autograd_cases as AG
 import conv_patterns as GRIDS
+import batchnorm_forms as BN
 import gemm_forms as GEMM
 import pointgan_forms as PG
 import sdfnet_forms as FORMS
@@ -184,6 +185,27 @@ def test_gemm_family_reductions(on_cpu):
 @pytest.mark.parametrize("N,C,S", [(4, 8, 64), (4, 256, 1), (3, 7, 27)])
 def test_batchnorm(on_cpu, N, C, S):
     OPS.test_batchnorm_train_fwd_bwd(N, C, S)
+
+
+# the bodies of tests/test_gpu_batchnorm_forms.py (tests/batchnorm_forms.py): BatchNorm against float64, every operand and output inside
+# NaN buffers.  The twin shares csrc/batchnorm_core.h with the kernels (the plan, the slices, the division-free walk, the shift and the
+# test for a second pass): a mistake there fails here as it would on the GPU.  Its loops over lanes, the two-groups-in-flight loop and
+# its tail are a hand copy of the kernels', not shared code: a mistake in the kernels' own loops or launch arguments shows on the
+# GPU only.  It runs every shape it finishes quickly, which takes every branch it has: float4 and scalar slices, one and many,
+# training / eval, with and without running statistics, n == 1, the second pass, train 1 / 0 of the backward, the five activations,
+# the grouped loops and their refusals.  The plans are checked by tests/test_batchnorm_plan_host.py.
+@pytest.mark.parametrize("shape_id", BN.TWIN_IDS)
+def test_batchnorm_forms(on_cpu, shape_id):
+    BN.body_shape(shape_id)
+
+
+@pytest.mark.parametrize("gid", BN.GROUPED_IDS)
+def test_batchnorm_grouped_forms_bn(on_cpu, gid):
+    BN.body_grouped(gid)
+
+
+def test_batchnorm_refusals(on_cpu):
+    BN.body_refusals()
 
 
 def test_activations_and_reductions(on_cpu):
