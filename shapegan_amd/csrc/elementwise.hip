@@ -18,6 +18,10 @@ static int ew_grid(long n, int per_thread) {
     return (int)b;
 }
 
+// clamp as torch.clamp does it: a NaN stays a NaN (fminf(fmaxf(NaN, lo), hi) is lo: a NaN critic weight became -clip and stayed
+// pinned there, where the reference's p.data.clamp_ keeps it and the run visibly dies).  Finite values and infinities: the same bits.
+__device__ __forceinline__ float sg_clamp_keep_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
 __device__ __forceinline__ float act_grad_from_output(float y, float dy, int act, float slope) {
     switch (act) {
         case SG_ACT_LEAKY: return y > 0.f ? dy : dy * slope;
@@ -106,7 +110,7 @@ __global__ void __launch_bounds__(256) rmsprop_kernel(float* __restrict__ p, con
         const float s = alpha * sq[e] + (1.f - alpha) * gg * gg;
         sq[e] = s;
         float v = p[e] - lr * (gg / (sqrtf(s) + eps));
-        if (clip > 0.f) v = fminf(fmaxf(v, -clip), clip);
+        if (clip > 0.f) v = sg_clamp_keep_nan(v, -clip, clip);
         p[e] = v;
     }
 }
@@ -225,7 +229,7 @@ __global__ void __launch_bounds__(256) adam_dev_multi_kernel(AdamDevMulti a, con
 
 __global__ void __launch_bounds__(256) clamp_kernel(float* __restrict__ p, long n, float lo, float hi) {
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256)
-        p[e] = fminf(fmaxf(p[e], lo), hi);
+        p[e] = sg_clamp_keep_nan(p[e], lo, hi);
 }
 
 // the same for up to 16 tensors in one launch (Discriminator.clip_weights, model/gan.py:67-69: eight parameter tensors per update):
@@ -237,7 +241,7 @@ struct ClampMulti {
 __global__ void __launch_bounds__(256) clamp_multi_kernel(ClampMulti t, float lo, float hi) {
     float* __restrict__ p = t.p[blockIdx.y];
     const long n = t.n[blockIdx.y];
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) p[e] = fminf(fmaxf(p[e], lo), hi);
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) p[e] = sg_clamp_keep_nan(p[e], lo, hi);
 }
 
 // out = clamp(x, -c, c) [/ divisor]: VoxelDataset.__getitem__'s clamp_ and /= (datasets.py:19-22), NaN-propagating like
@@ -245,8 +249,7 @@ __global__ void __launch_bounds__(256) clamp_multi_kernel(ClampMulti t, float lo
 __global__ void __launch_bounds__(256) voxel_prepare_kernel(const float* __restrict__ x, float* __restrict__ out, long n,
                                                             float c, float divisor) {
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
-        float v = x[e];
-        v = v < -c ? -c : (v > c ? c : v);
+        const float v = sg_clamp_keep_nan(x[e], -c, c);
         out[e] = divisor > 0.f ? v / divisor : v;
     }
 }

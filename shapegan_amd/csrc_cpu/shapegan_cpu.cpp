@@ -1496,6 +1496,8 @@ int sg_adam_step_dev_multi_cpu(int nsets, float* const* p, const float* const* g
                                const float* lr, const float* b1, const float* b2, const float* eps, long long* const* step_dev,
                                float* const* corr_dev, const float* gscale, const int* skip, void* stream) {
     CPU_CHECK(nsets > 0 && nsets <= 4 && p && g && m && v && n && lr && b1 && b2 && eps && step_dev && corr_dev && gscale);
+    // (every set is looked at before the first is updated, as the library does before its one launch)
+    for (int i = 0; i < nsets; ++i) CPU_CHECK(p[i] && g[i] && m[i] && v[i] && n[i] > 0 && step_dev[i] && corr_dev[i]);
     for (int i = 0; i < nsets; ++i) {
         const int rc = sg_adam_step_dev_guarded_cpu(p[i], g[i], m[i], v[i], n[i], lr[i], b1[i], b2[i], eps[i], step_dev[i], corr_dev[i],
                                                     gscale[i], skip, stream);

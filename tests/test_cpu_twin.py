@@ -16,6 +16,7 @@ import autograd_cases as AG
 import conv_patterns as GRIDS
 import batchnorm_forms as BN
 import gemm_forms as GEMM
+import optim_forms as OF
 import pointgan_forms as PG
 import sdfnet_forms as FORMS
 import test_gpu_modules as M
@@ -206,6 +207,60 @@ def test_batchnorm_grouped_forms_bn(on_cpu, gid):
 
 def test_batchnorm_refusals(on_cpu):
     BN.body_refusals()
+
+
+# the bodies of tests/test_gpu_optim_forms.py (tests/optim_forms.py): the fused optimizers and the elementwise kernels against float64,
+# every operand and output inside NaN buffers.  The twin's Adam is not lane-faithful: it has no tickets (the ticket words stay as
+# they were: zero), takes the corrections from pow and leaves the contraction of b2 v + c2 g g to the compiler; its reduction, row
+# sums and scatter are plain loops.  A wrong formula, a dropped scale, an ignored guard or a NaN-dropping clamp fails here as on the GPU;
+# the grid-stride rounds, the float4 tails, the tickets and the four-loads-in-flight loop show on the GPU only.  It runs every case but
+# the two largest optimizer lengths.
+@pytest.mark.parametrize("n", OF.TWIN_N)
+def test_adam_forms(on_cpu, n):
+    OF.body_adam(n)
+
+
+@pytest.mark.parametrize("n", OF.TWIN_N)
+def test_rmsprop_forms(on_cpu, n):
+    OF.body_rmsprop(n)
+
+
+@pytest.mark.parametrize("kind", OF.NONFINITE)
+def test_optimizers_nan_inf_and_overflowing_gradients(on_cpu, kind):
+    OF.body_nonfinite(kind)
+
+
+@pytest.mark.parametrize("preset", OF.COUNTER_PRESETS)
+def test_adam_device_counter(on_cpu, preset):
+    OF.body_dev_counter(preset)
+
+
+def test_adam_multi_and_guard_forms(on_cpu):
+    for case_id in sorted(OF.MULTI):
+        OF.body_multi(case_id)
+    OF.body_multi_refusals()
+    OF.body_guard()
+
+
+def test_clamp_forms_keep_nan(on_cpu):
+    for n in OF.CLAMP_N:
+        OF.body_clamp(n)
+    for nt in OF.CLAMP_MULTI:
+        OF.body_clamp_multi(nt)
+    OF.body_clip_nan()
+
+
+def test_elementwise_forms(on_cpu):
+    for n in OF.REDUCE_N:
+        OF.body_reduce(n)
+    for n in OF.ACT_N:
+        OF.body_act(n)
+    for S in OF.ROWSUM_S:
+        OF.body_act_rowsum(S)
+    for L_ in OF.ROWS_L:
+        OF.body_rows(L_)
+    for n in OF.AXPBY_N:
+        OF.body_axpby(n)
 
 
 def test_activations_and_reductions(on_cpu):
